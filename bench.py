@@ -10,7 +10,7 @@ every base, followed by the all-gather of the DELFI bin vector (N > 1).
 Fragments are synthetic (seeded, BASELINE.md section 4 distribution), generated
 on the device and resident in HBM before the timed region starts.
 
-    python bench.py --gpus N --steps K --warmup W [--depth 30] [--contigs 1,2,...]
+    python bench.py --gpus N --steps K --warmup W [--depth 30] [--contigs 1,2,...] [--dump-outputs DIR]
 
 Prints ONE JSON line on rank 0.
 """
@@ -48,7 +48,11 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-end-to-end", action="store_true", help="skip the file -> result legs (end_to_end in the JSON)")
     ap.add_argument("--no-kernel-rows", action="store_true", help="skip the next-row / BAM-mode kernel rooflines (tools/kernel_rows.py)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (rank 0)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if os.environ.get("FTK_BENCH_WATCHDOG"):  # debugging aid: dump every thread's stack and exit after <seconds>
         import faulthandler
         faulthandler.dump_traceback_later(float(os.environ["FTK_BENCH_WATCHDOG"]), exit=True)
@@ -417,6 +421,9 @@ def main():
         for timed, host_s, e0, e1 in trace:
             sys.stderr.write(f"step timed={int(timed)} host_enqueue={host_s * 1e3:7.3f} ms  gpu={e0.elapsed_time(e1):7.3f} ms\n")
     value = bins_all * args.steps / dt
+    if args.dump_outputs and rank == 0:
+        dump_outputs(torch, dev, args.dump_outputs, all_cov, all_hist, all_over, gather_in[:, :rows_rank], all_wps,
+                     [(per[c]["wps_off"], per[c]["b"] - per[c]["a"]) for c in mine], gather_out)
 
     # ---- roofline of the dominant kernel (WPS), from the last timed step -------
     wps_bytes = 0
@@ -574,6 +581,53 @@ def main():
             pass
         sys.stdout.flush()
         print(json.dumps(out), flush=True)
+
+
+DUMP_SEED = 20240917
+DUMP_HIST_ROWS = 4096            # sampled rows of the length histogram (x 1001 bins, float32: 16 MB)
+DUMP_WPS_SEGMENTS = (256, 8192)  # sampled runs of consecutive WPS scores (float64: 16 MB)
+
+
+def dump_outputs(torch, dev, outdir, cov, hist, over, delfi, wps, wps_units, gathered):
+    """--dump-outputs: the arrays the timed step leaves for its caller, as float32 / float64 .npy files under 64 MB
+    in all.  Per-window rows are written whole; the length histogram and the per-base WPS scores are a fixed, seeded
+    sample (the same rows and bases for the same arguments), plus the histogram's column sums over every window.
+    ``wps_units`` lists (offset, bases) of each unit's scores in ``wps``, whose padding between units is not written
+    by the step and never sampled."""
+    torch.cuda.synchronize()
+    os.makedirs(outdir, exist_ok=True)
+    rng = np.random.default_rng(DUMP_SEED)
+    n_rows = int(cov.numel())
+    rows = np.sort(rng.choice(n_rows, size=min(DUMP_HIST_ROWS, n_rows), replace=False))
+    # WPS: runs of consecutive bases in the rank's scores with the units back to back (a run may cross into the next unit)
+    offs = np.array([o for o, _ in wps_units], np.int64)
+    lens = np.array([n for _, n in wps_units], np.int64)
+    ends = np.cumsum(lens)
+    n_seg, seg = DUMP_WPS_SEGMENTS
+    seg = min(seg, int(ends[-1]))
+    starts = np.sort(rng.integers(0, int(ends[-1]) - seg + 1, n_seg))
+    v = (starts[:, None] + np.arange(seg)).ravel()
+    u = np.searchsorted(ends, v, side="right")
+    idx = torch.from_numpy(offs[u] + v - (ends[u] - lens[u])).to(dev)
+    host = lambda t: t.cpu().numpy()
+    out = {
+        "coverage": host(cov).astype(np.float64),
+        "fraglen_overflow": host(over).astype(np.float64),
+        "fraglen_hist_total": host(hist.sum(dim=0, dtype=torch.int64)).astype(np.float64),
+        "fraglen_hist_rows": rows.astype(np.float64),
+        "fraglen_hist_sample": host(hist[torch.from_numpy(rows).to(dev)]).astype(np.float32),
+        "delfi_short": host(delfi[0]).astype(np.float64),
+        "delfi_long": host(delfi[1]).astype(np.float64),
+        "wps_sample_starts": starts.astype(np.float64),
+        "wps_sample": host(wps[idx]).reshape(n_seg, seg).astype(np.float64),
+    }
+    if gathered is not None:  # N ranks: the all-gathered DELFI (short, long) rows of every rank
+        out["delfi_gathered"] = host(gathered).astype(np.float64)
+    total = sum(a.nbytes for a in out.values())
+    if total > 64 << 20:
+        raise SystemExit(f"bench.py: --dump-outputs would write {total} bytes, more than 64 MB")
+    for name, a in out.items():
+        np.save(os.path.join(outdir, name + ".npy"), a)
 
 
 def rep_summary(runs):

@@ -13,7 +13,7 @@ def test_decoder_under_asan_ubsan(tmp_path):
     if not os.path.exists(hipcc):
         pytest.skip("hipcc not available")
     exe = str(tmp_path / "decode_sanitize")
-    cmd = [hipcc, "-x", "c++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-omit-frame-pointer",
+    cmd = [hipcc, "-x", "c++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-gpu-sanitize", "-fno-omit-frame-pointer",
            "-D__HIP_PLATFORM_AMD__", f"-I{ROOT}/include", f"-I{ROOT}/finaletoolkit_amd/csrc", "-I/opt/rocm/include",
            os.path.join(ROOT, "tests", "native", "decode_sanitize.cpp"),
            os.path.join(ROOT, "finaletoolkit_amd", "csrc", "ftk_decode.cpp"),
@@ -44,7 +44,7 @@ def test_decoder_pipeline_under_tsan(tmp_path):
     if not os.path.exists(hipcc):
         pytest.skip("hipcc not available")
     exe = str(tmp_path / "decode_tsan")
-    cmd = [hipcc, "-x", "c++", "-O1", "-g", "-std=c++17", "-fsanitize=thread", "-fno-omit-frame-pointer",
+    cmd = [hipcc, "-x", "c++", "-O1", "-g", "-std=c++17", "-fsanitize=thread", "-fno-gpu-sanitize", "-fno-omit-frame-pointer",
            "-D__HIP_PLATFORM_AMD__", f"-I{ROOT}/include", f"-I{ROOT}/finaletoolkit_amd/csrc", "-I/opt/rocm/include",
            os.path.join(ROOT, "tests", "native", "decode_sanitize.cpp"),
            os.path.join(ROOT, "finaletoolkit_amd", "csrc", "ftk_decode.cpp"),
@@ -70,7 +70,8 @@ def test_decoder_pipeline_under_tsan(tmp_path):
         frags[name] = (s, s + rng.integers(210, 600, n), rng.integers(0, 61, n), rng.integers(0, 2, n).astype(bool))
     bam = str(tmp_path / "multi.bam")
     write_synthetic_bam(bam, contigs, frags)
-    env = dict(os.environ, TSAN_OPTIONS="halt_on_error=0", FTK_STREAM_PIECE="65536", FTK_BAM_STRETCH="4096")
+    env = dict(os.environ, TSAN_OPTIONS="halt_on_error=0:suppressions=" + os.path.join(ROOT, "tests", "native", "tsan.supp"),
+               FTK_STREAM_PIECE="65536", FTK_BAM_STRETCH="4096")
     r = subprocess.run([exe, "--files", text, bam], capture_output=True, text=True, env=env, timeout=600)
     assert r.returncode == 0 and "decode_sanitize ok" in r.stdout, (r.stdout[-500:], r.stderr[-2000:])
     assert "ThreadSanitizer" not in r.stderr, r.stderr[-3000:]
