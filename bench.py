@@ -10,9 +10,13 @@ every base, followed by the all-gather of the DELFI bin vector (N > 1).
 Fragments are synthetic (seeded, BASELINE.md section 4 distribution), generated
 on the device and resident in HBM before the timed region starts.
 
-    python bench.py --gpus N --steps K --warmup W [--depth 30] [--contigs 1,2,...] [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--depth 30] [--contigs 1,2,...] [--dump-outputs DIR] [--full]
 
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0.  A plain run does only what the headline needs: set-up, warm-up, the timed steps,
+--dump-outputs and the line (with the roofline of the last timed step and the checks of its results).  --full adds
+what takes runs of its own: the CPU baselines (``cpu_baseline``), the kernel rows (``next_rows``,
+``roofline.bam_kernels``) and the file -> result legs (``end_to_end``); --no-cpu-baseline, --no-kernel-rows and
+--no-end-to-end leave single ones out of a --full run.
 """
 from __future__ import annotations
 
@@ -44,15 +48,19 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--depth", type=float, default=30.0)
     ap.add_argument("--contigs", type=str, default="", help="comma list (default: b37 1-22,X,Y)")
-    ap.add_argument("--cpu-seconds", type=float, default=20.0, help="budget of the CPU baseline sample")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-end-to-end", action="store_true", help="skip the file -> result legs (end_to_end in the JSON)")
-    ap.add_argument("--no-kernel-rows", action="store_true", help="skip the next-row / BAM-mode kernel rooflines (tools/kernel_rows.py)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run the CPU baselines, the kernel rows and the file -> result legs")
+    ap.add_argument("--cpu-seconds", type=float, default=20.0, help="budget of the CPU baseline sample (--full)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baselines")
+    ap.add_argument("--no-end-to-end", action="store_true", help="--full without the file -> result legs (end_to_end in the JSON)")
+    ap.add_argument("--no-kernel-rows", action="store_true", help="--full without the next-row / BAM-mode kernel rooflines (tools/kernel_rows.py)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (rank 0)")
     args = ap.parse_args()
     if args.steps < 1:
         ap.error("--steps must be at least 1")
+    if not args.full:  # a plain run: the headline alone
+        args.no_cpu_baseline = args.no_end_to_end = args.no_kernel_rows = True
     if os.environ.get("FTK_BENCH_WATCHDOG"):  # debugging aid: dump every thread's stack and exit after <seconds>
         import faulthandler
         faulthandler.dump_traceback_later(float(os.environ["FTK_BENCH_WATCHDOG"]), exit=True)

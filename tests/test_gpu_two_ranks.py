@@ -294,13 +294,27 @@ def test_bench_gpus_n_never_runs_fewer_ranks(tmp_path):
     assert r.returncode != 0 and "must agree" in r.stderr
 
 
+def test_bench_plain_run_is_the_headline_alone():
+    """Without --full, bench.py prints the headline line (with the last timed step's roofline and the checks of its
+    results) and runs nothing else: no CPU baseline, no kernel rows, no file -> result legs."""
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", "2", "--warmup", "1", "--contigs", "21,22"],
+                       cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    line = json.loads(r.stdout.strip().splitlines()[-1])
+    assert line["unit"] == "windows/s" and line["value"] > 0 and line["ms_per_step"] > 0 and line["higher_is_better"]
+    assert line["n_gpus"] == 1 and line["checks"] and all(line["checks"].values()), line["checks"]
+    assert line["roofline"]["achieved"] > 0 and "bam_kernels" not in line["roofline"]
+    assert line["cpu_baseline"] is None and line["next_rows"] is None and line["end_to_end"] is None
+
+
 def test_bench_two_ranks_share_the_gpu():
     """bench.py's own N-rank path (unit split, per-rank launches, all-gather of the DELFI vector) with two ranks
     on GPU 0: one JSON line from rank 0, n_gpus 2, every check true."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env.update(FTK_BENCH_SHARE_GPU="1")
     r = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--steps", "2", "--warmup", "1", "--contigs",
-                        "20,21,22", "--no-cpu-baseline"], cwd=ROOT, env=env, capture_output=True, text=True,
+                        "20,21,22", "--no-cpu-baseline", "--full"], cwd=ROOT, env=env, capture_output=True, text=True,
                        timeout=1500)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])
@@ -324,7 +338,7 @@ def test_bench_eight_ranks_share_the_gpu():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env.update(FTK_BENCH_SHARE_GPU="1")
     r = subprocess.run([sys.executable, "bench.py", "--gpus", "8", "--steps", "2", "--warmup", "1", "--contigs",
-                        "17,18,19,20,21,22,X,Y", "--no-cpu-baseline"], cwd=ROOT, env=env, capture_output=True, text=True,
+                        "17,18,19,20,21,22,X,Y", "--no-cpu-baseline", "--full"], cwd=ROOT, env=env, capture_output=True, text=True,
                        timeout=2400)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])
@@ -495,7 +509,7 @@ def test_bench_under_torch_distributed_run():
     env.update(FTK_BENCH_SHARE_GPU="1", FTK_BENCH_WATCHDOG="500")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                         "--master-addr", "127.0.0.1", "--master-port", str(port), "bench.py", "--gpus", "2", "--steps", "2",
-                        "--warmup", "1", "--contigs", "21,22", "--no-cpu-baseline"], cwd=ROOT, env=env, capture_output=True,
+                        "--warmup", "1", "--contigs", "21,22", "--no-cpu-baseline", "--full"], cwd=ROOT, env=env, capture_output=True,
                        text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads([x for x in r.stdout.strip().splitlines() if x.startswith("{")][-1])

@@ -14,7 +14,7 @@ Each leg: repetitions (first / median / best), the stage split the function repo
 `results_ok` against the oracle on one whole contig (checker only, untimed), a floor and the reference-shaped
 single-thread Python rate of the same unit of work on a small sample.
 
-`bench.py` imports `measure`; run alone (`python tools/cmd_legs.py [--scale 0.1]`) it writes its own genome file.
+`bench.py --full` imports `measure`; run alone (`python tools/cmd_legs.py [--scale 0.1]`) it writes its own genome file.
 """
 from __future__ import annotations
 

@@ -6,7 +6,7 @@
   bam_kernels  the window-feature blocks, the WPS tiles and the merged launch on a chr1-sized 60x contig WITH read1 columns
                (the BAM fetch rule, io/alignment.py:242-268): the kernels of BASELINE config 5.
 
-``bench.py`` calls ``measure()`` for its ``next_rows`` / ``roofline.bam_kernels`` entries; run as a script (under
+``bench.py --full`` calls ``measure()`` for its ``next_rows`` / ``roofline.bam_kernels`` entries; run as a script (under
 ``rocprofv3 --kernel-trace --stats`` or ``--pmc`` for the summaries in profiles/) it prints the same dict as JSON.
 usage: python3 tools/kernel_rows.py [next|bam|all] [reps=5]
 
