@@ -27,14 +27,19 @@ struct BamRow {
 enum BamRule : int {
     kBamNotFragment = 0,  // filtered by flag, read2, TLEN 0, or a record whose CIGAR does not fit its block_size
     kBamFragment = 1,
-    // the reference yields a fragment the columns cannot hold: a negative start (reference_end + TLEN < 0) or a
-    // coordinate beyond int32.  Dropped and COUNTED (ftk_fragstream_skipped / ftk_fragtable_skipped): the Python
-    // surface warns, the reference would have kept the fragment.
+    // the reference yields a fragment the columns cannot hold: a negative start (reference_end + TLEN < 0), or the
+    // fragment's or read1's end at or beyond kBamCoordLimit.  Dropped and COUNTED (ftk_fragstream_skipped /
+    // ftk_fragtable_skipped): the Python surface warns, the reference would have kept the fragment; the rest of the
+    // contig loads.
     kBamUnrepresentable = 2,
     // read1 without a CIGAR and TLEN < 0: the reference evaluates `None + tlen` (io/alignment.py:257) and raises
     // TypeError.  Dropped and counted; the Python surface raises TypeError like the reference.
     kBamNoCigarReverse = 3,
 };
+
+// Coordinates a contig's columns hold: below 2^30 (kPadCoord, ftk_internal.h - the value that pads them; the loader
+// refuses a contig whose largest end reaches it).
+constexpr long long kBamCoordLimit = 1ll << 30;
 
 // r: the record behind its block_size field (bs bytes).  RD32 reads a little-endian uint32 at an unaligned address.
 template <class RD32>
@@ -69,7 +74,8 @@ FTK_BAMRULE_HD int bam_rule(const uint8_t* r, uint32_t bs, RD32 rd32, BamRow& f)
         fs = end_pos + tlen;
         fe = end_pos;
     }
-    if (fs < 0 || fe < 0 || fs > INT32_MAX || fe > INT32_MAX || end_pos > INT32_MAX) return kBamUnrepresentable;
+    // (fs < fe: the fragment then lies in [0, kBamCoordLimit), read1's end below it too)
+    if (fs < 0 || fe >= kBamCoordLimit || end_pos >= kBamCoordLimit) return kBamUnrepresentable;
     f.fs = (int32_t)fs;
     f.fe = (int32_t)fe;
     f.r1s = pos;

@@ -347,6 +347,9 @@ bool ftk_fragstream::run_bam(RawBuf& buf, size_t n_first) {
             clk.lap(5);  // "other" holds the chain check (and any redone range)
             for (auto& st : seg)
                 for (auto& r : st.runs) {
+                    // (counted for every contig: a pass that takes over from the device pass counts the file anew)
+                    skipped[0] += r.c.skipped[0];
+                    skipped[1] += r.c.skipped[1];
                     if (emitted_refs.count(r.ref)) continue;  // handed out by the device pass this one replaces
                     if (cur_ref >= 0 && r.ref != cur_ref) {
                         clk.lap(3);
@@ -364,8 +367,6 @@ bool ftk_fragstream::run_bam(RawBuf& buf, size_t n_first) {
                         cur.length = ref_lens[r.ref];
                     }
                     cur_rows += r.c.start.size();
-                    skipped[0] += r.c.skipped[0];
-                    skipped[1] += r.c.skipped[1];
                     if (!r.c.start.empty()) cur.parts.push_back(std::move(r.c));  // sorted / gathered by the packer
                 }
             clk.lap(3);

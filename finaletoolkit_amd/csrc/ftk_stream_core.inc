@@ -839,6 +839,9 @@ void ftk_fragstream::run_guarded() {
             first_skip = 0;
             ahead_ok = !has_only;
             reads_issued = 0;
+            // the second pass parses every record of the file again, those of the contigs handed out included
+            skipped[0] = 0;
+            skipped[1] = 0;
             rewind(fp);
         };
         if (!ok && want_device_retry && !stopped && bam) {
@@ -859,6 +862,8 @@ void ftk_fragstream::run_guarded() {
             partial_tail_ok = false;
             first_skip = 0;
             ahead_ok = !has_only;
+            skipped[0] = 0;  // (run_bam counts every contig's records again, those handed out included)
+            skipped[1] = 0;
             rewind(fp);
             const size_t n2 = fill(buf, 0);
             ok = run_bam(buf, n2);

@@ -394,8 +394,10 @@ def frag_length_intervals(input_file, interval_file: str, output_file: str | Non
         if failed:
             raise failed[0]
         clock.lap("result_rows_tail")
-        for c in by_contig:  # contigs the file does not hold: the error the reference's fetch raises (ValueError)
+        for c, idx in by_contig.items():  # contigs the file does not hold: the error the reference's fetch raises (ValueError)
             src.require(c)
+            # a header contig without a usable read (never fed): every interval's row is all -1 (:202-238)
+            _result_rows(results, intervals, np.asarray(idx, dtype=np.int64), np.zeros((len(idx), 7)), lines)
     else:
         plan = sharding.IntervalPlan([iv[0] for iv in intervals], iv_starts.tolist(), iv_stops.tolist())
         local, err = {}, None

@@ -106,7 +106,8 @@ def _check_skipped(lib, stream, path: str, seen: list) -> None:
                         "is None for them, and the reference fails the same way at io/alignment.py:257)")
     if out[0] > seen[0]:
         warnings.warn(f"{path}: {out[0] - seen[0]} read1 record(s) whose fragment starts before position 0 "
-                      "(reference_end + TLEN < 0) or lies beyond 2^31 were dropped; the reference keeps such "
+                      "(reference_end + TLEN < 0) or that reaches 2^30 (the largest coordinate held here) were "
+                      "dropped; the reference keeps such "
                       "fragments", UserWarning, stacklevel=3)
         seen[0] = out[0]
 

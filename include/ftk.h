@@ -196,9 +196,10 @@ int64_t ftk_fragstream_ref_length(ftk_fragstream* s, int i);
 int ftk_fragstream_stage_ms(ftk_fragstream* s, double out[6]);
 /* BAM records met so far (cumulative; read it after every ftk_fragstream_next, the final one included) that the
  * reference does NOT simply skip and this library cannot turn into a row (csrc/ftk_bamrule.h):
- *   out[0]  read1 records whose fragment the int32 columns cannot hold - a NEGATIVE start (reference_end + TLEN < 0,
- *           io/alignment.py:257) or a coordinate beyond 2^31 - 1.  The reference yields such a fragment; here it is
- *           dropped and counted (the Python surface issues a UserWarning).
+ *   out[0]  read1 records whose fragment the columns cannot hold - a NEGATIVE start (reference_end + TLEN < 0,
+ *           io/alignment.py:257), or a fragment or read1 alignment that ends at or beyond 2^30 (the largest end a
+ *           contig's columns hold: ftk_frags_from_host refuses a contig beyond it).  The reference yields such a fragment; here it is dropped and
+ *           counted (the Python surface issues a UserWarning) and the rest of its contig loads.
  *   out[1]  read1 records WITHOUT a CIGAR and TLEN < 0.  pysam's reference_end is None for them and the reference
  *           raises TypeError at io/alignment.py:257; here they are dropped and counted (the Python surface raises
  *           TypeError).  A CIGAR-less read1 with TLEN > 0 is a fragment, as in the reference (:253-255).

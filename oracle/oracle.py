@@ -201,11 +201,12 @@ def c_cleavage(fr: Frags, adj_start, adj_stop, min_len=None, max_len=None, mapq_
 # BAM records -> rows (restates io/alignment.py:60-71,242-268 over records read with gzip + struct; pinned to the
 # reference's own code by tests/golden/bam.json.gz, oracle/gen_golden_bam.py)
 # ---------------------------------------------------------------------------
-def bam_rows(path, read1_only=True):
+def bam_rows(path, read1_only=True, count_nocigar=False):
     """``(names, lengths, {contig: rows})``: per contig the rows ``(fs, fe, mapq, fwd, r1s, r1e)`` the reference's
     ``_fetch_sam`` yields for a whole-contig fetch at ``quality_threshold=0``, in FILE order; ``[r1s, r1e)`` is the
     alignment htslib's region iterator tests (``bam_endpos``: a reference length of 0 counts as 1).  Raises TypeError
-    where the reference does (a CIGAR-less read1 with TLEN < 0: ``None + tlen``, :257)."""
+    where the reference does (a CIGAR-less read1 with TLEN < 0: ``None + tlen``, :257) - unless ``count_nocigar``:
+    such records are then left out and counted, and a fourth item ``{contig: count}`` is returned."""
     import gzip
     import struct
     with gzip.open(path, "rb") as fh:
@@ -222,6 +223,7 @@ def bam_rows(path, read1_only=True):
         lengths.append(struct.unpack_from("<i", data, o + 4 + l_name)[0])
         o += 8 + l_name
     out = {n: [] for n in names}
+    nocigar = {n: 0 for n in names}
     while o + 4 <= len(data):
         (bs,) = struct.unpack_from("<i", data, o)
         ref_id, pos, l_name, mapq, _bin, n_cigar, flag, _l_seq, _nref, _npos, tlen = struct.unpack_from("<iiBBHHHiiii", data, o + 4)
@@ -241,10 +243,15 @@ def bam_rows(path, read1_only=True):
         if tlen > 0:                                      # :253-255
             fs, fe = pos, pos + tlen
         elif tlen < 0:                                    # :256-258
+            if reference_end is None and count_nocigar:
+                nocigar[names[ref_id]] += 1
+                continue
             fs, fe = reference_end + tlen, reference_end
         else:
             continue
         out[names[ref_id]].append((fs, fe, mapq, 0 if flag & 0x10 else 1, pos, end_pos))
+    if count_nocigar:
+        return names, lengths, out, nocigar
     return names, lengths, out
 
 

@@ -249,8 +249,9 @@ def bam_record(ref_id, pos, mapq, flag, cigar, tlen, name, l_seq=None, mate_ref=
         l_seq = sum(n for op, n in cigar if op in (0, 1, 4, 7, 8))
     rlen = 0 if flag & 0x4 else sum(n for op, n in cigar if op in (0, 2, 3, 7, 8))
     nm = name.encode() + b"\0"
-    body = struct.pack("<iiBBHHHiiii", ref_id, pos, len(nm), mapq, bam_reg2bin(max(pos, 0), max(pos, 0) + (rlen or 1)),
-                       len(cigar), flag, l_seq, ref_id if mate_ref is None else mate_ref, mate_pos, tlen)
+    b = max(pos, 0)
+    bin_ = bam_reg2bin(b, b + (rlen or 1)) if b + (rlen or 1) <= 1 << 29 else 4680  # (no BAI bin beyond 2^29)
+    body = struct.pack("<iiBBHHHiiii", ref_id, pos, len(nm), mapq, bin_, len(cigar), flag, l_seq, ref_id if mate_ref is None else mate_ref, mate_pos, tlen)
     body += nm + b"".join(struct.pack("<I", (n << 4) | op) for op, n in cigar)
     body += b"\x12" * ((l_seq + 1) // 2) + b"\x1e" * l_seq + aux
     return struct.pack("<i", len(body)) + body
@@ -275,3 +276,176 @@ def write_bam(path, contigs, records, level=6):
     bgzf.write_index(str(path) + ".bai", True,
                      [(c, bgzf.virtual_offset(offsets, spans.get(k, (0, 0))[0]), bgzf.virtual_offset(offsets, spans.get(k, (0, 0))[1]))
                       for k, (c, _) in enumerate(contigs)])
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Seeded adversarial BAMs: what the record rule (csrc/ftk_bamrule.h) and the record chain of the device parser
+# (csrc/ftk_bamparse.hip) meet in the wild and worse.  The expectations come from oracle.bam_rows, never from the
+# library's own decoders.
+# ---------------------------------------------------------------------------------------------------------------------
+BAM_COORD_LIMIT = 1 << 30  # the library's columns hold coordinates below 2^30: a fragment beyond is dropped and counted
+_PROPER = (99, 83, 147, 163, 67, 115, 131, 179)  # paired + proper pair: read1 / read2 on either strand
+
+
+def _fuzz_cigar(rng):
+    """[(op, length)] over all ten ops: none, only ops that consume no reference, a few ops, or up to ~300."""
+    k = rng.random()
+    if k < 0.04:
+        return []
+    if k < 0.08:
+        return [(int(rng.choice([1, 4, 5, 6])), int(rng.integers(1, 60))) for _ in range(int(rng.integers(1, 4)))]
+    n = int(rng.integers(1, 8)) if k < 0.97 else int(rng.integers(8, 300))
+    return list(zip(rng.integers(0, 10, n).tolist(), rng.integers(1, 40 if n > 8 else 150, n).tolist()))
+
+
+def _fuzz_flag(rng):
+    k = rng.random()
+    if k < 0.75:
+        return int(rng.choice(_PROPER)) | int(rng.choice([0, 0, 0, 0x20]))
+    if k < 0.85:
+        return 1 << int(rng.integers(0, 12))  # every flag bit alone
+    return int(rng.integers(0, 1 << 12))      # and in random combinations
+
+
+def _fuzz_name(rng, lo=1, hi=254):
+    return rng.integers(33, 127, int(rng.integers(lo, hi + 1))).astype(np.uint8).tobytes().decode()
+
+
+def fuzz_record(rng, ref_id, pos, prev=None):
+    """One adversarial alignment record at ``pos``.  ``prev``: the bytes of the record before it, of which a B or Z tag
+    may carry a copy of the first 36+ bytes (a plausible fake record chain for guess_record_start; no decoder here reads
+    the aux fields, so the copy is taken raw)."""
+    import struct
+    cigar = _fuzz_cigar(rng)
+    rlen = sum(n for op, n in cigar if op in (0, 2, 3, 7, 8))
+    k = rng.random()
+    if k < 0.4:
+        tlen = int(rng.integers(max(rlen, 1), max(rlen, 1) + 600))
+    elif k < 0.8:
+        tlen = -int(rng.integers(max(rlen, 1), max(rlen, 1) + 600))
+    elif k < 0.86:
+        tlen = 0
+    else:
+        tlen = int(rng.integers(-100_000, 100_000))  # inconsistent with the alignment
+    if not cigar:
+        tlen = abs(tlen)  # (a CIGAR-less read1 with TLEN < 0 makes the reference raise: write_nocigar_bam's file alone)
+    k = rng.random()
+    l_seq = 0 if k < 0.05 else int(rng.integers(16_000, 20_000)) if k < 0.053 else None  # some records > a 16 KB stretch
+    aux = b""
+    if prev is not None and rng.random() < 0.08:
+        cp = prev[:int(rng.integers(36, min(len(prev), 120) + 1))]
+        aux = b"XBBC" + struct.pack("<I", len(cp)) + cp if rng.random() < 0.5 else b"XZZ" + cp + b"\0"
+    return bam_record(ref_id, pos, int(rng.integers(0, 256)), _fuzz_flag(rng), cigar, tlen, _fuzz_name(rng), l_seq=l_seq,
+                      mate_pos=pos, aux=aux)
+
+
+def _negative_start(rng, ref_id, pos):
+    """A reverse read1 of a proper pair whose fragment starts before position 0 (reference_end + TLEN < 0)."""
+    rl = int(rng.integers(20, 120))
+    return bam_record(ref_id, pos, int(rng.integers(0, 256)), 83, [(4, 3), (0, rl)], -(pos + rl + int(rng.integers(1, 300))),
+                      _fuzz_name(rng, 4, 20))
+
+
+def _rejected(rng, ref_id, pos):
+    """A record the reference never turns into a fragment: read2, a rejecting flag bit, or TLEN 0."""
+    flag, tlen = [(147, -200), (163, 200), (99 | 0x400, 200), (99 | 0x100, 200), (99 | 0x800, 200), (99 | 0x4, 200),
+                  (97, 200), (99 | 0x8, 200), (99 | 0x200, 200), (65, 200), (99, 0), (83, 0)][int(rng.integers(0, 12))]
+    return bam_record(ref_id, pos, int(rng.integers(0, 256)), flag, [(0, 100)], tlen, _fuzz_name(rng, 4, 40))
+
+
+def _lite(rng, ref_id, pos):
+    """A short proper pair (read1 and read2, 50 bases): many contig runs fit in one piece."""
+    return [bam_record(ref_id, pos, 60, flag, [(0, 50)], tlen, "r%d" % int(rng.integers(0, 1 << 30)))
+            for flag, tlen in ((99, 200), (147, -200))]
+
+
+def fuzz_contig_records(rng, ref_id, length, n, negative=0, kind="fuzz"):
+    """``[(ref_id, pos, bytes)]`` of one contig in coordinate order: ``n`` records of ``kind`` ("fuzz", "rejected",
+    "lite": a short pair each) plus ``negative`` negative-start fragments among the first positions."""
+    pos = np.sort(rng.integers(0, max(length - 1, 1), n)).tolist()
+    neg = sorted(rng.integers(0, min(length, 400), negative).tolist())
+    items = sorted([(p, 1) for p in pos] + [(p, 0) for p in neg])
+    out, prev = [], None
+    for p, normal in items:
+        if not normal:
+            bs = [_negative_start(rng, ref_id, p)]
+        elif kind == "rejected":
+            bs = [_rejected(rng, ref_id, p)]
+        elif kind == "lite":
+            bs = _lite(rng, ref_id, p)
+        else:
+            bs = [fuzz_record(rng, ref_id, p, prev)]
+        for b in bs:
+            out.append((ref_id, p, b))
+            prev = b
+    return out
+
+
+def unplaced_records(rng, n):
+    """Unmapped reads without a reference (ref_id -1, pos -1): they close a coordinate-sorted BAM."""
+    return [(-1, -1, bam_record(-1, -1, 0, int(rng.choice([77, 141, 4])), [], 0, _fuzz_name(rng, 1, 60),
+                                l_seq=int(rng.integers(0, 150)), mate_pos=-1)) for _ in range(n)]
+
+
+def write_fuzz_bam(path, seed, layout, unplaced=0, level=6):
+    """A seeded adversarial BAM.  ``layout``: ``[(name, length, n_records, n_negative_starts, kind)]`` in header order
+    (kind as in ``fuzz_contig_records``).  Returns the header's ``[(name, length)]``."""
+    rng = np.random.default_rng(seed)
+    contigs = [(c, n) for c, n, *_ in layout]
+    records = []
+    for ref_id, (_, length, n, neg, kind) in enumerate(layout):
+        records += fuzz_contig_records(rng, ref_id, length, n, neg, kind)
+    records += unplaced_records(rng, unplaced)
+    write_bam(path, contigs, records, level=level)
+    return contigs
+
+
+def write_nocigar_bam(path, seed):
+    """Fuzzed records around CIGAR-less read1 records with TLEN < 0 (the reference raises TypeError on them)."""
+    rng = np.random.default_rng(seed)
+    contigs = [("chrA", 200_000), ("chrB", 100_000)]
+    records = fuzz_contig_records(rng, 0, 200_000, 3000, 3)
+    for k, p in enumerate((1_000, 50_000, 150_000)):
+        records.append((0, p, bam_record(0, p, 30 + k, 83, [], -250, f"nocig{k}", l_seq=80)))
+    records.append((0, 60_000, bam_record(0, 60_000, 30, 99, [], 250, "nocig_fwd", l_seq=80)))  # TLEN > 0: a fragment
+    records.sort(key=lambda r: r[1])
+    records += fuzz_contig_records(rng, 1, 100_000, 1000)
+    write_bam(path, contigs, records)
+    return contigs
+
+
+def write_top_bam(path, seed):
+    """A contig of 1.1e9 bases whose fragments end at 2^30 - 1, at 2^30 and a little beyond (and one proper pair with a
+    stray TLEN of 1.2e9 near its start), fuzzed records around them, and a normal contig behind it."""
+    rng = np.random.default_rng(seed)
+    top = BAM_COORD_LIMIT
+    contigs = [("chrBig", 1_100_000_000), ("chrAfter", 300_000)]
+    recs = fuzz_contig_records(rng, 0, 1_100_000_000, 4000, 5) + fuzz_contig_records(rng, 0, 3000, 300)
+    for p in range(top - 2_000, top + 50, 97):
+        recs += [(0, p, b) for b in _lite(rng, 0, p)]
+    recs.append((0, 5_000, bam_record(0, 5_000, 60, 99, [(0, 100)], 1_200_000_000, "stray_tlen")))
+    for k, end in enumerate((top - 1, top, top + 1, top + 7, top - 2)):
+        recs.append((0, end - 150, bam_record(0, end - 150, 60, 99, [(0, 100)], 150, f"fwd_end{k}")))   # fe = end
+        recs.append((0, end - 100, bam_record(0, end - 100, 60, 83, [(0, 100)], -300, f"rev_end{k}")))  # fe = end
+    recs.append((0, top - 60, bam_record(0, top - 60, 60, 99, [(0, 100)], 50, "read1_past")))  # fe < 2^30 <= bam_endpos
+    recs.sort(key=lambda r: r[1])
+    recs += fuzz_contig_records(rng, 1, 300_000, 5000, 2)
+    write_bam(path, contigs, recs)
+    return contigs
+
+
+def bam_expected(path):
+    """The reference's rows of a BAM as the library must hold them (oracle.bam_rows, never the library's decoders):
+    ``({contig: (start, end, mapq, fwd, r1s, r1e, file_rank)} in stable start order, [n_dropped, n_nocigar_reverse],
+    {contig: rows in file order}, {contig: [n_dropped, n_nocigar_reverse]})``.  Dropped: the fragments the columns
+    cannot hold - a negative start, or the fragment or its read1 reaching 2^30."""
+    from oracle import oracle as O
+    _, _, rows, nocigar = O.bam_rows(path, count_nocigar=True)
+    want, per = {}, {}
+    for c, rr in rows.items():
+        kept = [r for r in rr if r[0] >= 0 and r[1] < BAM_COORD_LIMIT and r[5] < BAM_COORD_LIMIT]
+        per[c] = [len(rr) - len(kept), nocigar[c]]
+        order = sorted(range(len(kept)), key=lambda j: kept[j][0])  # stable, like the decoder
+        a = np.array([kept[j] for j in order], np.int64).reshape(-1, 6)
+        want[c] = tuple(a[:, k] for k in range(6)) + (np.array(order, np.int64),)
+    return want, [sum(v[0] for v in per.values()), sum(v[1] for v in per.values())], rows, per

@@ -163,6 +163,20 @@ def test_length_intervals(G):
         _stats_equal(g, w)
 
 
+def test_length_intervals_on_a_first_streamed_read(G, monkeypatch):
+    """The same intervals when the BAM is streamed in one pass (FTK_LAZY_SOURCE=0, as without a usable index): chrZ,
+    a header contig without a usable read, gets the reference's all -1 row (interval w62), not None."""
+    monkeypatch.setenv("FTK_LAZY_SOURCE", "0")
+    source.close_all()
+    iv = os.path.join(GOLDEN, "edge_intervals.bed")
+    got = frag.frag_length_intervals(EDGE, iv)
+    assert any(w[0] == "chrZ" for w in G["edge"]["frag_length_intervals"])
+    for g, w in zip(got, G["edge"]["frag_length_intervals"], strict=True):
+        assert g is not None, w[:4]
+        _stats_equal(g, w)
+    source.close_all()
+
+
 @pytest.mark.parametrize("sec", ["fixture", "edge"])
 def test_cleavage(G, A, sec):
     path = PATH[sec]

@@ -360,6 +360,7 @@ from tests.test_abi import _decode
 lib = L.load()
 path = sys.argv[1]
 n_device = [0]
+skipped, ranks = [], {{}}  # per stream: ftk_fragstream_skipped at its end; per contig: the file-order rank
 
 
 def stream(contig=None, threads=4):
@@ -383,15 +384,22 @@ def stream(contig=None, threads=4):
                                                    rank.ctypes.data_as(C.c_void_p)) == 0
             # the file-order rank is a permutation and the rows are in stable start order
             assert rows == 0 or (np.array_equal(np.sort(rank), np.arange(rows)) and np.all(np.diff(cols[0]) >= 0))
+            ranks[name] = rank
             n_device[0] += 1
         else:
             ps = [C.c_void_p() for _ in range(6)]
             assert lib.ftk_fragtable_columns(t, 0, *[C.byref(p) for p in ps]) == 0
             cols = [None if not p.value or rows == 0 else np.ctypeslib.as_array(C.cast(p, C.POINTER(ct)), (rows,)).copy()
                     for p, ct in zip(ps, (C.c_int32, C.c_int32, C.c_uint8, C.c_uint8, C.c_int32, C.c_int32))]
+            p = C.c_void_p()
+            assert lib.ftk_fragtable_order(t, 0, C.byref(p)) == 0
+            ranks[name] = np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_int32)), (rows,)).copy() if rows and p.value else None
         out[name] = (rows, cols, lib.ftk_fragtable_contig_length(t, 0))
         order.append(name)
         lib.ftk_fragtable_free(t)
+    sk = (C.c_int64 * 2)()
+    assert lib.ftk_fragstream_skipped(s, C.byref(sk)) == 0
+    skipped.append(list(sk))
     lib.ftk_fragstream_close(s)
     return out, order
 
