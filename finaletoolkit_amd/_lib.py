@@ -57,6 +57,7 @@ EXPORTS = [
     "ftk_bigwig_fixedstep_sections", "ftk_format_frag_rows", "ftk_bgzf_write", "ftk_synth_bam_contig", "ftk_fill_wps_records", "ftk_bgzf_inflate_device",
     "ftk_comm_unique_id", "ftk_comm_create", "ftk_comm_size", "ftk_allgather_i64", "ftk_allreduce_sum_i64", "ftk_comm_send",
     "ftk_comm_recv", "ftk_comm_join", "ftk_comm_destroy",
+    "ftk_frags_format_rows", "ftk_bgzf_deflate_device", "ftk_frags_write",
 ]
 
 
@@ -88,6 +89,14 @@ class Motif(C.Structure):
                 ("both_strands", C.c_int32), ("negative_strand", C.c_int32), ("guard", C.c_int32),
                 ("rev_oob_is_error", C.c_int32)]
 
+
+class ExportResult(C.Structure):
+    _fields_ = [("n_rows", C.c_int64), ("text_bytes", C.c_int64), ("first_off", C.c_int64), ("end_off", C.c_int64),
+                ("n_linear", C.c_int64), ("linear", C.c_void_p), ("n_runs", C.c_int64), ("run_bin", C.c_void_p),
+                ("run_beg", C.c_void_p), ("run_end", C.c_void_p), ("stage_ms", C.c_double * 5)]
+
+
+LAYOUT = {"frag": 0, "bed6": 1, "bed3": 2}
 
 _lib = None
 
@@ -297,6 +306,10 @@ def load() -> C.CDLL:
     lib.ftk_ref_gc_counts.argtypes = [vp, C.c_int, vp, vp, i64, vp]
     lib.ftk_ref_set_layout.argtypes = [vp, C.c_int, i64, i32, i32, vp, vp, i64]
     lib.ftk_motif_counts.argtypes = [vp, C.c_int, C.c_int, vp, vp, i64, C.POINTER(Motif), i32, i32, vp, vp, vp]
+    lib.ftk_frags_format_rows.argtypes = [vp, C.c_int, C.c_char_p, i32, i32, i32, C.c_int, pp, pi64, pi64]
+    lib.ftk_bgzf_deflate_device.argtypes = [vp, vp, i64, vp, i64, pi64, vp, C.c_int]
+    lib.ftk_frags_write.argtypes = [vp, C.c_int, C.c_char_p, i32, i32, i32, C.c_int, C.c_char_p, C.c_int, C.c_int, C.c_int,
+                                    C.POINTER(ExportResult)]
     lib.ftk_comm_unique_id.argtypes = [C.c_char_p]
     lib.ftk_comm_create.argtypes = [vp, C.c_int, C.c_int, C.c_char_p, C.POINTER(vp)]
     lib.ftk_comm_size.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]

@@ -112,6 +112,50 @@ def write_index(path, bai: bool, spans: list[tuple[str, int, int]], linear=None)
     write_bgzf(path, head + body)
 
 
+def reg2bin(beg: int, end: int) -> int:
+    """The bin of ``[beg, end)`` in the UCSC binning scheme of tabix / BAI (14-bit minimum shift, 5 levels; SAM spec
+    5.3).  An empty interval is binned as ``[beg, beg + 1)``."""
+    end = max(int(end), int(beg) + 1) - 1
+    beg = int(beg)
+    for shift, first in ((14, 4681), (17, 585), (20, 73), (23, 9), (26, 1)):
+        if beg >> shift == end >> shift:
+            return first + (beg >> shift)
+    return 0
+
+
+def write_tabix(path, contigs) -> None:
+    """The full tabix index of a BED-like BGZF file (``TBI\\1``, format 0x10000, columns 1 / 2 / 3, meta ``#``), the
+    one htslib's ``tabix`` / ``pysam.TabixFile.fetch`` search: per contig the binning index, the pseudo-bin 37450 as
+    htslib writes it (chunk = the contig's span, then ``n_mapped = rows, 0``) and the 16 kb linear index.
+
+    ``contigs``: in file order, dicts with ``name``, ``v_begin`` / ``v_end`` (virtual offsets of the contig's first
+    row and behind its last), ``rows``, ``linear`` (uint64 per window, ``linear_index``'s shape) and ``runs`` =
+    ``(bin[], v_begin[], v_end[])``: runs of consecutive rows that share a bin, in file order.  A bin's chunks that
+    touch are merged (so a chunk holds rows of its own bin only).  Contigs without rows are left out."""
+    import numpy as np
+    contigs = [c for c in contigs if c["rows"] > 0]
+    body = b""
+    for c in contigs:
+        bins: dict[int, list] = {}
+        rb, r0, r1 = c["runs"]
+        for b, v0, v1 in zip(np.asarray(rb).tolist(), np.asarray(r0).tolist(), np.asarray(r1).tolist()):
+            chunks = bins.setdefault(int(b), [])
+            if chunks and v0 == chunks[-1][1]:
+                chunks[-1][1] = v1
+            else:
+                chunks.append([v0, v1])
+        body += struct.pack("<i", len(bins) + 1)
+        for b in sorted(bins):
+            body += struct.pack("<Ii", b, len(bins[b]))
+            body += np.asarray(bins[b], dtype="<u8").tobytes()
+        body += struct.pack("<Ii", 37450, 2) + struct.pack("<QQQQ", int(c["v_begin"]), int(c["v_end"]), int(c["rows"]), 0)
+        lin = np.asarray(c["linear"], dtype="<u8")
+        body += struct.pack("<i", len(lin)) + lin.tobytes()
+    names = b"".join(c["name"].encode() + b"\0" for c in contigs)
+    head = b"TBI\1" + struct.pack("<iiiiiiii", len(contigs), 0x10000, 1, 2, 3, ord("#"), 0, len(names)) + names
+    write_bgzf(path, head + body)
+
+
 def write_frag_gz(path, contig_rows, bed6: bool = False, with_tbi_stub: bool = True, level: int = 6,
                   with_index: bool = False) -> None:
     """Write a FinaleDB fragment file (``chrom start stop mapq strand``; BED6

@@ -1174,3 +1174,4 @@ static int wps_params(ftk_ctx* ctx, const ContigData& c, int64_t chrom_size, int
 #include "ftk_api_perbase.inc"
 #include "ftk_api_ref.inc"
 #include "ftk_api_comm.inc"
+#include "ftk_api_export.inc"

@@ -1690,4 +1690,11 @@ void inflate_launch(hipStream_t s, const uint8_t* d_comp, const InflateBlock* d_
     }
 }
 
+// The same CRC kernel for the write direction (ftk_fragtext.hip): tab[k].out_off / out_len name the byte ranges of `data`.
+void crc_launch(hipStream_t s, const InflateBlock* d_tab, int n_blocks, const uint8_t* data, uint32_t* d_crc) {
+    if (n_blocks <= 0) return;
+    const int groups = std::min((n_blocks + kCrcWaves - 1) / kCrcWaves, 1 << 20);
+    hipLaunchKernelGGL(bgzf_crc_kernel, dim3(groups), dim3(64 * kCrcWaves), 0, s, d_tab, n_blocks, data, d_crc);
+}
+
 }  // namespace ftk

@@ -482,6 +482,65 @@ class Engine:
                 return s[:k].copy(), e[:k].copy(), q[:k].copy(), st[:k].copy()
             cap = int(n.value)
 
+    # -- export: columns -> rows -> BGZF on the device (csrc/ftk_fragtext.hip) ----------------------------------
+    @staticmethod
+    def _export_args(print_name, quality_threshold, min_length, max_length, layout):
+        if layout not in L.LAYOUT:
+            raise ValueError(f"layout must be one of {sorted(L.LAYOUT)}, not {layout!r}")
+        f = L.make_filter(quality_threshold, min_length, max_length)
+        return str(print_name).encode(), f.mapq_min, f.min_len, f.max_len, L.LAYOUT[layout]
+
+    def format_rows(self, name: str, print_name: str, quality_threshold=30, min_length=None, max_length=None,
+                    layout="frag"):
+        """``(text bytes, rows)``: the kept fragments of resident contig ``name`` as rows that carry ``print_name``,
+        formatted on the device (``ftk_frags_format_rows``)."""
+        args = self._export_args(print_name, quality_threshold, min_length, max_length, layout)
+        out, n, rows = C.c_void_p(), C.c_int64(), C.c_int64()
+        self._check(self.lib.ftk_frags_format_rows(self.ctx, self.contig_id(name), *args, C.byref(out), C.byref(n),
+                                                   C.byref(rows)))
+        try:
+            return C.string_at(out.value, n.value), int(rows.value)
+        finally:
+            self.lib.ftk_buffer_free(out.value)
+
+    def bgzf_deflate(self, data: bytes, write_eof: bool = True):
+        """``(BGZF image bytes, block offsets int64[n_blocks + 1])`` of ``data``, deflated on the device
+        (``ftk_bgzf_deflate_device``)."""
+        n = len(data)
+        n_blocks = -(-n // 0xFF00)
+        cap = n + 31 * n_blocks + 28  # the stored bound: 18 header + 5 stored-block header + 8 trailer per member
+        out = np.empty(max(cap, 1), np.uint8)
+        offs = np.zeros(n_blocks + 1, np.int64)
+        got = C.c_int64()
+        src = np.frombuffer(data, np.uint8) if n else None
+        self._check(self.lib.ftk_bgzf_deflate_device(self.ctx, L.ptr(src), n, L.ptr(out), cap, C.byref(got), L.ptr(offs),
+                                                     int(bool(write_eof))))
+        return out[: got.value].tobytes(), offs
+
+    def write_contig(self, name: str, print_name: str, path: str, quality_threshold=30, min_length=None,
+                     max_length=None, layout="frag", append=False, write_eof=False, deflate_on_host=False) -> dict:
+        """Append the kept rows of resident contig ``name`` to ``path`` as BGZF members built on the device
+        (``ftk_frags_write``).  Returns ``rows``, ``text_bytes``, ``first_off`` / ``end_off`` (file offsets), the
+        tabix inputs ``linear`` (uint64 virtual offsets per 16 kb window) and ``runs`` = ``(bin int32[], begin
+        uint64[], end uint64[])``, and ``stage_ms`` (format, deflate + CRC, compaction, copy, write)."""
+        args = self._export_args(print_name, quality_threshold, min_length, max_length, layout)
+        res = L.ExportResult()
+        self._check(self.lib.ftk_frags_write(self.ctx, self.contig_id(name), *args, str(path).encode(), int(bool(append)),
+                                             int(bool(write_eof)), int(bool(deflate_on_host)), C.byref(res)))
+
+        def take(p, n, dtype):
+            if not p or n == 0:
+                return np.zeros(0, dtype)
+            try:
+                return np.frombuffer(C.string_at(p, n * np.dtype(dtype).itemsize), dtype).copy()
+            finally:
+                self.lib.ftk_buffer_free(p)
+        nr = int(res.n_runs)
+        return dict(rows=int(res.n_rows), text_bytes=int(res.text_bytes), first_off=int(res.first_off),
+                    end_off=int(res.end_off), linear=take(res.linear, int(res.n_linear), np.uint64),
+                    runs=(take(res.run_bin, nr, np.int32), take(res.run_beg, nr, np.uint64), take(res.run_end, nr, np.uint64)),
+                    stage_ms=[float(v) for v in res.stage_ms])
+
     def wps(self, name: str, start: int, stop: int, chrom_size: int, window_size=120, min_length=120,
             max_length=180, quality_threshold=30, out=None):
         """a7: WPS per base of [start, stop) (frag/_wps.py:156-188)."""

@@ -17,7 +17,7 @@ from .exceptions import InvalidInputError
 from .source import get_engine, open_source
 
 __all__ = ["chrom_sizes_to_list", "chrom_sizes_to_dict", "get_intervals", "overlaps", "frags_in_region", "frag_generator",
-           "frag_array", "agg_bw", "gen_kmers", "reverse_complement", "validate_compatible_contigs", "valid_interval",
+           "frag_array", "frag_export", "agg_bw", "gen_kmers", "reverse_complement", "validate_compatible_contigs", "valid_interval",
            "_none_eq", "_none_geq", "_none_leq"]
 
 FragTuple = Tuple[str, int, int, int, bool]
@@ -151,6 +151,61 @@ def frag_array(input_file, contig: str, quality_threshold: int = 30, start=None,
     if not parts:
         return np.zeros(0, dtype=[("start", "i8"), ("stop", "i8"), ("strand", "?")])
     return np.concatenate(parts)
+
+
+_EXPORT_LAYOUTS = ("frag", "bed6", "bed3")
+
+
+def frag_export(input_file, output_file, contig=None, quality_threshold: int = 30, min_length=None, max_length=None,
+                layout: str = "frag", workers=None, verbose=False) -> dict:
+    """Write the fragments of ``input_file`` (BAM, or a fragment file / BED6) that pass ``mapq >= quality_threshold``
+    and ``min_length <= length <= max_length`` as a tabix-indexed BGZF file ``output_file`` (+ ``.tbi``): rows
+    ``contig start end mapq strand`` (``layout="frag"``), with a ``.`` name column (``"bed6"``) or ``contig start
+    end`` alone (``"bed3"``), sorted by start within a contig, contigs in the order of the input.  Rows are formatted
+    and deflated on the GPU, contig by contig as the input is decoded (``ftk_frags_write``).  Returns
+    ``{contig: rows written}`` for the contigs visited (``contig``: that one alone)."""
+    import os
+    import sys
+    import time
+
+    from . import bgzf, writers
+    from .source import ContigFeed
+    output_file = os.fspath(output_file)
+    writers.check_suffix(output_file, (".gz", ".bgz"), "output_file should have .gz or .bgz as suffix")
+    if output_file == "-":
+        raise ValueError("output_file should have .gz or .bgz as suffix")
+    if layout not in _EXPORT_LAYOUTS:
+        raise ValueError(f"layout must be one of {_EXPORT_LAYOUTS}, not {layout!r}")
+    if os.path.abspath(os.fspath(input_file)) == os.path.abspath(output_file) or (
+            os.path.exists(output_file) and os.path.exists(os.fspath(input_file)) and os.path.samefile(input_file, output_file)):
+        raise ValueError("input_file and output_file are the same file")
+    t0 = time.time()
+    eng = get_engine()
+    feed = ContigFeed(input_file, workers, names=None if contig is None else [str(contig)])
+    written, index, first = {}, [], True
+    try:
+        for src, c in feed:
+            res = eng.write_contig(src.key(c), c, output_file, quality_threshold, min_length, max_length, layout,
+                                   append=not first)
+            first = False
+            written[c] = res["rows"]
+            index.append(dict(name=c, v_begin=res["first_off"] << 16, v_end=res["end_off"] << 16, rows=res["rows"],
+                              linear=res["linear"], runs=res["runs"]))
+            if verbose:
+                sys.stderr.write(f"frag_export: {c}: {res['rows']} rows, {res['text_bytes']} bytes of text -> "
+                                 f"{res['end_off'] - res['first_off']} bytes\n")
+        src = feed.finish()
+    except BaseException:
+        feed.close()
+        raise
+    if contig is not None and str(contig) not in written:
+        src.require(str(contig))  # not in the file: the ValueError of every other command
+    with open(output_file, "ab" if not first else "wb") as fh:
+        fh.write(bgzf._EOF)
+    bgzf.write_tabix(output_file + ".tbi", index)
+    if verbose:
+        sys.stderr.write(f"frag_export: {sum(written.values())} rows in {time.time() - t0:.3f} s\n")
+    return written
 
 
 def agg_bw(input_file, interval_file, output_file, median_window_size: int = 1, mean: bool = False,

@@ -504,6 +504,57 @@ int ftk_motif_counts(ftk_ctx* ctx, int contig_id, int ref_id, const int32_t* w_s
  * same kernel on device-resident pieces: FTK_DEVICE_INFLATE.) */
 int ftk_bgzf_inflate_device(ftk_ctx* ctx, const uint8_t* file_bytes, int64_t n, uint8_t* out, int64_t cap, int64_t* n_out);
 
+/* ---- fragment export: columns -> rows -> BGZF on the device (csrc/ftk_fragtext.hip) -------------------
+ * The write direction of the decoders above: a resident contig's fragments that pass the keep rule
+ * (mapq >= mapq_min, min_len <= end - start <= max_len, FTK_LEN_OPEN = no bound: the length / MAPQ half of
+ * ftk_filter) as text rows in resident order (sorted by start, equal starts in the order they are held), the
+ * file the decoders read (io/alignment.py:270-302):
+ *   FTK_LAYOUT_FRAG  "<contig>\t<start>\t<end>\t<mapq>\t<+|->\n"
+ *   FTK_LAYOUT_BED6  the same with a "." name column before mapq
+ *   FTK_LAYOUT_BED3  "<contig>\t<start>\t<end>\n"
+ * `name` is the contig name to print (1..255 bytes).  A contig's text must stay below 4 GB.
+ *   ftk_frags_format_rows    the formatter alone: the rows in library-owned host memory (*out, ftk_buffer_free;
+ *                            NUL-terminated), *out_len bytes, *n_rows kept rows (may be NULL).  The bytes are those of
+ *                            ftk_format_frag_rows for the kept rows (bed3: its first three columns).
+ *   ftk_bgzf_deflate_device  the mirror of ftk_bgzf_inflate_device: n host bytes in, a BGZF image out - one member
+ *                            per 0xFF00 bytes (18-byte header with BSIZE, raw DEFLATE: per block the smallest of
+ *                            stored / fixed / dynamic codes, CRC-32, ISIZE), the 28-byte EOF block when write_eof.
+ *                            *n_out = bytes of the image; FTK_ERR_INVALID (with *n_out set) when cap is too small.
+ *                            block_offsets (may be NULL): ceil(n / 0xFF00) + 1 entries, as ftk_bgzf_write's.  The
+ *                            image depends on the input alone.  At most 4 GB per call.
+ *   ftk_frags_write          format, deflate, compact on the device, one copy to the host, one write: the contig's
+ *                            members are appended to `path` (append == 0: the file is created / truncated first) and
+ *                            the EOF block behind them when write_eof; the text never visits the host.  A contig
+ *                            starts on a fresh block, so its virtual offset is its first member's file offset.
+ *                            deflate_on_host != 0 or FTK_EXPORT_DEFLATE=host: the same text goes through
+ *                            ftk_bgzf_write at level 1 instead (the A/B and size yardstick).  *res receives what a
+ *                            tabix index needs; its four arrays are library-owned (ftk_buffer_free each; NULL when
+ *                            the contig keeps no row - such a contig writes no member). */
+#define FTK_LAYOUT_FRAG 0
+#define FTK_LAYOUT_BED6 1
+#define FTK_LAYOUT_BED3 2
+typedef struct ftk_export_result {
+    int64_t n_rows;     /* kept rows                                                             */
+    int64_t text_bytes; /* bytes of their text                                                   */
+    int64_t first_off;  /* file offset of the contig's first member                              */
+    int64_t end_off;    /* file offset behind its last member                                    */
+    int64_t n_linear;   /* 16 kb windows up to the last one a kept row reaches                   */
+    uint64_t* linear;   /* virtual offset of the first row overlapping each window (a window
+                         * without one takes the next window's, as htslib writes it)             */
+    int64_t n_runs;     /* runs of consecutive rows with one bin (reg2bin: 14-bit shift, 5 levels) */
+    int32_t* run_bin;   /* the run's bin                                                         */
+    uint64_t* run_beg;  /* virtual offsets of its first byte and behind its last byte            */
+    uint64_t* run_end;
+    double stage_ms[5]; /* format kernels, deflate + CRC kernels, scan + compaction (HIP events);
+                         * device -> host copy, file write (wall clock)                          */
+} ftk_export_result;
+int ftk_frags_format_rows(ftk_ctx* ctx, int contig_id, const char* name, int32_t mapq_min, int32_t min_len,
+                          int32_t max_len, int layout, char** out, int64_t* out_len, int64_t* n_rows);
+int ftk_bgzf_deflate_device(ftk_ctx* ctx, const uint8_t* data, int64_t n, uint8_t* out, int64_t cap, int64_t* n_out,
+                            int64_t* block_offsets, int write_eof);
+int ftk_frags_write(ftk_ctx* ctx, int contig_id, const char* name, int32_t mapq_min, int32_t min_len, int32_t max_len,
+                    int layout, const char* path, int append, int write_eof, int deflate_on_host, ftk_export_result* res);
+
 /* ---- output writers (host only; no ctx / GPU needed) ---------------------------------------------
  * The reference prints per-base results one Python f-string at a time (frag/_wps.py:208-229 WIG,
  * frag/_multi_wps.py:328-341 bedGraph) and hands bigWig entries to pyBigWig (:300-325).  These format the
