@@ -58,6 +58,7 @@ EXPORTS = [
     "ftk_comm_unique_id", "ftk_comm_create", "ftk_comm_size", "ftk_allgather_i64", "ftk_allreduce_sum_i64", "ftk_comm_send",
     "ftk_comm_recv", "ftk_comm_join", "ftk_comm_destroy",
     "ftk_frags_format_rows", "ftk_bgzf_deflate_device", "ftk_frags_write",
+    "ftk_mask_lds_intervals", "ftk_frags_mask_keep", "ftk_frags_format_rows_masked", "ftk_frags_write_masked",
 ]
 
 
@@ -94,6 +95,11 @@ class ExportResult(C.Structure):
     _fields_ = [("n_rows", C.c_int64), ("text_bytes", C.c_int64), ("first_off", C.c_int64), ("end_off", C.c_int64),
                 ("n_linear", C.c_int64), ("linear", C.c_void_p), ("n_runs", C.c_int64), ("run_bin", C.c_void_p),
                 ("run_beg", C.c_void_p), ("run_end", C.c_void_p), ("stage_ms", C.c_double * 5)]
+
+
+class RegionMask(C.Structure):
+    _fields_ = [("wl_start", C.c_void_p), ("wl_end", C.c_void_p), ("n_wl", C.c_int64),
+                ("bl_start", C.c_void_p), ("bl_end", C.c_void_p), ("n_bl", C.c_int64), ("policy", C.c_int32)]
 
 
 LAYOUT = {"frag": 0, "bed6": 1, "bed3": 2}
@@ -310,6 +316,11 @@ def load() -> C.CDLL:
     lib.ftk_bgzf_deflate_device.argtypes = [vp, vp, i64, vp, i64, pi64, vp, C.c_int]
     lib.ftk_frags_write.argtypes = [vp, C.c_int, C.c_char_p, i32, i32, i32, C.c_int, C.c_char_p, C.c_int, C.c_int, C.c_int,
                                     C.POINTER(ExportResult)]
+    pmask = C.POINTER(RegionMask)
+    lib.ftk_mask_lds_intervals.argtypes = []
+    lib.ftk_frags_mask_keep.argtypes = [vp, C.c_int, pmask, vp, pi64]
+    lib.ftk_frags_format_rows_masked.argtypes = lib.ftk_frags_format_rows.argtypes + [pmask]
+    lib.ftk_frags_write_masked.argtypes = lib.ftk_frags_write.argtypes + [pmask]
     lib.ftk_comm_unique_id.argtypes = [C.c_char_p]
     lib.ftk_comm_create.argtypes = [vp, C.c_int, C.c_int, C.c_char_p, C.POINTER(vp)]
     lib.ftk_comm_size.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]

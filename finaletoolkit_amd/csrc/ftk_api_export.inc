@@ -1,5 +1,5 @@
 // Part of ftk_api.hip's translation unit (#included there last) - the write direction: `ftk_frags_format_rows`,
-// `ftk_bgzf_deflate_device`, `ftk_frags_write` over the kernels of ftk_fragtext.hip.
+// `ftk_bgzf_deflate_device`, `ftk_frags_write` and their region-mask forms over the kernels of ftk_fragtext.hip.
 #include "ftk_fragtext.h"
 
 namespace {
@@ -53,25 +53,89 @@ int row_params(ftk_ctx* ctx, const char* name, int32_t mapq_min, int32_t min_len
     return FTK_OK;
 }
 
+// A caller's region mask, checked and laid out the way the kernel reads it: four arrays (whitelist starts / ends,
+// blacklist starts / ends) in one host block, each padded to a multiple of four entries (starts with INT32_MAX, ends
+// with 0) and starting on a 256-byte boundary, so that one copy puts them into the scratch arena.
+struct MaskPack {
+    std::vector<int32_t> host;
+    size_t off[4] = {0, 0, 0, 0};  // in entries
+    int32_t n_wl = -1, n_bl = 0, policy = FTK_POLICY_MIDPOINT;
+    MaskView view(const int32_t* dev) const {
+        return MaskView{dev + off[0], dev + off[1], n_wl, dev + off[2], dev + off[3], n_bl, policy};
+    }
+};
+
+int mask_check(ftk_ctx* ctx, const char* what, const int32_t* s, const int32_t* e, int64_t n) {
+    if (n > (int64_t(1) << 30)) return fail(ctx, FTK_ERR_INVALID, "%s holds too many intervals (%lld)", what, (long long)n);
+    if (n > 0 && (!s || !e)) return fail(ctx, FTK_ERR_INVALID, "%s arrays are NULL", what);
+    for (int64_t k = 0; k < n; ++k) {
+        if (s[k] >= e[k]) return fail(ctx, FTK_ERR_INVALID, "%s interval %lld: start %d >= end %d", what, (long long)k, s[k], e[k]);
+        if (k && s[k] < e[k - 1])
+            return fail(ctx, FTK_ERR_INVALID, "%s interval %lld starts at %d, inside or in front of its predecessor (end %d): "
+                        "the intervals must be sorted and disjoint", what, (long long)k, s[k], e[k - 1]);
+    }
+    return FTK_OK;
+}
+
+int mask_pack(ftk_ctx* ctx, const ftk_region_mask* m, MaskPack* p) {
+    if (m->policy != FTK_POLICY_MIDPOINT && m->policy != FTK_POLICY_ANY)
+        return fail(ctx, FTK_ERR_INVALID, "region masks take FTK_POLICY_MIDPOINT or FTK_POLICY_ANY, not %d", m->policy);
+    const int64_t n_wl = m->n_wl < 0 ? -1 : m->n_wl, n_bl = m->n_bl <= 0 ? 0 : m->n_bl;
+    int rc = mask_check(ctx, "whitelist", m->wl_start, m->wl_end, n_wl);
+    if (!rc) rc = mask_check(ctx, "blacklist", m->bl_start, m->bl_end, n_bl);
+    if (rc) return rc;
+    p->n_wl = (int32_t)n_wl;
+    p->n_bl = (int32_t)n_bl;
+    p->policy = m->policy;
+    const int32_t* src[4] = {m->wl_start, m->wl_end, m->bl_start, m->bl_end};
+    const int64_t cnt[4] = {n_wl < 0 ? 0 : n_wl, n_wl < 0 ? 0 : n_wl, n_bl, n_bl};
+    size_t total = 0;
+    for (int a = 0; a < 4; ++a) {
+        p->off[a] = total;
+        total += align_up(((size_t)cnt[a] + 3) / 4 * 4 * sizeof(int32_t) + 16) / sizeof(int32_t);
+    }
+    p->host.assign(total, 0);
+    for (int a = 0; a < 4; ++a) {
+        int32_t* dst = p->host.data() + p->off[a];
+        if (cnt[a]) memcpy(dst, src[a], (size_t)cnt[a] * sizeof(int32_t));
+        if (!(a & 1))
+            for (size_t k = (size_t)cnt[a]; k < ((size_t)cnt[a] + 3) / 4 * 4 + 4; ++k) dst[k] = INT32_MAX;
+    }
+    return FTK_OK;
+}
+
 // Format contig `c` into the scratch (stream-ordered; total is on the host when this returns).  with_deflate reserves
-// the BGZF scratch behind the text in the same arena.
-int format_contig(ftk_ctx* ctx, ContigData* c, const RowParams& p, bool with_deflate, ExportText* x) {
+// the BGZF scratch behind the text in the same arena.  mk (may be NULL): the region mask - its intervals are copied
+// in and its keep bitmap written in front of pass 1, again if the scratch moves.
+int format_contig(ftk_ctx* ctx, ContigData* c, const RowParams& p, bool with_deflate, const MaskPack* mk, ExportText* x) {
     HIPCHK(ctx, hipSetDevice(ctx->device));
     const int64_t n = c->n;
-    const size_t agg_bytes = format_agg_bytes(n);
+    const size_t mask_bytes = mk ? align_up(mk->host.size() * sizeof(int32_t)) + align_up(mask_words(n) * 8 + 8) : 0;
+    const size_t agg_bytes = format_agg_bytes(n) + mask_bytes;
     const size_t nb = (size_t)((n + kRowsPerBlock - 1) / kRowsPerBlock);
     int rc = reserve_scratch(ctx, agg_bytes);
     if (rc) return rc;
     RowAgg *d_agg = nullptr, *d_pre = nullptr, *d_total = nullptr;
+    int32_t* d_mask = nullptr;
+    unsigned long long* d_bits = nullptr;
     auto carve = [&](Arena& a) {
         d_agg = a.take<RowAgg>(nb + 1);
         d_pre = a.take<RowAgg>(nb + 1);
         d_total = d_pre + nb;
+        if (mk) {
+            d_mask = a.take<int32_t>(mk->host.size());
+            d_bits = a.take<unsigned long long>(mask_words(n) + 1);
+        }
     };
     auto pass1 = [&]() -> int {
         Arena a(ctx);
         carve(a);
-        format_pass1(ctx->stream, c->v.start, c->v.end, c->v.mapq, n, p, d_agg, d_pre, d_total);
+        if (mk) {  // (the caller's MaskPack outlives the stream synchronisation below)
+            HIPCHK(ctx, hipMemcpyAsync(d_mask, mk->host.data(), mk->host.size() * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+            mask_keep(ctx->stream, c->v.start, c->v.end, n, mk->view(d_mask), d_bits);
+            HIPCHK(ctx, hipGetLastError());
+        }
+        format_pass1(ctx->stream, c->v.start, c->v.end, c->v.mapq, n, p, d_agg, d_pre, d_total, d_bits);
         HIPCHK(ctx, hipGetLastError());
         return FTK_OK;
     };
@@ -88,7 +152,10 @@ int format_contig(ftk_ctx* ctx, ContigData* c, const RowParams& p, bool with_def
     rc = reserve_scratch(ctx, agg_bytes + align_up((size_t)t.bytes + 64) + 2 * align_up((size_t)x->n_runs * 4 + 4) +
                                   align_up((size_t)x->n_lin * 4 + 4) + (with_deflate ? deflate_scratch_bytes((int64_t)t.bytes) : 0) + 4096);
     if (rc) return rc;
-    if (ctx->scratch != before && (rc = pass1())) return rc;  // the scratch moved: the prefixes went with the old block
+    if (ctx->scratch != before) {  // the scratch moved: the prefixes (and the mask) went with the old block
+        if ((rc = pass1())) return rc;
+        if (mk) HIPCHK(ctx, hipStreamSynchronize(ctx->stream));  // (the copy reads the caller's host block)
+    }
     Arena a(ctx);
     carve(a);
     x->d_text = a.take<uint8_t>((size_t)t.bytes + 64);
@@ -99,7 +166,7 @@ int format_contig(ftk_ctx* ctx, ContigData* c, const RowParams& p, bool with_def
     if (t.rows) {
         HIPCHK(ctx, hipMemsetAsync(x->d_lin, 0xFF, (size_t)x->n_lin * 4, ctx->stream));
         format_pass2(ctx->stream, c->v.start, c->v.end, c->v.mapq, c->v.strand, n, p, d_pre, x->d_text, x->d_run_bin,
-                     x->d_run_off, x->d_lin, x->n_lin);
+                     x->d_run_off, x->d_lin, x->n_lin, d_bits);
         HIPCHK(ctx, hipGetLastError());
     }
     return FTK_OK;
@@ -139,8 +206,52 @@ void export_result_free(ftk_export_result* r) {
 
 extern "C" {
 
+int ftk_mask_lds_intervals(void) { return kMaskLdsIntervals; }
+
+int ftk_frags_mask_keep(ftk_ctx* ctx, int contig_id, const ftk_region_mask* mask, uint8_t* keep_out, int64_t* n_kept) {
+    if (!ctx) return fail(nullptr, FTK_ERR_INVALID, "ctx is NULL");
+    if (!mask) return fail(ctx, FTK_ERR_INVALID, "mask is NULL");
+    if (n_kept) *n_kept = 0;
+    MaskPack mk;
+    int rc = mask_pack(ctx, mask, &mk);
+    if (rc) return rc;
+    ContigData* c;
+    if ((rc = get_contig(ctx, contig_id, &c))) return rc;
+    const int64_t n = c->n;
+    if (n > 0 && !keep_out) return fail(ctx, FTK_ERR_INVALID, "keep_out is NULL");
+    if (n == 0) return FTK_OK;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const size_t words = mask_words(n);
+    if ((rc = reserve_scratch(ctx, align_up(mk.host.size() * sizeof(int32_t)) + align_up(words * 8 + 8)))) return rc;
+    Arena a(ctx);
+    int32_t* d_mask = a.take<int32_t>(mk.host.size());
+    unsigned long long* d_bits = a.take<unsigned long long>(words + 1);
+    std::vector<unsigned long long> bits(words);
+    HIPCHK(ctx, hipMemcpyAsync(d_mask, mk.host.data(), mk.host.size() * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+    mask_keep(ctx->stream, c->v.start, c->v.end, n, mk.view(d_mask), d_bits);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(bits.data(), d_bits, words * 8, hipMemcpyDeviceToHost, ctx->stream);
+    const hipError_t e2 = hipStreamSynchronize(ctx->stream);  // (always: the copies use this frame's host blocks)
+    if (e != hipSuccess || e2 != hipSuccess)
+        return fail(ctx, FTK_ERR_HIP, "mask kernel failed: %s", hipGetErrorString(e != hipSuccess ? e : e2));
+    int64_t kept = 0;
+    for (int64_t i = 0; i < n; ++i) {
+        const uint8_t b = (uint8_t)((bits[(size_t)(i >> 6)] >> (i & 63)) & 1u);
+        keep_out[i] = b;
+        kept += b;
+    }
+    if (n_kept) *n_kept = kept;
+    return FTK_OK;
+}
+
 int ftk_frags_format_rows(ftk_ctx* ctx, int contig_id, const char* name, int32_t mapq_min, int32_t min_len, int32_t max_len,
                           int layout, char** out, int64_t* out_len, int64_t* n_rows) {
+    return ftk_frags_format_rows_masked(ctx, contig_id, name, mapq_min, min_len, max_len, layout, out, out_len, n_rows, nullptr);
+}
+
+int ftk_frags_format_rows_masked(ftk_ctx* ctx, int contig_id, const char* name, int32_t mapq_min, int32_t min_len,
+                                 int32_t max_len, int layout, char** out, int64_t* out_len, int64_t* n_rows,
+                                 const ftk_region_mask* mask) {
     if (!ctx) return fail(nullptr, FTK_ERR_INVALID, "ctx is NULL");
     if (!out || !out_len) return fail(ctx, FTK_ERR_INVALID, "bad arguments");
     *out = nullptr;
@@ -149,10 +260,12 @@ int ftk_frags_format_rows(ftk_ctx* ctx, int contig_id, const char* name, int32_t
     RowParams p;
     int rc = row_params(ctx, name, mapq_min, min_len, max_len, layout, &p);
     if (rc) return rc;
+    MaskPack mk;
+    if (mask && (rc = mask_pack(ctx, mask, &mk))) return rc;
     ContigData* c;
     if ((rc = get_contig(ctx, contig_id, &c))) return rc;
     ExportText x;
-    if ((rc = format_contig(ctx, c, p, false, &x))) return rc;
+    if ((rc = format_contig(ctx, c, p, false, mask ? &mk : nullptr, &x))) return rc;
     char* buf = (char*)malloc((size_t)x.total.bytes + 1);
     if (!buf) return fail(ctx, FTK_ERR_OOM, "out of host memory");
     if (x.total.bytes) {
@@ -213,12 +326,21 @@ int ftk_bgzf_deflate_device(ftk_ctx* ctx, const uint8_t* data, int64_t n, uint8_
 
 int ftk_frags_write(ftk_ctx* ctx, int contig_id, const char* name, int32_t mapq_min, int32_t min_len, int32_t max_len,
                     int layout, const char* path, int append, int write_eof, int deflate_on_host, ftk_export_result* res) {
+    return ftk_frags_write_masked(ctx, contig_id, name, mapq_min, min_len, max_len, layout, path, append, write_eof,
+                                  deflate_on_host, res, nullptr);
+}
+
+int ftk_frags_write_masked(ftk_ctx* ctx, int contig_id, const char* name, int32_t mapq_min, int32_t min_len,
+                           int32_t max_len, int layout, const char* path, int append, int write_eof, int deflate_on_host,
+                           ftk_export_result* res, const ftk_region_mask* mask) {
     if (!ctx) return fail(nullptr, FTK_ERR_INVALID, "ctx is NULL");
     if (!path || !res) return fail(ctx, FTK_ERR_INVALID, "bad arguments");
     memset(res, 0, sizeof(*res));
     RowParams p;
     int rc = row_params(ctx, name, mapq_min, min_len, max_len, layout, &p);
     if (rc) return rc;
+    MaskPack mk;
+    if (mask && (rc = mask_pack(ctx, mask, &mk))) return rc;
     ContigData* c;
     if ((rc = get_contig(ctx, contig_id, &c))) return rc;
     if (const char* env = getenv("FTK_EXPORT_DEFLATE"))
@@ -235,7 +357,7 @@ int ftk_frags_write(ftk_ctx* ctx, int contig_id, const char* name, int32_t mapq_
     for (auto& e : ev) HIPCHK(ctx, hipEventCreate(&e));
     HIPCHK(ctx, hipEventRecord(ev[0], ctx->stream));
     ExportText x;
-    if ((rc = format_contig(ctx, c, p, !deflate_on_host, &x))) return rc;
+    if ((rc = format_contig(ctx, c, p, !deflate_on_host, mask ? &mk : nullptr, &x))) return rc;
     HIPCHK(ctx, hipEventRecord(ev[1], ctx->stream));
     const size_t T = (size_t)x.total.bytes;
     const int64_t nb = x.n_blocks;

@@ -16,6 +16,9 @@ constexpr int kRowsPerBlock = 1024;  // rows per workgroup of the formatter (256
 constexpr int kDeflateLanes = 8192;  // BGZF blocks compressed side by side (one lane each)
 constexpr int kDeflateHash = 4096;   // hash table entries per lane (uint32)
 constexpr int kDeflateTokens = 8192; // LZ77 tokens per DEFLATE block (uint32 each)
+// Intervals of ONE region mask a formatter workgroup stages in LDS (starts and ends: 8 bytes each).  Two masks take
+// 16 KiB per workgroup, so the eight workgroups of 256 threads that fill a CU's wave slots fit its 160 KiB together.
+constexpr int kMaskLdsIntervals = 1024;
 
 enum : int { kLayoutFrag = 0, kLayoutBed6 = 1, kLayoutBed3 = 2 };
 
@@ -38,15 +41,33 @@ struct RowAgg {
     int32_t pad_;
 };
 
+// Region masks of one contig on the device: sorted, disjoint intervals, both arrays padded to a multiple of four
+// entries (starts with INT32_MAX, ends with 0) and 16-byte aligned.  n_wl < 0: no whitelist, n_wl == 0: a whitelist
+// that holds nothing; n_bl <= 0: no blacklist.  policy: FTK_POLICY_MIDPOINT / FTK_POLICY_ANY.
+struct MaskView {
+    const int32_t *wl_start, *wl_end;
+    int32_t n_wl;
+    const int32_t *bl_start, *bl_end;
+    int32_t n_bl;
+    int32_t policy;
+};
+inline size_t mask_words(int64_t n) { return (size_t)((n + 63) / 64); }
+// keep_bits[i >> 6] bit (i & 63) = row i is in the whitelist (or there is none) and not in the blacklist; the unused
+// bits of the last word are zero.  The MAPQ / length rule is not looked at here.
+void mask_keep(hipStream_t s, const int32_t* start, const int32_t* end, int64_t n, const MaskView& m,
+               unsigned long long* keep_bits);
+
 size_t format_agg_bytes(int64_t n);  // scratch for the two RowAgg arrays + the total
 // pass 1 (row lengths, per-workgroup sums) + the device-wide scan: block_prefix[b] = everything in front of workgroup b
 void format_pass1(hipStream_t s, const int32_t* start, const int32_t* end, const uint8_t* mapq, int64_t n,
-                  const RowParams& p, RowAgg* block_agg, RowAgg* block_prefix, RowAgg* total);
+                  const RowParams& p, RowAgg* block_agg, RowAgg* block_prefix, RowAgg* total,
+                  const unsigned long long* keep_bits = nullptr);
 // pass 2: the bytes, the bin runs (run r: bin run_bin[r], first text byte run_off[r]) and, for every 16 kb window, the
-// text offset of the first kept row that overlaps it (lin[w]; preset to all-ones by the caller)
+// text offset of the first kept row that overlaps it (lin[w]; preset to all-ones by the caller).
+// keep_bits (both passes; nullptr = none): mask_keep's bitmap, ANDed into the keep rule
 void format_pass2(hipStream_t s, const int32_t* start, const int32_t* end, const uint8_t* mapq, const uint8_t* strand,
                   int64_t n, const RowParams& p, const RowAgg* block_prefix, uint8_t* text, int32_t* run_bin,
-                  uint32_t* run_off, uint32_t* lin, int32_t n_lin);
+                  uint32_t* run_off, uint32_t* lin, int32_t n_lin, const unsigned long long* keep_bits = nullptr);
 
 // BGZF members of `n` bytes of device text (n < 2^32 - 65536): scratch sizes and the launch sequence.  d_out receives
 // the members back to back; d_offs[k] = offset of member k in d_out, d_offs[n_blocks] = their total size.

@@ -5,7 +5,8 @@
 // workgroup of 1024 rows; one workgroup scans those; pass 2 recomputes the lengths, scans them inside the workgroup and
 // writes the bytes.  The RowAgg carries, besides bytes and rows, the bin of the last kept row and the last 16 kb window
 // reached so far: a row knows from its prefix alone whether it opens a bin run and which windows it is the first row
-// of, so runs and the linear index are written with plain stores, each entry by exactly one row.
+// of, so runs and the linear index are written with plain stores, each entry by exactly one row.  Region masks
+// (whitelist / blacklist) come in as a bitmap that mask_keep_kernel writes in front of pass 1, with the same tiling.
 //
 // (c) One LANE per BGZF block: a greedy LZ77 parse (4-byte hash, one candidate, matches verified and extended with
 // 4-byte compares), tokens in per-lane global scratch, and per DEFLATE block of at most 8192 tokens the cheaper of the
@@ -122,14 +123,20 @@ __device__ RowAgg block_scan_inclusive(RowAgg v, RowAgg* sh /* [2][threads] */, 
     return sh[cur * threads + t];
 }
 
+// the mask bits of a thread's four rows (i0 is a multiple of four, so they share a word); no bitmap: all four
+__device__ uint32_t keep_nibble(const unsigned long long* __restrict__ keep_bits, int64_t n, int64_t i0) {
+    if (!keep_bits || i0 >= n) return 15u;
+    return (uint32_t)(keep_bits[i0 >> 6] >> (i0 & 63)) & 15u;
+}
+
 __device__ RowAgg thread_rows(const int32_t* __restrict__ start, const int32_t* __restrict__ end,
-                              const uint8_t* __restrict__ mapq, int64_t n, int64_t i0, const RowParams& p) {
+                              const uint8_t* __restrict__ mapq, int64_t n, int64_t i0, const RowParams& p, uint32_t nib) {
     RowAgg a = agg_none();
     for (int k = 0; k < kFmtRows; ++k) {
         const int64_t i = i0 + k;
         if (i >= n) break;
         const int32_t s = start[i], e = end[i], q = mapq[i];
-        if (row_kept(s, e, q, p)) a = agg_combine(a, agg_row(s, e, q, p));
+        if (row_kept(s, e, q, p) && ((nib >> k) & 1u)) a = agg_combine(a, agg_row(s, e, q, p));
     }
     return a;
 }
@@ -137,10 +144,12 @@ __device__ RowAgg thread_rows(const int32_t* __restrict__ start, const int32_t* 
 __global__ __launch_bounds__(kFmtThreads) void format_pass1_kernel(const int32_t* __restrict__ start,
                                                                     const int32_t* __restrict__ end,
                                                                     const uint8_t* __restrict__ mapq, int64_t n, RowParams p,
-                                                                    RowAgg* __restrict__ block_agg) {
+                                                                    RowAgg* __restrict__ block_agg,
+                                                                    const unsigned long long* __restrict__ keep_bits) {
     __shared__ RowAgg sh[2 * kFmtThreads];
     const int64_t i0 = ((int64_t)blockIdx.x * kFmtThreads + threadIdx.x) * kFmtRows;
-    const RowAgg inc = block_scan_inclusive(thread_rows(start, end, mapq, n, i0, p), sh, kFmtThreads);
+    const RowAgg inc =
+        block_scan_inclusive(thread_rows(start, end, mapq, n, i0, p, keep_nibble(keep_bits, n, i0)), sh, kFmtThreads);
     if (threadIdx.x == kFmtThreads - 1) block_agg[blockIdx.x] = inc;
 }
 
@@ -170,10 +179,11 @@ __global__ __launch_bounds__(kFmtThreads) void format_pass2_kernel(
     const int32_t* __restrict__ start, const int32_t* __restrict__ end, const uint8_t* __restrict__ mapq,
     const uint8_t* __restrict__ strand, int64_t n, RowParams p, const RowAgg* __restrict__ block_prefix,
     uint8_t* __restrict__ text, int32_t* __restrict__ run_bin, uint32_t* __restrict__ run_off, uint32_t* __restrict__ lin,
-    int32_t n_lin) {
+    int32_t n_lin, const unsigned long long* __restrict__ keep_bits) {
     __shared__ RowAgg sh[2 * kFmtThreads];
     const int64_t i0 = ((int64_t)blockIdx.x * kFmtThreads + threadIdx.x) * kFmtRows;
-    const RowAgg mine = thread_rows(start, end, mapq, n, i0, p);
+    const uint32_t nib = keep_nibble(keep_bits, n, i0);
+    const RowAgg mine = thread_rows(start, end, mapq, n, i0, p, nib);
     __shared__ RowAgg incl[kFmtThreads];
     incl[threadIdx.x] = block_scan_inclusive(mine, sh, kFmtThreads);
     __syncthreads();
@@ -184,7 +194,7 @@ __global__ __launch_bounds__(kFmtThreads) void format_pass2_kernel(
         const int64_t i = i0 + k;
         if (i >= n) break;
         const int32_t s = start[i], e = end[i], q = mapq[i];
-        if (!row_kept(s, e, q, p)) continue;
+        if (!row_kept(s, e, q, p) || !((nib >> k) & 1u)) continue;
         const RowAgg row = agg_row(s, e, q, p);
         const uint32_t off = (uint32_t)pre.bytes;
         put_row(text + pre.bytes, s, e, q, strand[i], p);
@@ -203,6 +213,117 @@ __global__ __launch_bounds__(kFmtThreads) void format_pass2_kernel(
     }
 }
 
+
+// ---- region masks: one keep bit per row, written in front of the two passes above ---------------------------------
+// Index of the last a[k] <= key in the sorted a[0..m), -1 when there is none.  Branch-free: the trip count depends on
+// m alone (uniform over the workgroup) and every step is a load and a select.
+template <class Ptr>
+__device__ __forceinline__ int last_le(Ptr a, int m, int32_t key) {
+    if (m <= 0) return -1;
+    int base = 0;
+    for (int len = m; len > 1;) {
+        const int half = len >> 1;
+        base += a[base + half - 1] <= key ? half : 0;
+        len -= half;
+    }
+    return base - 1 + (a[base] <= key ? 1 : 0);
+}
+
+// Bits k = 0..3: row k of this thread is in the mask.  On disjoint sorted intervals the only candidate for a row is
+// the last interval with start <= key (midpoint: key = test = (s + e) >> 1; any: key = e - 1, test = s - the ends are
+// sorted too, so if that interval ends at or before s every earlier one does): in iff its end > test.
+template <class Ptr>
+__device__ __forceinline__ uint32_t rows_in_slice(Ptr ps, Ptr pe, int m, const int32_t* key, const int32_t* test, uint32_t valid) {
+    uint32_t in = 0;
+#pragma unroll
+    for (int k = 0; k < kFmtRows; ++k) {
+        const int j = last_le(ps, m, key[k]);
+        in |= (j >= 0 && pe[j < 0 ? 0 : j] > test[k] ? 1u : 0u) << k;
+    }
+    return in & valid;
+}
+
+// One mask against the workgroup's rows.  [lo, hi) = the intervals its rows can touch (block-uniform, from the
+// smallest and largest key).  A slice of at most kMaskLdsIntervals entries (counted from lo rounded down to a group
+// of four, so that the loads are 16 bytes wide and aligned) is staged in LDS and searched there; a longer one is
+// searched where it lies.
+__device__ uint32_t rows_in_mask(const int32_t* __restrict__ gs, const int32_t* __restrict__ ge, int lo, int hi,
+                                 int32_t* sh_s, int32_t* sh_e, const int32_t* key, const int32_t* test, uint32_t valid) {
+    if (hi <= lo) return 0u;
+    const int lo4 = lo & ~3;
+    const int n4 = (((hi + 3) & ~3) - lo4) >> 2;  // (the arrays are padded to a multiple of four)
+    if (n4 * 4 <= kMaskLdsIntervals) {
+        const int4* s4 = reinterpret_cast<const int4*>(gs + lo4);
+        const int4* e4 = reinterpret_cast<const int4*>(ge + lo4);
+        for (int q = threadIdx.x; q < n4; q += kFmtThreads) {
+            reinterpret_cast<int4*>(sh_s)[q] = s4[q];
+            reinterpret_cast<int4*>(sh_e)[q] = e4[q];
+        }
+        __syncthreads();
+        return rows_in_slice((const int32_t*)sh_s, (const int32_t*)sh_e, hi - lo4, key, test, valid);
+    }
+    return rows_in_slice(gs + lo, ge + lo, hi - lo, key, test, valid);
+}
+
+__global__ __launch_bounds__(kFmtThreads) void mask_keep_kernel(const int32_t* __restrict__ start,
+                                                                 const int32_t* __restrict__ end, int64_t n, MaskView m,
+                                                                 unsigned long long* __restrict__ keep_bits, int64_t n_words) {
+    __shared__ __attribute__((aligned(16))) int32_t sh_iv[4][kMaskLdsIntervals];
+    __shared__ int32_t sh_min[kFmtThreads / 64], sh_max[kFmtThreads / 64];
+    __shared__ int sh_slice[4];
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int64_t i0 = ((int64_t)blockIdx.x * kFmtThreads + t) * kFmtRows;
+    const bool any = m.policy == FTK_POLICY_ANY;
+    int32_t key[kFmtRows], test[kFmtRows];
+    uint32_t valid = 0;
+    int32_t kmin = INT32_MAX, kmax = INT32_MIN;
+#pragma unroll
+    for (int k = 0; k < kFmtRows; ++k) {
+        key[k] = test[k] = 0;
+        if (i0 + k < n) {
+            const int32_t s = start[i0 + k], e = end[i0 + k];
+            const int32_t mid = (s + e) >> 1;  // (both below 2^30: the sum fits)
+            key[k] = any ? e - 1 : mid;
+            test[k] = any ? s : mid;
+            valid |= 1u << k;
+            kmin = key[k] < kmin ? key[k] : kmin;
+            kmax = key[k] > kmax ? key[k] : kmax;
+        }
+    }
+    // rows are sorted by start, not by key: the workgroup's key range by a reduction
+    for (int d = 32; d; d >>= 1) {
+        const int32_t a = __shfl_xor(kmin, d), b = __shfl_xor(kmax, d);
+        kmin = a < kmin ? a : kmin;
+        kmax = b > kmax ? b : kmax;
+    }
+    if (lane == 0) {
+        sh_min[wave] = kmin;
+        sh_max[wave] = kmax;
+    }
+    __syncthreads();
+    if (t < 4) {  // wl lo, wl hi, bl lo, bl hi: two binary searches per mask
+        for (int w = 0; w < kFmtThreads / 64; ++w) {
+            kmin = sh_min[w] < kmin ? sh_min[w] : kmin;
+            kmax = sh_max[w] > kmax ? sh_max[w] : kmax;
+        }
+        const int32_t* gs = t < 2 ? m.wl_start : m.bl_start;
+        const int cnt = t < 2 ? m.n_wl : m.n_bl;
+        const int j = last_le(gs, cnt, (t & 1) ? kmax : kmin);
+        sh_slice[t] = (t & 1) ? j + 1 : (j < 0 ? 0 : j);
+    }
+    __syncthreads();
+    const uint32_t in_wl = m.n_wl < 0 ? valid
+                                      : rows_in_mask(m.wl_start, m.wl_end, sh_slice[0], sh_slice[1], sh_iv[0], sh_iv[1], key, test, valid);
+    const uint32_t in_bl = m.n_bl <= 0 ? 0u
+                                       : rows_in_mask(m.bl_start, m.bl_end, sh_slice[2], sh_slice[3], sh_iv[2], sh_iv[3], key, test, valid);
+    // sixteen lanes hold one 64-bit word (4 bits each): OR them together with lane shuffles; the group's first lane
+    // stores the word
+    unsigned long long word = (unsigned long long)(in_wl & ~in_bl) << (4 * (lane & 15));
+    for (int d = 1; d < 16; d <<= 1) word |= __shfl_xor(word, d);
+    const int64_t w = (int64_t)blockIdx.x * (kRowsPerBlock / 64) + wave * 4 + (lane >> 4);
+    if ((lane & 15) == 0 && w < n_words) keep_bits[w] = word;
+}
+
 }  // namespace
 
 size_t format_agg_bytes(int64_t n) {
@@ -211,20 +332,30 @@ size_t format_agg_bytes(int64_t n) {
 }
 
 void format_pass1(hipStream_t s, const int32_t* start, const int32_t* end, const uint8_t* mapq, int64_t n,
-                  const RowParams& p, RowAgg* block_agg, RowAgg* block_prefix, RowAgg* total) {
+                  const RowParams& p, RowAgg* block_agg, RowAgg* block_prefix, RowAgg* total,
+                  const unsigned long long* keep_bits) {
     const int64_t nb = (n + kRowsPerBlock - 1) / kRowsPerBlock;
     if (nb > 0)
-        hipLaunchKernelGGL(format_pass1_kernel, dim3((unsigned)nb), dim3(kFmtThreads), 0, s, start, end, mapq, n, p, block_agg);
+        hipLaunchKernelGGL(format_pass1_kernel, dim3((unsigned)nb), dim3(kFmtThreads), 0, s, start, end, mapq, n, p, block_agg,
+                           keep_bits);
     hipLaunchKernelGGL(format_scan_kernel, dim3(1), dim3(kScanThreads), 0, s, block_agg, nb, block_prefix, total);
 }
 
 void format_pass2(hipStream_t s, const int32_t* start, const int32_t* end, const uint8_t* mapq, const uint8_t* strand,
                   int64_t n, const RowParams& p, const RowAgg* block_prefix, uint8_t* text, int32_t* run_bin,
-                  uint32_t* run_off, uint32_t* lin, int32_t n_lin) {
+                  uint32_t* run_off, uint32_t* lin, int32_t n_lin, const unsigned long long* keep_bits) {
     const int64_t nb = (n + kRowsPerBlock - 1) / kRowsPerBlock;
     if (nb > 0)
         hipLaunchKernelGGL(format_pass2_kernel, dim3((unsigned)nb), dim3(kFmtThreads), 0, s, start, end, mapq, strand, n, p,
-                           block_prefix, text, run_bin, run_off, lin, n_lin);
+                           block_prefix, text, run_bin, run_off, lin, n_lin, keep_bits);
+}
+
+void mask_keep(hipStream_t s, const int32_t* start, const int32_t* end, int64_t n, const MaskView& m,
+               unsigned long long* keep_bits) {
+    const int64_t nb = (n + kRowsPerBlock - 1) / kRowsPerBlock;
+    if (nb > 0)
+        hipLaunchKernelGGL(mask_keep_kernel, dim3((unsigned)nb), dim3(kFmtThreads), 0, s, start, end, n, m, keep_bits,
+                           (int64_t)mask_words(n));
 }
 
 // ---------------------------------------------------------------------------------------------------------------

@@ -84,6 +84,23 @@ NARROW_WIRE_MIN = 1 << 22
 _NARROW_WIRE = __import__("os").environ.get("FTK_WPS_NARROW_WIRE", "1") != "0"
 
 
+def _checked_policy(policy: str) -> str:
+    if policy not in L.POLICY:
+        from .exceptions import InvalidInputError
+        raise InvalidInputError(f"{policy} is not a valid policy")
+    return policy
+
+
+class RegionMask:
+    """One contig's region masks for the export (``Engine.mask_keep`` / ``format_rows`` / ``write_contig``):
+    ``whitelist`` / ``blacklist`` are ``(starts, ends)`` of sorted, disjoint intervals or ``None`` (no such mask; an
+    EMPTY whitelist keeps nothing); ``policy`` is ``"midpoint"`` or ``"any"`` and serves both."""
+    __slots__ = ("whitelist", "blacklist", "policy")
+
+    def __init__(self, whitelist=None, blacklist=None, policy="midpoint"):
+        self.whitelist, self.blacklist, self.policy = whitelist, blacklist, policy
+
+
 class Engine:
     def __init__(self, device: int = 0):
         self.lib = L.load()
@@ -490,14 +507,59 @@ class Engine:
         f = L.make_filter(quality_threshold, min_length, max_length)
         return str(print_name).encode(), f.mapq_min, f.min_len, f.max_len, L.LAYOUT[layout]
 
+    @staticmethod
+    def _mask_struct(mask):
+        """``(ftk_region_mask or None, the arrays it points into)`` of a ``RegionMask`` / ``None``."""
+        if mask is None:
+            return None, ()
+        m = L.RegionMask()
+        keep = []
+        for tag, pair in (("wl", mask.whitelist), ("bl", mask.blacklist)):
+            if pair is None:
+                setattr(m, "n_" + tag, -1 if tag == "wl" else 0)
+                continue
+            s = np.ascontiguousarray(pair[0], dtype=np.int32)
+            e = np.ascontiguousarray(pair[1], dtype=np.int32)
+            if s.ndim != 1 or s.shape != e.shape:
+                raise ValueError("a mask's starts and ends must be two 1-d arrays of one length")
+            keep += [s, e]
+            setattr(m, tag + "_start", s.ctypes.data)
+            setattr(m, tag + "_end", e.ctypes.data)
+            setattr(m, "n_" + tag, len(s))
+        m.policy = mask.policy if isinstance(mask.policy, int) else L.POLICY[_checked_policy(mask.policy)]
+        return m, keep
+
+    def mask_lds_intervals(self) -> int:
+        """Intervals of one mask a workgroup of the mask kernel stages in LDS (``kMaskLdsIntervals``); a tile whose
+        rows can touch more searches the global arrays."""
+        return int(self.lib.ftk_mask_lds_intervals())
+
+    def mask_keep(self, name: str, mask):
+        """``(bool[n], kept)``: which rows of resident contig ``name`` the region mask keeps (in the whitelist, if
+        any, and not in the blacklist, if any) - the mask kernel alone, without the MAPQ / length rule
+        (``ftk_frags_mask_keep``)."""
+        n = self.info(name)[0]
+        out = np.zeros(n, np.uint8)
+        kept = C.c_int64()
+        m, alive = self._mask_struct(mask if mask is not None else RegionMask())
+        self._check(self.lib.ftk_frags_mask_keep(self.ctx, self.contig_id(name), C.byref(m), L.ptr(out), C.byref(kept)))
+        del alive
+        return out.astype(bool), int(kept.value)
+
     def format_rows(self, name: str, print_name: str, quality_threshold=30, min_length=None, max_length=None,
-                    layout="frag"):
+                    layout="frag", mask=None):
         """``(text bytes, rows)``: the kept fragments of resident contig ``name`` as rows that carry ``print_name``,
-        formatted on the device (``ftk_frags_format_rows``)."""
+        formatted on the device (``ftk_frags_format_rows``; with a ``RegionMask``: ``ftk_frags_format_rows_masked``)."""
         args = self._export_args(print_name, quality_threshold, min_length, max_length, layout)
         out, n, rows = C.c_void_p(), C.c_int64(), C.c_int64()
-        self._check(self.lib.ftk_frags_format_rows(self.ctx, self.contig_id(name), *args, C.byref(out), C.byref(n),
-                                                   C.byref(rows)))
+        if mask is None:
+            self._check(self.lib.ftk_frags_format_rows(self.ctx, self.contig_id(name), *args, C.byref(out), C.byref(n),
+                                                       C.byref(rows)))
+        else:
+            m, alive = self._mask_struct(mask)
+            self._check(self.lib.ftk_frags_format_rows_masked(self.ctx, self.contig_id(name), *args, C.byref(out),
+                                                              C.byref(n), C.byref(rows), C.byref(m)))
+            del alive
         try:
             return C.string_at(out.value, n.value), int(rows.value)
         finally:
@@ -518,15 +580,22 @@ class Engine:
         return out[: got.value].tobytes(), offs
 
     def write_contig(self, name: str, print_name: str, path: str, quality_threshold=30, min_length=None,
-                     max_length=None, layout="frag", append=False, write_eof=False, deflate_on_host=False) -> dict:
+                     max_length=None, layout="frag", append=False, write_eof=False, deflate_on_host=False,
+                     mask=None) -> dict:
         """Append the kept rows of resident contig ``name`` to ``path`` as BGZF members built on the device
         (``ftk_frags_write``).  Returns ``rows``, ``text_bytes``, ``first_off`` / ``end_off`` (file offsets), the
         tabix inputs ``linear`` (uint64 virtual offsets per 16 kb window) and ``runs`` = ``(bin int32[], begin
-        uint64[], end uint64[])``, and ``stage_ms`` (format, deflate + CRC, compaction, copy, write)."""
+        uint64[], end uint64[])``, and ``stage_ms`` (format, deflate + CRC, compaction, copy, write).  ``mask``: a
+        ``RegionMask`` added to the keep rule (``ftk_frags_write_masked``; its kernel counts into ``stage_ms[0]``)."""
         args = self._export_args(print_name, quality_threshold, min_length, max_length, layout)
         res = L.ExportResult()
-        self._check(self.lib.ftk_frags_write(self.ctx, self.contig_id(name), *args, str(path).encode(), int(bool(append)),
-                                             int(bool(write_eof)), int(bool(deflate_on_host)), C.byref(res)))
+        tail = (str(path).encode(), int(bool(append)), int(bool(write_eof)), int(bool(deflate_on_host)), C.byref(res))
+        if mask is None:
+            self._check(self.lib.ftk_frags_write(self.ctx, self.contig_id(name), *args, *tail))
+        else:
+            m, alive = self._mask_struct(mask)
+            self._check(self.lib.ftk_frags_write_masked(self.ctx, self.contig_id(name), *args, *tail, C.byref(m)))
+            del alive
 
         def take(p, n, dtype):
             if not p or n == 0:

@@ -17,7 +17,7 @@ from .exceptions import InvalidInputError
 from .source import get_engine, open_source
 
 __all__ = ["chrom_sizes_to_list", "chrom_sizes_to_dict", "get_intervals", "overlaps", "frags_in_region", "frag_generator",
-           "frag_array", "frag_export", "agg_bw", "gen_kmers", "reverse_complement", "validate_compatible_contigs", "valid_interval",
+           "frag_array", "frag_export", "frag_filter", "read_region_mask", "agg_bw", "gen_kmers", "reverse_complement", "validate_compatible_contigs", "valid_interval",
            "_none_eq", "_none_geq", "_none_leq"]
 
 FragTuple = Tuple[str, int, int, int, bool]
@@ -156,20 +156,62 @@ def frag_array(input_file, contig: str, quality_threshold: int = 30, start=None,
 _EXPORT_LAYOUTS = ("frag", "bed6", "bed3")
 
 
-def frag_export(input_file, output_file, contig=None, quality_threshold: int = 30, min_length=None, max_length=None,
-                layout: str = "frag", workers=None, verbose=False) -> dict:
-    """Write the fragments of ``input_file`` (BAM, or a fragment file / BED6) that pass ``mapq >= quality_threshold``
-    and ``min_length <= length <= max_length`` as a tabix-indexed BGZF file ``output_file`` (+ ``.tbi``): rows
-    ``contig start end mapq strand`` (``layout="frag"``), with a ``.`` name column (``"bed6"``) or ``contig start
-    end`` alone (``"bed3"``), sorted by start within a contig, contigs in the order of the input.  Rows are formatted
-    and deflated on the GPU, contig by contig as the input is decoded (``ftk_frags_write``).  Returns
-    ``{contig: rows written}`` for the contigs visited (``contig``: that one alone)."""
-    import os
-    import sys
-    import time
+COORD_BOUND = 1 << 30  # the project's coordinate bound (a contig's columns hold values below it)
 
-    from . import bgzf, writers
-    from .source import ContigFeed
+
+def read_region_mask(bed_file) -> dict:
+    """A whitelist / blacklist BED (plain or gzip; the first three columns) as ``{contig: (starts int32[], ends
+    int32[])}``, sorted, with overlapping intervals merged - neither intersect policy can tell the merged set from the
+    given one (``merge_intervals``; touching intervals stay apart).  Blank lines and lines that start with ``#``, ``track`` or ``browser`` are skipped; a row
+    with fewer than three columns, a coordinate that is no integer, ``start < 0``, ``stop <= start`` or ``stop >
+    2**30`` is a ``ValueError`` that names the file and the line."""
+    import gzip
+    import os
+    path = os.fspath(bed_file)
+    with open(path, "rb") as fh:
+        zipped = fh.read(2) == b"\x1f\x8b"
+    per = {}
+    with (gzip.open if zipped else open)(path, "rt") as fh:
+        for no, line in enumerate(fh, 1):
+            if not line.strip() or line.startswith(("#", "track", "browser")):
+                continue
+            parts = line.split()
+            if len(parts) < 3:
+                raise ValueError(f"{path}, line {no}: a BED row needs three columns, found {len(parts)}")
+            try:
+                a, b = int(parts[1]), int(parts[2])
+            except ValueError:
+                raise ValueError(f"{path}, line {no}: coordinates {parts[1]!r}, {parts[2]!r} are not integers") from None
+            if a < 0:
+                raise ValueError(f"{path}, line {no}: start {a} < 0")
+            if b <= a:
+                raise ValueError(f"{path}, line {no}: stop {b} <= start {a}")
+            if b > COORD_BOUND:
+                raise ValueError(f"{path}, line {no}: stop {b} > 2**30, the coordinate bound")
+            per.setdefault(parts[0], []).append((a, b))
+    return {c: merge_intervals(*zip(*iv)) for c, iv in per.items()}
+
+
+def merge_intervals(starts, ends):
+    """``(starts, ends)`` int32, sorted by start, OVERLAPPING intervals made one: sorted and disjoint.  Intervals that
+    only touch (``[a, b)``, ``[b, c)``) stay two: under the ``any`` policy a zero-length fragment ``[b, b)`` is in
+    neither of them (``b > a and b < b`` fails, so does ``b > b``) but would be in ``[a, c)``; every other fragment,
+    and every fragment under ``midpoint``, is in the one exactly when it is in one of the two."""
+    s = np.asarray(starts, dtype=np.int64)
+    e = np.asarray(ends, dtype=np.int64)
+    if len(s) == 0:
+        return np.zeros(0, np.int32), np.zeros(0, np.int32)
+    o = np.argsort(s, kind="stable")
+    s, e = s[o], np.maximum.accumulate(e[o])
+    first = np.concatenate(([True], s[1:] >= e[:-1]))  # opens a run: starts at or behind the end of everything in front
+    last = np.concatenate((first[1:], [True]))
+    return s[first].astype(np.int32), e[last].astype(np.int32)
+
+
+def _check_export_args(input_file, output_file, layout) -> str:
+    import os
+
+    from . import writers
     output_file = os.fspath(output_file)
     writers.check_suffix(output_file, (".gz", ".bgz"), "output_file should have .gz or .bgz as suffix")
     if output_file == "-":
@@ -179,20 +221,38 @@ def frag_export(input_file, output_file, contig=None, quality_threshold: int = 3
     if os.path.abspath(os.fspath(input_file)) == os.path.abspath(output_file) or (
             os.path.exists(output_file) and os.path.exists(os.fspath(input_file)) and os.path.samefile(input_file, output_file)):
         raise ValueError("input_file and output_file are the same file")
+    return output_file
+
+
+def _export(label, input_file, output_file, contig, quality_threshold, min_length, max_length, layout, workers, verbose,
+            whitelist=None, blacklist=None, intersect_policy="midpoint") -> dict:
+    """The body of ``frag_export`` and ``frag_filter`` (arguments checked by the caller): every contig of the feed goes
+    through ``Engine.write_contig``; ``whitelist`` / ``blacklist`` are ``read_region_mask`` results or ``None``."""
+    import sys
+    import time
+
+    from . import bgzf
+    from .engine import RegionMask
+    from .source import ContigFeed
     t0 = time.time()
     eng = get_engine()
     feed = ContigFeed(input_file, workers, names=None if contig is None else [str(contig)])
+    none = (np.zeros(0, np.int32), np.zeros(0, np.int32))
     written, index, first = {}, [], True
     try:
         for src, c in feed:
+            mask = None
+            if whitelist is not None or blacklist is not None:
+                mask = RegionMask(None if whitelist is None else whitelist.get(c, none),
+                                  None if blacklist is None else blacklist.get(c), intersect_policy)
             res = eng.write_contig(src.key(c), c, output_file, quality_threshold, min_length, max_length, layout,
-                                   append=not first)
+                                   append=not first, mask=mask)
             first = False
             written[c] = res["rows"]
             index.append(dict(name=c, v_begin=res["first_off"] << 16, v_end=res["end_off"] << 16, rows=res["rows"],
                               linear=res["linear"], runs=res["runs"]))
             if verbose:
-                sys.stderr.write(f"frag_export: {c}: {res['rows']} rows, {res['text_bytes']} bytes of text -> "
+                sys.stderr.write(f"{label}: {c}: {res['rows']} rows, {res['text_bytes']} bytes of text -> "
                                  f"{res['end_off'] - res['first_off']} bytes\n")
         src = feed.finish()
     except BaseException:
@@ -204,8 +264,41 @@ def frag_export(input_file, output_file, contig=None, quality_threshold: int = 3
         fh.write(bgzf._EOF)
     bgzf.write_tabix(output_file + ".tbi", index)
     if verbose:
-        sys.stderr.write(f"frag_export: {sum(written.values())} rows in {time.time() - t0:.3f} s\n")
+        sys.stderr.write(f"{label}: {sum(written.values())} rows in {time.time() - t0:.3f} s\n")
     return written
+
+
+def frag_export(input_file, output_file, contig=None, quality_threshold: int = 30, min_length=None, max_length=None,
+                layout: str = "frag", workers=None, verbose=False) -> dict:
+    """Write the fragments of ``input_file`` (BAM, or a fragment file / BED6) that pass ``mapq >= quality_threshold``
+    and ``min_length <= length <= max_length`` as a tabix-indexed BGZF file ``output_file`` (+ ``.tbi``): rows
+    ``contig start end mapq strand`` (``layout="frag"``), with a ``.`` name column (``"bed6"``) or ``contig start
+    end`` alone (``"bed3"``), sorted by start within a contig, contigs in the order of the input.  Rows are formatted
+    and deflated on the GPU, contig by contig as the input is decoded (``ftk_frags_write``).  Returns
+    ``{contig: rows written}`` for the contigs visited (``contig``: that one alone)."""
+    output_file = _check_export_args(input_file, output_file, layout)
+    return _export("frag_export", input_file, output_file, contig, quality_threshold, min_length, max_length, layout,
+                   workers, verbose)
+
+
+def frag_filter(input_file, output_file, whitelist_file=None, blacklist_file=None, intersect_policy: str = "midpoint",
+                contig=None, quality_threshold: int = 30, min_length=None, max_length=None, layout: str = "frag",
+                workers=None, verbose=False) -> dict:
+    """``frag_export`` with region masks: a fragment is written when it passes the MAPQ / length rule, is IN
+    ``whitelist_file`` (a BED; if given) and is NOT in ``blacklist_file`` (if given).  A fragment is in a BED when one
+    of its intervals ``[r_start, r_stop)`` on the fragment's contig holds ``frag_generator``'s own rule for
+    ``intersect_policy``: ``"midpoint"``: ``r_start <= (start + stop) // 2 < r_stop``; ``"any"``: ``stop > r_start
+    and start < r_stop``.  One policy serves both masks.  Rows are whole fragments, each written at most once, in the
+    order ``frag_export`` writes them (this is not bedtools' ``-f 0.5`` clipping of the reference's ``filter_file``).
+    The mask test is a kernel in front of the device formatter (``ftk_frags_write_masked``).  Every contig of the
+    input is visited; one the whitelist does not name yields 0 rows.  Returns ``{contig: rows written}``; with both
+    masks ``None`` the file and its index are ``frag_export``'s byte for byte."""
+    output_file = _check_export_args(input_file, output_file, layout)
+    _check_policy(intersect_policy)
+    whitelist = None if whitelist_file is None else read_region_mask(whitelist_file)
+    blacklist = None if blacklist_file is None else read_region_mask(blacklist_file)
+    return _export("frag_filter", input_file, output_file, contig, quality_threshold, min_length, max_length, layout,
+                   workers, verbose, whitelist, blacklist, intersect_policy)
 
 
 def agg_bw(input_file, interval_file, output_file, median_window_size: int = 1, mean: bool = False,

@@ -512,7 +512,8 @@ int ftk_bgzf_inflate_device(ftk_ctx* ctx, const uint8_t* file_bytes, int64_t n, 
  *   FTK_LAYOUT_FRAG  "<contig>\t<start>\t<end>\t<mapq>\t<+|->\n"
  *   FTK_LAYOUT_BED6  the same with a "." name column before mapq
  *   FTK_LAYOUT_BED3  "<contig>\t<start>\t<end>\n"
- * `name` is the contig name to print (1..255 bytes).  A contig's text must stay below 4 GB.
+ * `name` is the contig name to print (1..255 bytes).  A contig's text must stay below 4 GB.  The `_masked` forms
+ * below add a whitelist / blacklist of regions to the keep rule.
  *   ftk_frags_format_rows    the formatter alone: the rows in library-owned host memory (*out, ftk_buffer_free;
  *                            NUL-terminated), *out_len bytes, *n_rows kept rows (may be NULL).  The bytes are those of
  *                            ftk_format_frag_rows for the kept rows (bed3: its first three columns).
@@ -554,6 +555,39 @@ int ftk_bgzf_deflate_device(ftk_ctx* ctx, const uint8_t* data, int64_t n, uint8_
                             int64_t* block_offsets, int write_eof);
 int ftk_frags_write(ftk_ctx* ctx, int contig_id, const char* name, int32_t mapq_min, int32_t min_len, int32_t max_len,
                     int layout, const char* path, int append, int write_eof, int deflate_on_host, ftk_export_result* res);
+
+/* Region masks in front of the formatter (csrc/ftk_fragtext.hip, mask_keep_kernel): a whitelist and / or a
+ * blacklist of one contig as sorted, disjoint HOST intervals [start, end) with start < end (touching ones are
+ * accepted and differ from their union for a zero-length fragment at the touch point; the Python loader merges
+ * overlapping intervals only).  A fragment [s, e) is IN a mask when one interval [a, b) of it holds
+ *   FTK_POLICY_MIDPOINT  a <= (s + e) / 2 < b        (utils/_frag_generator.py:35-42)
+ *   FTK_POLICY_ANY       e > a and s < b             (utils/_frag_generator.py:44-50)
+ * and a row is kept when it passes the MAPQ / length rule, is in the whitelist (if one is given) and is not in the
+ * blacklist (if one is given).  Rows stay whole fragments, each written at most once, in resident order.  The
+ * library checks order, start < end and the policy (FTK_ERR_INVALID), and copies the arrays to the device.
+ *   ftk_frags_mask_keep          the mask test alone: keep_out[i] = 1 / 0 per resident row (n host bytes, n as
+ *                                ftk_frags_info reports it), *n_kept their sum (may be NULL)
+ *   ftk_frags_format_rows_masked / ftk_frags_write_masked
+ *                                ftk_frags_format_rows / ftk_frags_write with the mask in the keep rule; mask ==
+ *                                NULL is the unmasked call (the two are thin calls of these).  The mask kernel's
+ *                                time (and the intervals' copy) counts into stage_ms[0].
+ *   ftk_mask_lds_intervals       intervals of one mask a workgroup (1024 rows) keeps in LDS; a tile whose rows can
+ *                                touch more searches the global arrays instead (same result) */
+typedef struct ftk_region_mask {
+    const int32_t *wl_start, *wl_end;
+    int64_t n_wl; /* < 0: no whitelist; 0: a whitelist that holds nothing on this contig */
+    const int32_t *bl_start, *bl_end;
+    int64_t n_bl; /* <= 0: no blacklist */
+    int32_t policy; /* FTK_POLICY_MIDPOINT | FTK_POLICY_ANY */
+} ftk_region_mask;
+int ftk_mask_lds_intervals(void);
+int ftk_frags_mask_keep(ftk_ctx* ctx, int contig_id, const ftk_region_mask* mask, uint8_t* keep_out, int64_t* n_kept);
+int ftk_frags_format_rows_masked(ftk_ctx* ctx, int contig_id, const char* name, int32_t mapq_min, int32_t min_len,
+                                 int32_t max_len, int layout, char** out, int64_t* out_len, int64_t* n_rows,
+                                 const ftk_region_mask* mask);
+int ftk_frags_write_masked(ftk_ctx* ctx, int contig_id, const char* name, int32_t mapq_min, int32_t min_len,
+                           int32_t max_len, int layout, const char* path, int append, int write_eof, int deflate_on_host,
+                           ftk_export_result* res, const ftk_region_mask* mask);
 
 /* ---- output writers (host only; no ctx / GPU needed) ---------------------------------------------
  * The reference prints per-base results one Python f-string at a time (frag/_wps.py:208-229 WIG,
