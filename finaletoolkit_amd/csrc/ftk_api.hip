@@ -100,6 +100,85 @@ int reserve_scratch(ftk_ctx* ctx, size_t bytes) {
     return FTK_OK;
 }
 
+// One API call's buffers in the ctx scratch.  The call declares each buffer ONCE - out() for a user output that may be a
+// host or a device pointer, tmp() for a temporary - naming the pointer variable it is to be reached through.  The rest
+// follows from the declarations: the bytes reserve() asks for (behind `prefix` bytes the caller keeps at the scratch base),
+// the device address each variable gets (the user's own array when that is on the device), the copies finish() issues.
+// place() writes through the addresses the declarations named: those variables (and the structs that hold them) must
+// not be copied or moved between their declaration and reserve() / place().
+class Scratch {
+  public:
+    explicit Scratch(ftk_ctx* ctx, size_t prefix = 0) : ctx_(ctx), bytes_(prefix) {}
+    // user == nullptr: a temporary.  copy_back = false: the caller carries a host result home itself.
+    // Returns true when the buffer lives in the scratch (a temporary, or the device side of a host output).
+    template <class T>
+    bool out(T** dev, T* user, size_t n, bool copy_back = true) {
+        if (is_device_ptr(user)) {
+            *dev = user;
+            return false;
+        }
+        if (n_ < kMaxBufs) bufs_[n_] = Buf{dev, nullptr, copy_back ? user : nullptr, n * sizeof(T), bytes_};
+        ++n_;
+        bytes_ += align_up(n * sizeof(T));
+        return true;
+    }
+    template <class T>
+    void tmp(T** dev, size_t n) { out(dev, (T*)nullptr, n); }
+    size_t bytes() const { return bytes_; }
+    // once per call, before any of the declared variables is read
+    int reserve() { const int rc = reserve_scratch(ctx_, bytes_); return rc ? rc : place(); }
+    // (on its own: for buffers inside the prefix that another Scratch's reserve() made room for)
+    int place() {
+        if (n_ > kMaxBufs) return fail(ctx_, FTK_ERR_INVALID, "more than %d scratch buffers in one call", kMaxBufs);
+        if (bytes_ > ctx_->scratch_bytes)  // (every buffer ends at or below bytes_: none can leave the block)
+            return fail(ctx_, FTK_ERR_OOM, "the call's buffers end at byte %zu of a %zu-byte scratch block", bytes_, ctx_->scratch_bytes);
+        for (int i = 0; i < n_; ++i) {
+            Buf& b = bufs_[i];
+            b.d = (char*)ctx_->scratch + b.off;
+            memcpy(b.var, &b.d, sizeof(void*));  // (*var is a T* of the declaration's own T)
+        }
+        return FTK_OK;
+    }
+    // The host outputs' copies on ctx->stream, then one wait for the stream when a copy was issued - or when the call
+    // `must_sync` anyway (pageable staging of its own that must outlive the work).
+    int finish(bool must_sync = false) {
+        for (int i = 0; i < n_; ++i)
+            if (bufs_[i].host) {
+                HIPCHK(ctx_, hipMemcpyAsync(bufs_[i].host, bufs_[i].d, bufs_[i].bytes, hipMemcpyDeviceToHost, ctx_->stream));
+                must_sync = true;
+            }
+        if (must_sync) HIPCHK(ctx_, hipStreamSynchronize(ctx_->stream));
+        return FTK_OK;
+    }
+
+  private:
+    static constexpr int kMaxBufs = 16;
+    struct Buf {
+        void *var, *d, *host;  // the caller's pointer variable; the buffer in the scratch (place()); the user's host array or nullptr
+        size_t bytes, off;
+    };
+    ftk_ctx* ctx_;
+    size_t bytes_;
+    Buf bufs_[kMaxBufs];
+    int n_ = 0;
+};
+
+// The five window-feature outputs of a FeatureRequest / FusedParams, declared in one place (NULL: that feature is off).
+// want_hist without `hist`: the statistics-only call, whose histogram and overflow stay in the scratch.
+template <class R>
+void declare_feature_outputs(Scratch& s, R* r, size_t n_win, size_t hist_elems, bool want_hist, int64_t* count, uint32_t* hist,
+                             int64_t* overflow, int64_t* short_out, int64_t* long_out) {
+    if (count) s.out(&r->cov_out, count, n_win);
+    if (want_hist) {
+        s.out(&r->hist_out, hist, hist_elems);
+        s.out(&r->over_out, hist ? overflow : nullptr, n_win);
+    }
+    if (short_out || long_out) {
+        s.out(&r->short_out, short_out, n_win);
+        s.out(&r->long_out, long_out, n_win);
+    }
+}
+
 int get_contig(ftk_ctx* ctx, int contig_id, ContigData** out) {
     auto it = ctx->contigs.find(contig_id);
     if (it == ctx->contigs.end()) return fail(ctx, FTK_ERR_NO_CONTIG, "contig id %d is not loaded", contig_id);
@@ -254,27 +333,27 @@ int upload_common(ftk_ctx* ctx, int contig_id, const int32_t* start, const int32
 
 // Shared body of the window features: stage windows, plan candidate ranges.
 struct WindowCall {
+    int32_t *b_ws = nullptr, *b_we = nullptr;  // staging of host window arrays (b_we behind b_ws)
     const int32_t* d_ws = nullptr;
     const int32_t* d_we = nullptr;
     WindowPlan plan{};
+    void declare(Scratch& s, int64_t n_win) {
+        s.tmp(&b_ws, n_win);
+        s.tmp(&b_we, n_win);
+        s.tmp(&plan.cand_lo, n_win);
+        s.tmp(&plan.cand_hi, n_win);
+        s.tmp(&plan.nchunks, n_win);
+        s.tmp(&plan.chunk_off, n_win + 1);
+    }
 };
 
-size_t window_scratch_bytes(int64_t n_win) {
-    return 2 * align_up(n_win * 4) + 3 * align_up(n_win * 4) + align_up((n_win + 1) * 4);
-}
-
-int window_prepare(ftk_ctx* ctx, ContigData* c, Arena& a, const int32_t* w_start, const int32_t* w_end, int64_t n_win,
-                   int lmax, int small_max, WindowCall* wc, int64_t* const zero[4] = nullptr, bool plan = true) {
-    int32_t* b_ws = a.take<int32_t>(n_win);
-    int32_t* b_we = a.take<int32_t>(n_win);
-    wc->plan.cand_lo = a.take<int32_t>(n_win);
-    wc->plan.cand_hi = a.take<int32_t>(n_win);
-    wc->plan.nchunks = a.take<uint32_t>(n_win);
-    wc->plan.chunk_off = a.take<uint32_t>(n_win + 1);
+int window_prepare(ftk_ctx* ctx, ContigData* c, const int32_t* w_start, const int32_t* w_end, int64_t n_win, int lmax,
+                   int small_max, WindowCall* wc, int64_t* const zero[4] = nullptr, bool plan = true) {
+    int32_t *b_ws = wc->b_ws, *b_we = wc->b_we;
     int rc;
     const size_t gap = (size_t)((const char*)b_we - (const char*)b_ws), bytes = gap + (size_t)n_win * 4;
     if (!is_device_ptr(w_start) && !is_device_ptr(w_end) && n_win > 0 && bytes <= (16u << 10)) {
-        // both arrays in ONE copy (the arena lays b_we out behind b_ws): a small host-to-device copy costs the stream
+        // both arrays in ONE copy (declare() lays b_we out behind b_ws): a small host-to-device copy costs the stream
         // ~4.5 us whatever its size, and a window call on a resident contig is tens of microseconds.  Only up to
         // 16 KB: the runtime takes a slower route for larger pageable copies (2 x 9.7 KB as one copy: +9 us).
         static thread_local std::vector<char> both;
@@ -313,6 +392,35 @@ bool windows_suit_block_path(const ftk_ctx* ctx, const ContigData& c, int lmax, 
     (void)c;
     (void)lmax;
     return total > 0 && longest * n_win <= 8 * total;
+}
+
+// ---- argument checks of the three feature paths (features_common, the batch, the fused pass) in one place; each path
+// keeps the message texts it has always had (item >= 0: the batch's wording)
+bool bad_blacklist(int64_t n_bl, const int32_t* bl_start, const int32_t* bl_end) {
+    return n_bl < 0 || (n_bl > 0 && (!bl_start || !bl_end));
+}
+
+int checked_gaps(ftk_ctx* ctx, const ftk_gaps* gaps, int item, ftk_gaps* g) {
+    *g = gaps ? *gaps : ftk_gaps{};
+    if (!g->has_gaps || (g->n_telo >= 0 && g->n_telo <= FTK_MAX_TELOMERES)) return FTK_OK;
+    if (item >= 0) return fail(ctx, FTK_ERR_INVALID, "item %d: at most %d telomere intervals", item, FTK_MAX_TELOMERES);
+    return fail(ctx, FTK_ERR_INVALID, "at most %d telomere intervals per contig are supported", FTK_MAX_TELOMERES);
+}
+
+template <class P>  // FeatItem, FusedParams
+void set_gap_constants(const ftk_gaps& g, P* p) {
+    int gc[4];
+    gap_constants(g, gc);
+    p->cen0 = gc[0]; p->cen1 = gc[1]; p->tel0 = gc[2]; p->tel1 = gc[3];
+}
+
+// the batch's and the fused pass's output checks (features_common words its histogram checks differently)
+int check_delfi_hist_outputs(ftk_ctx* ctx, const int64_t* short_out, const int64_t* long_out, const uint32_t* hist_out,
+                             int32_t n_bins, int max_bins, const int64_t* overflow_out) {
+    if ((short_out || long_out) && (!short_out || !long_out)) return fail(ctx, FTK_ERR_INVALID, "NULL DELFI output pointer");
+    if (hist_out && (n_bins <= 0 || n_bins > max_bins || !overflow_out))
+        return fail(ctx, FTK_ERR_INVALID, "histogram needs n_bins in [1, %d] and overflow_out", max_bins);
+    return FTK_OK;
 }
 
 }  // namespace
@@ -758,6 +866,15 @@ struct FeatCall {
     bool want_hist() const { return hist_out || stats_out; }
 };
 
+// coverage + length histogram + DELFI counts as one request (ftk_window_features, ftk_window_features_wps)
+void every_feature_call(FeatCall* fc, const ftk_filter* f, int64_t* count_out, int32_t len_lo, int32_t n_bins, uint32_t* hist_out,
+                        int64_t* overflow_out, int32_t delfi_mapq_min, const int32_t* bl_start, const int32_t* bl_end,
+                        int64_t n_bl, const ftk_gaps* gaps, int64_t* short_out, int64_t* long_out) {
+    *fc = FeatCall{.f = f, .count_out = count_out, .hist_out = hist_out, .overflow_out = overflow_out, .len_lo = len_lo,
+                   .n_bins = n_bins, .delfi = short_out || long_out, .mapq_min = delfi_mapq_min, .bl_start = bl_start,
+                   .bl_end = bl_end, .n_bl = n_bl, .gaps = gaps, .short_out = short_out, .long_out = long_out};
+}
+
 // tail: a whole-interval WPS to run in the same launch (see launch_window_features).  scratch_prefix > 0: the caller keeps
 // that many bytes at the start of the ctx scratch for itself - the tail's scores when they are bound for host memory -
 // and tail->out is taken to be the scratch base.
@@ -781,49 +898,39 @@ int features_common(ftk_ctx* ctx, int contig_id, const int32_t* w_start, const i
     HIPCHK(ctx, hipSetDevice(ctx->device));
     if (fc.delfi) {
         if (!fc.short_out || !fc.long_out) return fail(ctx, FTK_ERR_INVALID, "NULL DELFI output pointer");
-        if (fc.n_bl < 0 || (fc.n_bl > 0 && (!fc.bl_start || !fc.bl_end)))
-            return fail(ctx, FTK_ERR_INVALID, "bad blacklist arguments");
-        if (fc.gaps) g = *fc.gaps;
-        if (g.has_gaps && (g.n_telo < 0 || g.n_telo > FTK_MAX_TELOMERES))
-            return fail(ctx, FTK_ERR_INVALID, "at most %d telomere intervals per contig are supported", FTK_MAX_TELOMERES);
+        if (bad_blacklist(fc.n_bl, fc.bl_start, fc.bl_end)) return fail(ctx, FTK_ERR_INVALID, "bad blacklist arguments");
+        if ((rc = checked_gaps(ctx, fc.gaps, -1, &g))) return rc;
         if (is_device_ptr(w_start) || is_device_ptr(w_end) || is_device_ptr(fc.bl_start))
             return fail(ctx, FTK_ERR_INVALID, "DELFI takes host window and blacklist arrays");
         if ((rc = get_delfi_meta(ctx, contig_id, w_start, w_end, n_win, fc.bl_start, fc.bl_end, fc.n_bl, &meta)))
             return rc;
     }
-    const bool c_dev = is_device_ptr(fc.count_out), h_dev = is_device_ptr(fc.hist_out),
-               o_dev = is_device_ptr(fc.overflow_out), s_dev = is_device_ptr(fc.short_out),
-               l_dev = is_device_ptr(fc.long_out), n_dev = is_device_ptr(fc.nfrag_out);
-    const bool st_dev = is_device_ptr(fc.stats_out);
     const size_t hist_elems = fc.want_hist() ? (size_t)n_win * (size_t)fc.n_bins : 0;
-    size_t need = window_scratch_bytes(n_win) + 5 * align_up(n_win * 8) + (h_dev ? 0 : align_up(hist_elems * 4)) +
-                  (fc.stats_out && !st_dev ? align_up((size_t)n_win * 7 * 8) : 0);
-    if ((rc = reserve_scratch(ctx, scratch_prefix + need))) return rc;
-    Arena a(ctx);
-    a.off = scratch_prefix;
+    FeatureRequest r;
+    r.filter = fc.f;
+    r.len_lo = fc.len_lo;
+    r.n_bins = fc.n_bins;
+    r.motif = fc.motif;
+    double* d_stats = nullptr;
+    int64_t* d_nfrag = nullptr;
+    WindowCall wc;
+    Scratch s(ctx, scratch_prefix);
+    declare_feature_outputs(s, &r, n_win, hist_elems, fc.want_hist(), fc.count_out, fc.hist_out, fc.overflow_out,
+                            fc.delfi ? fc.short_out : nullptr, fc.delfi ? fc.long_out : nullptr);
+    if (fc.stats_out) s.out(&d_stats, fc.stats_out, (size_t)n_win * 7);
+    if (fc.delfi) {
+        if (fc.nfrag_out) s.out(&d_nfrag, fc.nfrag_out, n_win);
+        r.delfi_mapq_min = fc.mapq_min;
+        r.gaps = g;
+        if (meta->n_r) { r.bl_off = meta->d_off; r.bl_r0 = meta->d_r0; r.bl_pm = meta->d_pm; }
+    }
+    wc.declare(s, n_win);
+    if ((rc = s.reserve())) return rc;
     WpsTail tail_here;
     if (tail && scratch_prefix) {
         tail_here = *tail;
         tail_here.out = (int64_t*)ctx->scratch;
         tail = &tail_here;
-    }
-    FeatureRequest r;
-    r.filter = fc.f;
-    r.cov_out = fc.count_out ? (c_dev ? fc.count_out : a.take<int64_t>(n_win)) : nullptr;
-    r.hist_out = fc.want_hist() ? (h_dev ? fc.hist_out : a.take<uint32_t>(hist_elems)) : nullptr;
-    r.over_out = fc.want_hist() ? (o_dev && fc.hist_out ? fc.overflow_out : a.take<int64_t>(n_win)) : nullptr;
-    double* d_stats = fc.stats_out ? (st_dev ? fc.stats_out : a.take<double>((size_t)n_win * 7)) : nullptr;
-    r.len_lo = fc.len_lo;
-    r.n_bins = fc.n_bins;
-    r.motif = fc.motif;
-    int64_t* d_nfrag = nullptr;
-    if (fc.delfi) {
-        r.short_out = s_dev ? fc.short_out : a.take<int64_t>(n_win);
-        r.long_out = l_dev ? fc.long_out : a.take<int64_t>(n_win);
-        d_nfrag = fc.nfrag_out ? (n_dev ? fc.nfrag_out : a.take<int64_t>(n_win)) : nullptr;
-        r.delfi_mapq_min = fc.mapq_min;
-        r.gaps = g;
-        if (meta->n_r) { r.bl_off = meta->d_off; r.bl_r0 = meta->d_r0; r.bl_pm = meta->d_pm; }
     }
     // longest fragment any requested feature can accept
     int lmax = 0;
@@ -832,9 +939,8 @@ int features_common(ftk_ctx* ctx, int contig_id, const int32_t* w_start, const i
     const bool small_path = !(fc.want_hist() && fc.n_bins > kHistSmallMaxBins);
     const bool block_path = !is_device_ptr(w_start) && !is_device_ptr(w_end) &&
                             windows_suit_block_path(ctx, *c, lmax, w_start, w_end, n_win);
-    WindowCall wc;
     int64_t* zero[4] = {r.cov_out, r.short_out, r.long_out, nullptr};
-    if ((rc = window_prepare(ctx, c, a, meta ? meta->d_ws : w_start, meta ? meta->d_we : w_end, n_win, lmax,
+    if ((rc = window_prepare(ctx, c, meta ? meta->d_ws : w_start, meta ? meta->d_we : w_end, n_win, lmax,
                              small_path ? kSmallMax : -1, &wc, zero, !block_path)))
         return rc;
     if (r.hist_out && !small_path && !block_path) {  // with the wave-per-window pass on, it writes / clears every row itself
@@ -857,21 +963,7 @@ int features_common(ftk_ctx* ctx, int contig_id, const int32_t* w_start, const i
     if (d_nfrag) launch_add_i64(ctx->stream, r.short_out, r.long_out, d_nfrag, (int)n_win);
     if (d_stats) launch_window_stats(ctx->stream, r.hist_out, (int)n_win, fc.n_bins, fc.len_lo, fc.short_cut, d_stats);
     HIPCHK(ctx, hipGetLastError());
-    bool host_out = false;
-    auto back = [&](void* dst, const void* src, size_t bytes, bool dev) -> hipError_t {
-        if (!dst || dev) return hipSuccess;
-        host_out = true;
-        return hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, ctx->stream);
-    };
-    HIPCHK(ctx, back(fc.count_out, r.cov_out, n_win * 8, c_dev));
-    HIPCHK(ctx, back(fc.hist_out, r.hist_out, hist_elems * 4, h_dev));
-    HIPCHK(ctx, back(fc.hist_out ? fc.overflow_out : nullptr, r.over_out, n_win * 8, o_dev));
-    HIPCHK(ctx, back(fc.short_out, r.short_out, n_win * 8, s_dev));
-    HIPCHK(ctx, back(fc.long_out, r.long_out, n_win * 8, l_dev));
-    HIPCHK(ctx, back(fc.nfrag_out, d_nfrag, n_win * 8, n_dev));
-    HIPCHK(ctx, back(fc.stats_out, d_stats, (size_t)n_win * 7 * 8, st_dev));
-    if (host_out) HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    return FTK_OK;
+    return s.finish();
 }
 
 }  // namespace
@@ -886,9 +978,8 @@ int ftk_window_features_batch(ftk_ctx* ctx, const ftk_feature_item* items, int32
     if (!items) return fail(ctx, FTK_ERR_INVALID, "items is NULL");
     const bool ch = count_out || hist_out, df = short_out || long_out;
     if (!ch && !df) return fail(ctx, FTK_ERR_INVALID, "no feature requested");
-    if (df && (!short_out || !long_out)) return fail(ctx, FTK_ERR_INVALID, "NULL DELFI output pointer");
-    if (hist_out && (n_bins <= 0 || n_bins > kHistMaxBins || !overflow_out))
-        return fail(ctx, FTK_ERR_INVALID, "histogram needs n_bins in [1, %d] and overflow_out", kHistMaxBins);
+    int rc = check_delfi_hist_outputs(ctx, short_out, long_out, hist_out, n_bins, kHistMaxBins, overflow_out);
+    if (rc) return rc;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     // make room first: an eviction in the middle of the loop below could free an earlier item's arrays
     while (ctx->delfi_cache.size() + (size_t)n_items > kDelfiCacheMax) {
@@ -902,19 +993,15 @@ int ftk_window_features_batch(ftk_ctx* ctx, const ftk_feature_item* items, int32
     for (int i = 0; i < n_items; ++i) {
         const ftk_feature_item& it = items[i];
         ContigData* c;
-        int rc = get_contig(ctx, it.contig_id, &c);
-        if (rc) return rc;
+        if ((rc = get_contig(ctx, it.contig_id, &c))) return rc;
         if (ch && (rc = check_filter(ctx, f, *c))) return rc;
         if (it.n_win <= 0 || it.n_win > (1 << 30) || !it.w_start || !it.w_end)
             return fail(ctx, FTK_ERR_INVALID, "item %d: bad window arguments", i);
-        if (it.n_bl < 0 || (it.n_bl > 0 && (!it.bl_start || !it.bl_end)))
-            return fail(ctx, FTK_ERR_INVALID, "item %d: bad blacklist arguments", i);
+        if (bad_blacklist(it.n_bl, it.bl_start, it.bl_end)) return fail(ctx, FTK_ERR_INVALID, "item %d: bad blacklist arguments", i);
         if (is_device_ptr(it.w_start) || is_device_ptr(it.w_end) || is_device_ptr(it.bl_start))
             return fail(ctx, FTK_ERR_INVALID, "item %d: windows and blacklist must be host arrays", i);
         ftk_gaps g{};
-        if (it.gaps) g = *it.gaps;
-        if (g.has_gaps && (g.n_telo < 0 || g.n_telo > FTK_MAX_TELOMERES))
-            return fail(ctx, FTK_ERR_INVALID, "item %d: at most %d telomere intervals", i, FTK_MAX_TELOMERES);
+        if ((rc = checked_gaps(ctx, it.gaps, i, &g))) return rc;
         DelfiMeta* meta = nullptr;
         if ((rc = get_delfi_meta(ctx, it.contig_id, it.w_start, it.w_end, it.n_win, df ? it.bl_start : nullptr,
                                  df ? it.bl_end : nullptr, df ? it.n_bl : 0, &meta)))
@@ -931,9 +1018,7 @@ int ftk_window_features_batch(ftk_ctx* ctx, const ftk_feature_item* items, int32
         if (ch) lmax = std::max(lmax, eff_lmax(f, *c));
         if (df) lmax = std::max(lmax, std::max(0, std::min(220, c->max_len)));
         h.lmax = lmax;
-        int gc[4];
-        gap_constants(g, gc);
-        h.cen0 = gc[0]; h.cen1 = gc[1]; h.tel0 = gc[2]; h.tel1 = gc[3];
+        set_gap_constants(g, &h);
         total += it.n_win;
         n_bam += c->v.r1_start != nullptr && (!f || f->fetch_mode == FTK_FETCH_BAM_READ1);
         if (total > (1 << 30)) return fail(ctx, FTK_ERR_INVALID, "too many windows in one batch");
@@ -941,40 +1026,19 @@ int ftk_window_features_batch(ftk_ctx* ctx, const ftk_feature_item* items, int32
     if (n_bam != 0 && n_bam != n_items)
         return fail(ctx, FTK_ERR_INVALID, "a batch cannot mix contigs with and without read1 columns");
     void* d_items = nullptr;
-    int rc = upload_batch_descriptors(ctx, 0, host.data(), host.size() * sizeof(FeatItem), &d_items);
-    if (rc) return rc;
-    const bool c_dev = is_device_ptr(count_out), h_dev = is_device_ptr(hist_out), o_dev = is_device_ptr(overflow_out),
-               s_dev = is_device_ptr(short_out), l_dev = is_device_ptr(long_out);
-    const size_t hist_elems = hist_out ? (size_t)total * (size_t)n_bins : 0;
-    if ((rc = reserve_scratch(ctx, 4 * align_up(total * 8) + (h_dev ? 0 : align_up(hist_elems * 4))))) return rc;
-    Arena a(ctx);
+    if ((rc = upload_batch_descriptors(ctx, 0, host.data(), host.size() * sizeof(FeatItem), &d_items))) return rc;
     FeatureRequest r;
     r.filter = f;
-    r.cov_out = count_out ? (c_dev ? count_out : a.take<int64_t>(total)) : nullptr;
-    r.hist_out = hist_out ? (h_dev ? hist_out : a.take<uint32_t>(hist_elems)) : nullptr;
-    r.over_out = hist_out ? (o_dev ? overflow_out : a.take<int64_t>(total)) : nullptr;
     r.len_lo = len_lo;
     r.n_bins = n_bins;
-    if (df) {
-        r.short_out = s_dev ? short_out : a.take<int64_t>(total);
-        r.long_out = l_dev ? long_out : a.take<int64_t>(total);
-        r.delfi_mapq_min = delfi_mapq_min;
-    }
+    Scratch s(ctx);
+    declare_feature_outputs(s, &r, total, (size_t)total * (size_t)n_bins, hist_out != nullptr, count_out, hist_out, overflow_out,
+                            short_out, long_out);
+    if (df) r.delfi_mapq_min = delfi_mapq_min;
+    if ((rc = s.reserve())) return rc;
     launch_window_features_batch(ctx->stream, (const FeatItem*)d_items, n_items, (int)total, r, n_bam != 0);
     HIPCHK(ctx, hipGetLastError());
-    bool host_out = false;
-    auto back = [&](void* dst, const void* src, size_t bytes, bool dev) -> hipError_t {
-        if (!dst || dev) return hipSuccess;
-        host_out = true;
-        return hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, ctx->stream);
-    };
-    HIPCHK(ctx, back(count_out, r.cov_out, total * 8, c_dev));
-    HIPCHK(ctx, back(hist_out, r.hist_out, hist_elems * 4, h_dev));
-    HIPCHK(ctx, back(hist_out ? overflow_out : nullptr, r.over_out, total * 8, o_dev));
-    HIPCHK(ctx, back(short_out, r.short_out, total * 8, s_dev));
-    HIPCHK(ctx, back(long_out, r.long_out, total * 8, l_dev));
-    if (host_out) HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    return FTK_OK;
+    return s.finish();
 }
 
 int ftk_window_counts(ftk_ctx* ctx, int contig_id, const int32_t* w_start, const int32_t* w_end, int64_t n_win,
@@ -1031,20 +1095,8 @@ int ftk_window_features(ftk_ctx* ctx, int contig_id, const int32_t* w_start, con
                         int64_t* overflow_out, int32_t delfi_mapq_min, const int32_t* bl_start, const int32_t* bl_end,
                         int64_t n_bl, const ftk_gaps* gaps, int64_t* short_out, int64_t* long_out) {
     FeatCall fc;
-    fc.f = f;
-    fc.count_out = count_out;
-    fc.hist_out = hist_out;
-    fc.overflow_out = overflow_out;
-    fc.len_lo = len_lo;
-    fc.n_bins = n_bins;
-    fc.delfi = short_out != nullptr || long_out != nullptr;
-    fc.mapq_min = delfi_mapq_min;
-    fc.bl_start = bl_start;
-    fc.bl_end = bl_end;
-    fc.n_bl = n_bl;
-    fc.gaps = gaps;
-    fc.short_out = short_out;
-    fc.long_out = long_out;
+    every_feature_call(&fc, f, count_out, len_lo, n_bins, hist_out, overflow_out, delfi_mapq_min, bl_start, bl_end, n_bl, gaps,
+                       short_out, long_out);
     return features_common(ctx, contig_id, w_start, w_end, n_win, fc);
 }
 
@@ -1059,12 +1111,13 @@ static int select_common(ftk_ctx* ctx, int contig_id, int32_t w_start, int32_t w
     if (!n_out || cap < 0) return fail(ctx, FTK_ERR_INVALID, "bad output arguments");
     HIPCHK(ctx, hipSetDevice(ctx->device));
     // candidate range of the single window (planned on the device, read back)
-    if ((rc = reserve_scratch(ctx, window_scratch_bytes(1)))) return rc;
     int32_t lohi[2];
     {
-        Arena a(ctx);
+        Scratch s(ctx);
         WindowCall wc;
-        if ((rc = window_prepare(ctx, c, a, &w_start, &w_end, 1, eff_lmax(f, *c), kSmallMax, &wc))) return rc;
+        wc.declare(s, 1);
+        if ((rc = s.reserve())) return rc;
+        if ((rc = window_prepare(ctx, c, &w_start, &w_end, 1, eff_lmax(f, *c), kSmallMax, &wc))) return rc;
         HIPCHK(ctx, hipMemcpyAsync(&lohi[0], wc.plan.cand_lo, 4, hipMemcpyDeviceToHost, ctx->stream));
         HIPCHK(ctx, hipMemcpyAsync(&lohi[1], wc.plan.cand_hi, 4, hipMemcpyDeviceToHost, ctx->stream));
         HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
@@ -1077,17 +1130,20 @@ static int select_common(ftk_ctx* ctx, int contig_id, int32_t w_start, int32_t w
     }
     const int nb = (int)((n_cand + 255) / 256);
     const int64_t ncap = std::min<int64_t>(cap, n_cand);
-    size_t need = 2 * align_up((size_t)(nb + 1) * 4) + 4 * align_up(ncap * 4) + 2 * align_up(ncap);
-    if ((rc = reserve_scratch(ctx, need))) return rc;
-    Arena a(ctx);
-    uint32_t* d_cnt = a.take<uint32_t>(nb + 1);
-    uint32_t* d_off = a.take<uint32_t>(nb + 1);
-    int32_t* d_len = len_out ? a.take<int32_t>(ncap) : nullptr;
-    int32_t* d_s = start_out ? a.take<int32_t>(ncap) : nullptr;
-    int32_t* d_e = end_out ? a.take<int32_t>(ncap) : nullptr;
-    uint8_t* d_q = mapq_out ? a.take<uint8_t>(ncap) : nullptr;
-    uint8_t* d_st = strand_out ? a.take<uint8_t>(ncap) : nullptr;
-    int32_t* d_ord = c->v.order ? a.take<int32_t>(ncap) : nullptr;
+    // (the columns are host arrays and only their first *n_out rows go back: temporaries, copied below)
+    uint32_t *d_cnt = nullptr, *d_off = nullptr;
+    int32_t *d_len = nullptr, *d_s = nullptr, *d_e = nullptr, *d_ord = nullptr;
+    uint8_t *d_q = nullptr, *d_st = nullptr;
+    Scratch s(ctx);
+    s.tmp(&d_cnt, nb + 1);
+    s.tmp(&d_off, nb + 1);
+    if (len_out) s.tmp(&d_len, ncap);
+    if (start_out) s.tmp(&d_s, ncap);
+    if (end_out) s.tmp(&d_e, ncap);
+    if (mapq_out) s.tmp(&d_q, ncap);
+    if (strand_out) s.tmp(&d_st, ncap);
+    if (c->v.order) s.tmp(&d_ord, ncap);
+    if ((rc = s.reserve())) return rc;
     launch_select_count(ctx->stream, c->v, lo, hi, w_start, w_end, *f, d_cnt);
     launch_scan_u32(ctx->stream, d_cnt, nb, d_off);
     launch_select_write(ctx->stream, c->v, lo, hi, w_start, w_end, *f, d_off, ncap, d_len, d_s, d_e, d_q, d_st, d_ord);

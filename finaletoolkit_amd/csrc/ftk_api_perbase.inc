@@ -1,4 +1,4 @@
-// Part of ftk_api.hip's translation unit (#included there, in this order: perbase, ref, comm) - per-base entry points: `ftk_wps*` (the narrow wire to the host, the merged feature + WPS launch, batches, intervals), `ftk_cleavage*`, `ftk_wps_adjust`.
+// Part of ftk_api.hip's translation unit (#included there, in this order: perbase, ref, comm, export) - per-base entry points: `ftk_wps*` (the narrow wire to the host, the merged feature + WPS launch, batches, intervals), `ftk_cleavage*`, `ftk_wps_adjust`, and their shared helpers (`ScoreOutput`, `open_wps_call`, `cleave_params`, `plan_interval_tiles`); buffers are bound through `Scratch` (ftk_api.hip).
 
 // ---- per-base scores to the host on a narrow wire -------------------------------------------------------------------
 // The reference's WPS is int64 per base (frag/_wps.py:176-188): 2 GB for chr1, 24.8 GB for a genome - and a device -> host
@@ -134,16 +134,115 @@ int copy_scores_narrow(ftk_ctx* ctx, const int64_t* d_scores, int16_t* d_narrow,
     *done = true;
     return FTK_OK;
 }
+
+// Whole-interval scores and their way into host memory (ftk_wps, ftk_window_features_wps).  Declared first on a Scratch,
+// host-bound scores sit at its base as wide | narrow | misfit; to_host() sends them on the narrow wire when that is on
+// and they fit, the plain way otherwise.  Scores the caller wants on the device need neither.
+struct ScoreOutput {
+    int64_t *user = nullptr, *d_wide = nullptr, n_pos = 0;
+    int16_t* d_narrow = nullptr;
+    int* d_misfit = nullptr;
+    bool host = false, narrow = false;
+    void declare(Scratch& s, int64_t* wps_out, int64_t n) {
+        static const bool narrow_env = !(getenv("FTK_WPS_NARROW_WIRE") && atoi(getenv("FTK_WPS_NARROW_WIRE")) == 0);
+        user = wps_out, n_pos = n;
+        host = s.out(&d_wide, wps_out, n, /*copy_back=*/false);
+        narrow = host && narrow_env && n >= kNarrowMin;
+        if (narrow) {
+            s.tmp(&d_narrow, n);
+            s.tmp(&d_misfit, 1);
+        }
+    }
+    int to_host(ftk_ctx* ctx) const {
+        if (!host) return FTK_OK;
+        bool done = false;
+        int rc;
+        if (narrow && (rc = copy_scores_narrow(ctx, d_wide, d_narrow, d_misfit, n_pos, user, &done))) return rc;
+        if (!done) {
+            HIPCHK(ctx, hipMemcpyAsync(user, d_wide, (size_t)n_pos * 8, hipMemcpyDeviceToHost, ctx->stream));
+            HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+        }
+        return FTK_OK;
+    }
+};
+
+// the opening of the per-base WPS entry points: the ctx, its contig, the WPS parameters
+int open_wps_call(ftk_ctx* ctx, int contig_id, int64_t chrom_size, int32_t window_size, int32_t min_len, int32_t max_len,
+                  int32_t mapq_min, ContigData** c, WpsParams* p) {
+    if (!ctx) return fail(nullptr, FTK_ERR_INVALID, "ctx is NULL");
+    int rc = get_contig(ctx, contig_id, c);
+    return rc ? rc : wps_params(ctx, **c, chrom_size, window_size, min_len, max_len, mapq_min, p);
+}
+
+CleaveParams cleave_params(const ContigData& c, int32_t min_len, int32_t max_len, int32_t mapq_min) {
+    CleaveParams p{};
+    p.min_len = min_len < 0 ? INT32_MIN : min_len;
+    p.max_len = max_len < 0 ? INT32_MAX : max_len;
+    p.mapq_min = mapq_min;
+    p.lmax = std::max(0, max_len < 0 ? c.max_len : std::min(max_len, c.max_len));
+    return p;
+}
+
+// Many intervals of one contig as ONE launch: per interval its start, stop and output offset, per tile its interval and
+// its number within that (ftk_wps_intervals, ftk_cleavage_intervals).
+struct TilePlan {
+    int64_t *d_s = nullptr, *d_e = nullptr, *d_o = nullptr;
+    int32_t *d_ti = nullptr, *d_tk = nullptr;
+    int64_t n_tiles = 0, total_out = 0;
+    std::vector<int32_t> tile_iv, tile_k;  // pageable staging of the uploads: the caller's finish(true) waits for them
+};
+
+// Checks the arguments (an interval may start at `lowest`), builds the plan, binds it and the output - *d_out: `out` or
+// its stand-in in the scratch, for s.finish() to copy back - and uploads it.  FTK_OK with n_tiles == 0: nothing to do.
+extern "C++" {  // (a template, in a file that is included inside ftk_api.hip's extern "C" block)
+template <class T>
+int plan_interval_tiles(ftk_ctx* ctx, Scratch& s, const int64_t* iv_start, const int64_t* iv_stop, int64_t n_iv,
+                        const int64_t* out_offset, int64_t lowest, const char* tiles_name, T* out, T** d_out, TilePlan* tp) {
+    if (n_iv < 0 || n_iv > INT32_MAX) return fail(ctx, FTK_ERR_INVALID, "n_iv out of range");
+    if (n_iv == 0) return FTK_OK;
+    if (!iv_start || !iv_stop || !out_offset || !out) return fail(ctx, FTK_ERR_INVALID, "NULL argument");
+    if (is_device_ptr(iv_start) || is_device_ptr(iv_stop) || is_device_ptr(out_offset))
+        return fail(ctx, FTK_ERR_INVALID, "interval arrays must be host arrays");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    for (int64_t i = 0; i < n_iv; ++i) {
+        const int64_t len = iv_stop[i] - iv_start[i];
+        if (len <= 0) continue;
+        if (iv_start[i] < lowest || iv_stop[i] > (1LL << 31)) return fail(ctx, FTK_ERR_INVALID, "interval out of range");
+        if (out_offset[i] < 0) return fail(ctx, FTK_ERR_INVALID, "negative output offset");
+        tp->total_out = std::max(tp->total_out, out_offset[i] + len);
+        for (int64_t k = 0; k < (len + kWpsTile - 1) / kWpsTile; ++k) {
+            tp->tile_iv.push_back((int32_t)i);
+            tp->tile_k.push_back((int32_t)k);
+        }
+    }
+    const size_t n_tiles = tp->tile_iv.size();
+    if (n_tiles == 0) return FTK_OK;
+    if (n_tiles > (size_t)INT32_MAX) return fail(ctx, FTK_ERR_INVALID, "too many %s in one call", tiles_name);
+    s.tmp(&tp->d_s, n_iv);
+    s.tmp(&tp->d_e, n_iv);
+    s.tmp(&tp->d_o, n_iv);
+    s.tmp(&tp->d_ti, n_tiles);
+    s.tmp(&tp->d_tk, n_tiles);
+    s.out(d_out, out, tp->total_out);
+    int rc = s.reserve();
+    if (rc) return rc;
+    HIPCHK(ctx, hipMemcpyAsync(tp->d_s, iv_start, n_iv * 8, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(tp->d_e, iv_stop, n_iv * 8, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(tp->d_o, out_offset, n_iv * 8, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(tp->d_ti, tp->tile_iv.data(), n_tiles * 4, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(tp->d_tk, tp->tile_k.data(), n_tiles * 4, hipMemcpyHostToDevice, ctx->stream));
+    tp->n_tiles = (int64_t)n_tiles;
+    return FTK_OK;
+}
+}  // extern "C++"
 }  // namespace
 
 int ftk_wps(ftk_ctx* ctx, int contig_id, int64_t start, int64_t stop, int64_t chrom_size, int32_t window_size,
             int32_t min_len, int32_t max_len, int32_t mapq_min, int64_t* wps_out) {
-    if (!ctx) return fail(nullptr, FTK_ERR_INVALID, "ctx is NULL");
     ContigData* c;
-    int rc = get_contig(ctx, contig_id, &c);
-    if (rc) return rc;
     WpsParams p{};
-    if ((rc = wps_params(ctx, *c, chrom_size, window_size, min_len, max_len, mapq_min, &p))) return rc;
+    int rc = open_wps_call(ctx, contig_id, chrom_size, window_size, min_len, max_len, mapq_min, &c, &p);
+    if (rc) return rc;
     if (stop <= start) return FTK_OK;  // degenerate interval: empty result (frag/_wps.py:145-152)
     if (start < -(1LL << 30) || stop > (1LL << 31)) return fail(ctx, FTK_ERR_INVALID, "interval out of range");
     if (!wps_out) return fail(ctx, FTK_ERR_INVALID, "wps_out is NULL");
@@ -162,32 +261,18 @@ int ftk_wps(ftk_ctx* ctx, int contig_id, int64_t start, int64_t stop, int64_t ch
                 fprintf(stderr, "[ftk_wps] %lld positions: %.1f ms (scratch %.1f, launch %.1f)\n", n, ms, reserve_ms, kernel_ms);
         }
     } slow{slow_ms, t_call, (long long)n_pos};
-    const bool out_dev = is_device_ptr(wps_out);
-    static const bool narrow_env = !(getenv("FTK_WPS_NARROW_WIRE") && atoi(getenv("FTK_WPS_NARROW_WIRE")) == 0);
-    const bool narrow = !out_dev && narrow_env && n_pos >= kNarrowMin;
-    const size_t wide_bytes = align_up((size_t)n_pos * 8);
-    if (!out_dev && (rc = reserve_scratch(ctx, wide_bytes + (narrow ? align_up((size_t)n_pos * 2) + 256 : 0)))) return rc;
+    ScoreOutput so;
+    Scratch s(ctx);
+    so.declare(s, wps_out, n_pos);
+    if ((rc = s.reserve())) return rc;
     slow.reserve_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_call).count();
-    int64_t* d_out = out_dev ? wps_out : (int64_t*)ctx->scratch;
     p.start = start;
     p.stop = stop;
     const int64_t n_tiles = (n_pos + kWpsTile - 1) / kWpsTile;
-    launch_wps(ctx->stream, c->v, p, n_tiles, nullptr, nullptr, nullptr, nullptr, nullptr, d_out);
+    launch_wps(ctx->stream, c->v, p, n_tiles, nullptr, nullptr, nullptr, nullptr, nullptr, so.d_wide);
     HIPCHK(ctx, hipGetLastError());
     slow.kernel_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_call).count() - slow.reserve_ms;
-    if (!out_dev) {
-        bool done = false;
-        if (narrow) {
-            char* tail = (char*)ctx->scratch + wide_bytes;
-            if ((rc = copy_scores_narrow(ctx, d_out, (int16_t*)tail, (int*)(tail + align_up((size_t)n_pos * 2)), n_pos, wps_out, &done)))
-                return rc;
-        }
-        if (!done) {
-            HIPCHK(ctx, hipMemcpyAsync(wps_out, d_out, n_pos * 8, hipMemcpyDeviceToHost, ctx->stream));
-            HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-        }
-    }
-    return FTK_OK;
+    return so.to_host(ctx);
 }
 
 // ftk_window_features followed by ftk_wps on the same contig, as ONE launch when the request takes the FAST block
@@ -198,69 +283,38 @@ int ftk_window_features_wps(ftk_ctx* ctx, int contig_id, const int32_t* w_start,
                             int64_t n_bl, const ftk_gaps* gaps, int64_t* short_out, int64_t* long_out, int64_t start,
                             int64_t stop, int64_t chrom_size, int32_t window_size, int32_t min_len, int32_t max_len,
                             int32_t mapq_min, int64_t* wps_out) {
-    if (!ctx) return fail(nullptr, FTK_ERR_INVALID, "ctx is NULL");
     ContigData* c;
-    int rc = get_contig(ctx, contig_id, &c);
-    if (rc) return rc;
     WpsTail tail{};
-    if ((rc = wps_params(ctx, *c, chrom_size, window_size, min_len, max_len, mapq_min, &tail.p))) return rc;
+    int rc = open_wps_call(ctx, contig_id, chrom_size, window_size, min_len, max_len, mapq_min, &c, &tail.p);
+    if (rc) return rc;
     const bool wps_ok = stop > start && start >= -(1LL << 30) && stop <= (1LL << 31) && wps_out && n_win > 0;
-    // scores bound for host memory: the merged launch writes them to the head of the ctx scratch and they cross the link
-    // like ftk_wps' (16 bits per score when they fit)
-    const bool host_wps = wps_ok && !is_device_ptr(wps_out);
-    const int64_t n_pos = stop - start;
-    static const bool narrow_env = !(getenv("FTK_WPS_NARROW_WIRE") && atoi(getenv("FTK_WPS_NARROW_WIRE")) == 0);
-    const bool narrow = host_wps && narrow_env && n_pos >= kNarrowMin;
-    const size_t wide_bytes = host_wps ? align_up((size_t)n_pos * 8) : 0;
-    const size_t prefix = host_wps ? wide_bytes + (narrow ? align_up((size_t)n_pos * 2) + 256 : 0) : 0;
+    // scores bound for host memory: the merged launch writes them to the head of the ctx scratch - the prefix that
+    // features_common reserves in front of its own buffers - and they cross the link like ftk_wps' (ScoreOutput)
+    ScoreOutput so;
+    Scratch head(ctx);
+    if (wps_ok) so.declare(head, wps_out, stop - start);
     FeatCall fc;
-    fc.f = f;
-    fc.count_out = count_out;
-    fc.hist_out = hist_out;
-    fc.overflow_out = overflow_out;
-    fc.len_lo = len_lo;
-    fc.n_bins = n_bins;
-    fc.delfi = short_out || long_out;
-    fc.mapq_min = delfi_mapq_min;
-    fc.bl_start = bl_start;
-    fc.bl_end = bl_end;
-    fc.n_bl = n_bl;
-    fc.gaps = gaps;
-    fc.short_out = short_out;
-    fc.long_out = long_out;
+    every_feature_call(&fc, f, count_out, len_lo, n_bins, hist_out, overflow_out, delfi_mapq_min, bl_start, bl_end, n_bl, gaps,
+                       short_out, long_out);
     bool merged = false;
     if (wps_ok) {
         tail.p.start = start;
         tail.p.stop = stop;
         tail.n_tiles = (stop - start + kWpsTile - 1) / kWpsTile;
-        tail.out = wps_out;  // (host_wps: replaced by the scratch base inside features_common)
+        tail.out = wps_out;  // (host scores: replaced by the scratch base inside features_common)
     }
-    if ((rc = features_common(ctx, contig_id, w_start, w_end, n_win, fc, wps_ok ? &tail : nullptr, &merged, prefix))) return rc;
+    if ((rc = features_common(ctx, contig_id, w_start, w_end, n_win, fc, wps_ok ? &tail : nullptr, &merged, head.bytes()))) return rc;
     if (!merged) return ftk_wps(ctx, contig_id, start, stop, chrom_size, window_size, min_len, max_len, mapq_min, wps_out);
-    if (host_wps) {
-        int64_t* d_out = (int64_t*)ctx->scratch;
-        bool done = false;
-        if (narrow) {
-            char* nw = (char*)ctx->scratch + wide_bytes;
-            if ((rc = copy_scores_narrow(ctx, d_out, (int16_t*)nw, (int*)(nw + align_up((size_t)n_pos * 2)), n_pos, wps_out, &done)))
-                return rc;
-        }
-        if (!done) {
-            HIPCHK(ctx, hipMemcpyAsync(wps_out, d_out, (size_t)n_pos * 8, hipMemcpyDeviceToHost, ctx->stream));
-            HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-        }
-    }
-    return FTK_OK;
+    if ((rc = head.place())) return rc;
+    return so.to_host(ctx);
 }
 
 int ftk_wps_async(ftk_ctx* ctx, int contig_id, int64_t start, int64_t stop, int64_t chrom_size, int32_t window_size,
                   int32_t min_len, int32_t max_len, int32_t mapq_min, int64_t* wps_out_host, int* token_out) {
-    if (!ctx) return fail(nullptr, FTK_ERR_INVALID, "ctx is NULL");
     ContigData* c;
-    int rc = get_contig(ctx, contig_id, &c);
-    if (rc) return rc;
     WpsParams p{};
-    if ((rc = wps_params(ctx, *c, chrom_size, window_size, min_len, max_len, mapq_min, &p))) return rc;
+    int rc = open_wps_call(ctx, contig_id, chrom_size, window_size, min_len, max_len, mapq_min, &c, &p);
+    if (rc) return rc;
     if (!token_out) return fail(ctx, FTK_ERR_INVALID, "token_out is NULL");
     *token_out = -1;
     if (stop <= start) return FTK_OK;  // degenerate interval: empty result, nothing to wait for
@@ -323,56 +377,19 @@ int ftk_result_wait(ftk_ctx* ctx, int token) {
 int ftk_wps_intervals(ftk_ctx* ctx, int contig_id, const int64_t* iv_start, const int64_t* iv_stop, int64_t n_iv,
                       const int64_t* out_offset, int64_t chrom_size, int32_t window_size, int32_t min_len,
                       int32_t max_len, int32_t mapq_min, int64_t* wps_out) {
-    if (!ctx) return fail(nullptr, FTK_ERR_INVALID, "ctx is NULL");
     ContigData* c;
-    int rc = get_contig(ctx, contig_id, &c);
-    if (rc) return rc;
     WpsParams p{};
-    if ((rc = wps_params(ctx, *c, chrom_size, window_size, min_len, max_len, mapq_min, &p))) return rc;
-    if (n_iv < 0 || n_iv > INT32_MAX) return fail(ctx, FTK_ERR_INVALID, "n_iv out of range");
-    if (n_iv == 0) return FTK_OK;
-    if (!iv_start || !iv_stop || !out_offset || !wps_out) return fail(ctx, FTK_ERR_INVALID, "NULL argument");
-    if (is_device_ptr(iv_start) || is_device_ptr(iv_stop) || is_device_ptr(out_offset))
-        return fail(ctx, FTK_ERR_INVALID, "interval arrays must be host arrays");
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    std::vector<int32_t> tile_iv, tile_k;
-    int64_t total_out = 0;
-    for (int64_t i = 0; i < n_iv; ++i) {
-        int64_t len = iv_stop[i] - iv_start[i];
-        if (len <= 0) continue;
-        if (iv_start[i] < -(1LL << 30) || iv_stop[i] > (1LL << 31)) return fail(ctx, FTK_ERR_INVALID, "interval out of range");
-        if (out_offset[i] < 0) return fail(ctx, FTK_ERR_INVALID, "negative output offset");
-        total_out = std::max(total_out, out_offset[i] + len);
-        int64_t nt = (len + kWpsTile - 1) / kWpsTile;
-        for (int64_t k = 0; k < nt; ++k) {
-            tile_iv.push_back((int32_t)i);
-            tile_k.push_back((int32_t)k);
-        }
-    }
-    const size_t n_tiles = tile_iv.size();
-    if (n_tiles == 0) return FTK_OK;
-    if (n_tiles > (size_t)INT32_MAX) return fail(ctx, FTK_ERR_INVALID, "too many WPS tiles in one call");
-    const bool out_dev = is_device_ptr(wps_out);
-    size_t need = 3 * align_up(n_iv * 8) + 2 * align_up(n_tiles * 4) + (out_dev ? 0 : align_up(total_out * 8));
-    if ((rc = reserve_scratch(ctx, need))) return rc;
-    Arena a(ctx);
-    int64_t* d_s = a.take<int64_t>(n_iv);
-    int64_t* d_e = a.take<int64_t>(n_iv);
-    int64_t* d_o = a.take<int64_t>(n_iv);
-    int32_t* d_ti = a.take<int32_t>(n_tiles);
-    int32_t* d_tk = a.take<int32_t>(n_tiles);
-    int64_t* d_out = out_dev ? wps_out : a.take<int64_t>(total_out);
-    HIPCHK(ctx, hipMemcpyAsync(d_s, iv_start, n_iv * 8, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(d_e, iv_stop, n_iv * 8, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(d_o, out_offset, n_iv * 8, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(d_ti, tile_iv.data(), n_tiles * 4, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(d_tk, tile_k.data(), n_tiles * 4, hipMemcpyHostToDevice, ctx->stream));
-    launch_wps(ctx->stream, c->v, p, (int64_t)n_tiles, d_s, d_e, d_o, d_ti, d_tk, d_out);
+    int rc = open_wps_call(ctx, contig_id, chrom_size, window_size, min_len, max_len, mapq_min, &c, &p);
+    if (rc) return rc;
+    Scratch s(ctx);
+    TilePlan tp;
+    int64_t* d_out = nullptr;
+    if ((rc = plan_interval_tiles(ctx, s, iv_start, iv_stop, n_iv, out_offset, -(1LL << 30), "WPS tiles", wps_out, &d_out, &tp)))
+        return rc;
+    if (tp.n_tiles == 0) return FTK_OK;
+    launch_wps(ctx->stream, c->v, p, tp.n_tiles, tp.d_s, tp.d_e, tp.d_o, tp.d_ti, tp.d_tk, d_out);
     HIPCHK(ctx, hipGetLastError());
-    if (!out_dev) HIPCHK(ctx, hipMemcpyAsync(wps_out, d_out, total_out * 8, hipMemcpyDeviceToHost, ctx->stream));
-    // tile descriptor vectors are pageable staging: wait before they go away
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    return FTK_OK;
+    return s.finish(/*must_sync=*/true);  // (the plan's tile vectors are pageable staging)
 }
 
 int ftk_wps_window_features(ftk_ctx* ctx, int contig_id, int64_t start, int64_t stop, int64_t chrom_size,
@@ -381,12 +398,10 @@ int ftk_wps_window_features(ftk_ctx* ctx, int contig_id, int64_t start, int64_t 
                             int32_t len_lo, int32_t n_bins, uint32_t* hist_out, int64_t* overflow_out,
                             int32_t delfi_mapq_min, const int32_t* bl_start, const int32_t* bl_end, int64_t n_bl,
                             const ftk_gaps* gaps, int64_t* short_out, int64_t* long_out) {
-    if (!ctx) return fail(nullptr, FTK_ERR_INVALID, "ctx is NULL");
     ContigData* c;
-    int rc = get_contig(ctx, contig_id, &c);
-    if (rc) return rc;
     WpsParams p{};
-    if ((rc = wps_params(ctx, *c, chrom_size, window_size, min_len, max_len, mapq_min, &p))) return rc;
+    int rc = open_wps_call(ctx, contig_id, chrom_size, window_size, min_len, max_len, mapq_min, &c, &p);
+    if (rc) return rc;
     const bool ch = count_out || hist_out, df = short_out || long_out;
     if (!wps_out || (!ch && !df)) return fail(ctx, FTK_ERR_INVALID, "needs wps_out and at least one feature output");
     if (ch && (!f || f->policy != FTK_POLICY_MIDPOINT))
@@ -395,9 +410,8 @@ int ftk_wps_window_features(ftk_ctx* ctx, int contig_id, int64_t start, int64_t 
     // fetch semantics as everywhere else: read1 overlap (io/alignment.py:245) on a contig with read1 columns unless
     // the filter asks for the tabix rule
     const bool bam = c->v.r1_start != nullptr && (!ch || f->fetch_mode == FTK_FETCH_BAM_READ1);
-    if (df && (!short_out || !long_out)) return fail(ctx, FTK_ERR_INVALID, "NULL DELFI output pointer");
-    if (hist_out && (n_bins <= 0 || n_bins > 8192 || !overflow_out))
-        return fail(ctx, FTK_ERR_INVALID, "histogram needs n_bins in [1, 8192] and overflow_out");
+    // (8192: this pass's own histogram limit, below kHistMaxBins)
+    if ((rc = check_delfi_hist_outputs(ctx, short_out, long_out, hist_out, n_bins, 8192, overflow_out))) return rc;
     if (n_win <= 0 || win_start < 0 || win_len < kWpsTile + c->max_len || (int64_t)win_start + (int64_t)n_win * win_len > (1LL << 31))
         return fail(ctx, FTK_ERR_INVALID, "bins must be at least %d bp long (tile + longest fragment) and end below 2^31",
                     kWpsTile + c->max_len);
@@ -405,7 +419,7 @@ int ftk_wps_window_features(ftk_ctx* ctx, int contig_id, int64_t start, int64_t 
         return fail(ctx, FTK_ERR_INVALID, "the WPS interval must cover every fragment of the contig (start <= 0, stop >= %d)",
                     c->max_end);
     if (start < -(1LL << 30) || stop > (1LL << 31)) return fail(ctx, FTK_ERR_INVALID, "interval out of range");
-    if (n_bl < 0 || (n_bl > 0 && (!bl_start || !bl_end)) || is_device_ptr(bl_start))
+    if (bad_blacklist(n_bl, bl_start, bl_end) || is_device_ptr(bl_start))
         return fail(ctx, FTK_ERR_INVALID, "bad blacklist arguments");
     HIPCHK(ctx, hipSetDevice(ctx->device));
     FusedParams F{};
@@ -425,12 +439,8 @@ int ftk_wps_window_features(ftk_ctx* ctx, int contig_id, int64_t start, int64_t 
     F.do_delfi = df;
     F.df_q = std::min(std::max(delfi_mapq_min, 0), 256);
     ftk_gaps g{};
-    if (gaps) g = *gaps;
-    if (g.has_gaps && (g.n_telo < 0 || g.n_telo > FTK_MAX_TELOMERES))
-        return fail(ctx, FTK_ERR_INVALID, "at most %d telomere intervals per contig are supported", FTK_MAX_TELOMERES);
-    int gc[4];
-    gap_constants(g, gc);
-    F.cen0 = gc[0]; F.cen1 = gc[1]; F.tel0 = gc[2]; F.tel1 = gc[3];
+    if ((rc = checked_gaps(ctx, gaps, -1, &g))) return rc;
+    set_gap_constants(g, &F);
     if (df && n_bl > 0) {  // per-bin blacklist CSR, cached like ftk_delfi_counts' (same key: the bins' arrays)
         std::vector<int32_t> ws(n_win), we(n_win);
         for (int k = 0; k < n_win; ++k) { ws[k] = win_start + k * win_len; we[k] = ws[k] + win_len; }
@@ -439,19 +449,12 @@ int ftk_wps_window_features(ftk_ctx* ctx, int contig_id, int64_t start, int64_t 
         if (meta->n_r) { F.bl_off = meta->d_off; F.bl_r0 = meta->d_r0; F.bl_pm = meta->d_pm; }
     }
     const int64_t n_pos = stop - start;
-    const bool w_dev = is_device_ptr(wps_out), c_dev = is_device_ptr(count_out), h_dev = is_device_ptr(hist_out),
-               o_dev = is_device_ptr(overflow_out), s_dev = is_device_ptr(short_out), l_dev = is_device_ptr(long_out);
     const size_t hist_elems = hist_out ? (size_t)n_win * (size_t)n_bins : 0;
-    if ((rc = reserve_scratch(ctx, (w_dev ? 0 : align_up(n_pos * 8)) + 4 * align_up((size_t)n_win * 8) +
-                                       (h_dev ? 0 : align_up(hist_elems * 4)))))
-        return rc;
-    Arena a(ctx);
-    int64_t* d_wps = w_dev ? wps_out : a.take<int64_t>(n_pos);
-    F.cov_out = count_out ? (c_dev ? count_out : a.take<int64_t>(n_win)) : nullptr;
-    F.hist_out = hist_out ? (h_dev ? hist_out : a.take<uint32_t>(hist_elems)) : nullptr;
-    F.over_out = hist_out ? (o_dev ? overflow_out : a.take<int64_t>(n_win)) : nullptr;
-    F.short_out = df ? (s_dev ? short_out : a.take<int64_t>(n_win)) : nullptr;
-    F.long_out = df ? (l_dev ? long_out : a.take<int64_t>(n_win)) : nullptr;
+    int64_t* d_wps = nullptr;
+    Scratch s(ctx);
+    s.out(&d_wps, wps_out, n_pos);
+    declare_feature_outputs(s, &F, n_win, hist_elems, hist_out != nullptr, count_out, hist_out, overflow_out, short_out, long_out);
+    if ((rc = s.reserve())) return rc;
     // every feature output is accumulated with atomics: start from zero
     if (F.cov_out) HIPCHK(ctx, hipMemsetAsync(F.cov_out, 0, (size_t)n_win * 8, ctx->stream));
     if (F.hist_out) {
@@ -466,20 +469,7 @@ int ftk_wps_window_features(ftk_ctx* ctx, int contig_id, int64_t start, int64_t 
     p.stop = stop;
     launch_wps_fused(ctx->stream, c->v, p, (n_pos + kWpsTile - 1) / kWpsTile, F, d_wps);
     HIPCHK(ctx, hipGetLastError());
-    bool host_out = false;
-    auto back = [&](void* dst, const void* src, size_t bytes, bool dev) -> hipError_t {
-        if (!dst || dev) return hipSuccess;
-        host_out = true;
-        return hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, ctx->stream);
-    };
-    HIPCHK(ctx, back(wps_out, d_wps, (size_t)n_pos * 8, w_dev));
-    HIPCHK(ctx, back(count_out, F.cov_out, (size_t)n_win * 8, c_dev));
-    HIPCHK(ctx, back(hist_out, F.hist_out, hist_elems * 4, h_dev));
-    HIPCHK(ctx, back(hist_out ? overflow_out : nullptr, F.over_out, (size_t)n_win * 8, o_dev));
-    HIPCHK(ctx, back(short_out, F.short_out, (size_t)n_win * 8, s_dev));
-    HIPCHK(ctx, back(long_out, F.long_out, (size_t)n_win * 8, l_dev));
-    if (host_out) HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    return FTK_OK;
+    return s.finish();
 }
 
 int ftk_wps_batch(ftk_ctx* ctx, const int32_t* contig_ids, const int64_t* iv_start, const int64_t* iv_stop,
@@ -490,7 +480,6 @@ int ftk_wps_batch(ftk_ctx* ctx, const int32_t* contig_ids, const int64_t* iv_sta
     if (n_iv == 0) return FTK_OK;
     if (!contig_ids || !iv_start || !iv_stop || !chrom_size || !out_offset || !wps_out)
         return fail(ctx, FTK_ERR_INVALID, "NULL argument");
-    const bool out_dev = is_device_ptr(wps_out);
     long long total_out = 0;
     std::vector<WpsItem> host;
     WpsParams p{};
@@ -526,18 +515,13 @@ int ftk_wps_batch(ftk_ctx* ctx, const int32_t* contig_ids, const int64_t* iv_sta
     void* d_items = nullptr;
     int rc = upload_batch_descriptors(ctx, 1, host.data(), host.size() * sizeof(WpsItem), &d_items);
     if (rc) return rc;
-    int64_t* d_out = wps_out;
-    if (!out_dev) {
-        if ((rc = reserve_scratch(ctx, align_up((size_t)total_out * 8)))) return rc;
-        d_out = (int64_t*)ctx->scratch;
-    }
+    int64_t* d_out = nullptr;
+    Scratch s(ctx);
+    s.out(&d_out, wps_out, (size_t)total_out);
+    if ((rc = s.reserve())) return rc;
     launch_wps_batch(ctx->stream, p, (const WpsItem*)d_items, (int)host.size(), tiles, d_out);
     HIPCHK(ctx, hipGetLastError());
-    if (!out_dev) {
-        HIPCHK(ctx, hipMemcpyAsync(wps_out, d_out, (size_t)total_out * 8, hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    }
-    return FTK_OK;
+    return s.finish();
 }
 
 int ftk_cleavage_intervals(ftk_ctx* ctx, int contig_id, const int64_t* iv_start, const int64_t* iv_stop, int64_t n_iv,
@@ -547,53 +531,15 @@ int ftk_cleavage_intervals(ftk_ctx* ctx, int contig_id, const int64_t* iv_start,
     ContigData* c;
     int rc = get_contig(ctx, contig_id, &c);
     if (rc) return rc;
-    if (n_iv < 0 || n_iv > INT32_MAX) return fail(ctx, FTK_ERR_INVALID, "n_iv out of range");
-    if (n_iv == 0) return FTK_OK;
-    if (!iv_start || !iv_stop || !out_offset || !prop_out) return fail(ctx, FTK_ERR_INVALID, "NULL argument");
-    if (is_device_ptr(iv_start) || is_device_ptr(iv_stop) || is_device_ptr(out_offset))
-        return fail(ctx, FTK_ERR_INVALID, "interval arrays must be host arrays");
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    CleaveParams p{};
-    p.min_len = min_len < 0 ? INT32_MIN : min_len;
-    p.max_len = max_len < 0 ? INT32_MAX : max_len;
-    p.mapq_min = mapq_min;
-    p.lmax = std::max(0, max_len < 0 ? c->max_len : std::min(max_len, c->max_len));
-    std::vector<int32_t> tile_iv, tile_k;
-    int64_t total_out = 0;
-    for (int64_t i = 0; i < n_iv; ++i) {
-        const int64_t len = iv_stop[i] - iv_start[i];
-        if (len <= 0) continue;
-        if (iv_start[i] < 0 || iv_stop[i] > (1LL << 31)) return fail(ctx, FTK_ERR_INVALID, "interval out of range");
-        if (out_offset[i] < 0) return fail(ctx, FTK_ERR_INVALID, "negative output offset");
-        total_out = std::max(total_out, out_offset[i] + len);
-        for (int64_t k = 0; k < (len + kWpsTile - 1) / kWpsTile; ++k) {
-            tile_iv.push_back((int32_t)i);
-            tile_k.push_back((int32_t)k);
-        }
-    }
-    const size_t n_tiles = tile_iv.size();
-    if (n_tiles == 0) return FTK_OK;
-    if (n_tiles > (size_t)INT32_MAX) return fail(ctx, FTK_ERR_INVALID, "too many tiles in one call");
-    const bool out_dev = is_device_ptr(prop_out);
-    size_t need = 3 * align_up(n_iv * 8) + 2 * align_up(n_tiles * 4) + (out_dev ? 0 : align_up(total_out * 8));
-    if ((rc = reserve_scratch(ctx, need))) return rc;
-    Arena a(ctx);
-    int64_t* d_s = a.take<int64_t>(n_iv);
-    int64_t* d_e = a.take<int64_t>(n_iv);
-    int64_t* d_o = a.take<int64_t>(n_iv);
-    int32_t* d_ti = a.take<int32_t>(n_tiles);
-    int32_t* d_tk = a.take<int32_t>(n_tiles);
-    double* d_out = out_dev ? prop_out : a.take<double>(total_out);
-    HIPCHK(ctx, hipMemcpyAsync(d_s, iv_start, n_iv * 8, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(d_e, iv_stop, n_iv * 8, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(d_o, out_offset, n_iv * 8, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(d_ti, tile_iv.data(), n_tiles * 4, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(d_tk, tile_k.data(), n_tiles * 4, hipMemcpyHostToDevice, ctx->stream));
-    launch_cleavage(ctx->stream, c->v, p, (int64_t)n_tiles, d_s, d_e, d_o, d_ti, d_tk, d_out);
+    Scratch s(ctx);
+    TilePlan tp;
+    double* d_out = nullptr;
+    if ((rc = plan_interval_tiles(ctx, s, iv_start, iv_stop, n_iv, out_offset, 0, "tiles", prop_out, &d_out, &tp))) return rc;
+    if (tp.n_tiles == 0) return FTK_OK;
+    launch_cleavage(ctx->stream, c->v, cleave_params(*c, min_len, max_len, mapq_min), tp.n_tiles, tp.d_s, tp.d_e, tp.d_o, tp.d_ti,
+                    tp.d_tk, d_out);
     HIPCHK(ctx, hipGetLastError());
-    if (!out_dev) HIPCHK(ctx, hipMemcpyAsync(prop_out, d_out, total_out * 8, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));  // the tile descriptor vectors are pageable staging
-    return FTK_OK;
+    return s.finish(/*must_sync=*/true);  // (the plan's tile vectors are pageable staging)
 }
 
 int ftk_cleavage(ftk_ctx* ctx, int contig_id, int64_t start, int64_t stop, int32_t min_len, int32_t max_len,
@@ -608,24 +554,17 @@ int ftk_cleavage(ftk_ctx* ctx, int contig_id, int64_t start, int64_t stop, int32
     HIPCHK(ctx, hipSetDevice(ctx->device));
     // ONE interval: its tiles are numbered by the grid (no descriptor arrays to build and upload - for a whole contig
     // 60 000 tiles, half a megabyte of pageable staging and a stream synchronisation per call)
-    CleaveParams p{};
+    CleaveParams p = cleave_params(*c, min_len, max_len, mapq_min);
     p.start = start;
     p.stop = stop;
-    p.min_len = min_len < 0 ? INT32_MIN : min_len;
-    p.max_len = max_len < 0 ? INT32_MAX : max_len;
-    p.mapq_min = mapq_min;
-    p.lmax = std::max(0, max_len < 0 ? c->max_len : std::min(max_len, c->max_len));
     const int64_t n_pos = stop - start, n_tiles = (n_pos + kWpsTile - 1) / kWpsTile;
-    const bool out_dev = is_device_ptr(prop_out);
-    if (!out_dev && (rc = reserve_scratch(ctx, align_up((size_t)n_pos * 8)))) return rc;
-    double* d_out = out_dev ? prop_out : (double*)ctx->scratch;
+    double* d_out = nullptr;
+    Scratch s(ctx);
+    s.out(&d_out, prop_out, n_pos);
+    if ((rc = s.reserve())) return rc;
     launch_cleavage(ctx->stream, c->v, p, n_tiles, nullptr, nullptr, nullptr, nullptr, nullptr, d_out);
     HIPCHK(ctx, hipGetLastError());
-    if (!out_dev) {
-        HIPCHK(ctx, hipMemcpyAsync(prop_out, d_out, (size_t)n_pos * 8, hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    }
-    return FTK_OK;
+    return s.finish();
 }
 
 int ftk_wps_adjust(ftk_ctx* ctx, const double* scores, const int64_t* offsets, int64_t n_iv, int32_t median_window,
@@ -664,22 +603,32 @@ int ftk_wps_adjust(ftk_ctx* ctx, const double* scores, const int64_t* offsets, i
     const int64_t tiles_ub = total_out / tile + n_iv, fast_ub = fast ? total_out / kAdjustFastTile + n_iv : 0;
     if (tiles_ub > INT32_MAX - 1024) return fail(ctx, FTK_ERR_INVALID, "too many tiles in one call");
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    const bool in_dev = is_device_ptr(scores), out_dev = is_device_ptr(out);
+    const bool in_dev = is_device_ptr(scores);
     const int half = sw / 2;
-    size_t need = align_up((size_t)tiles_ub * sizeof(AdjustTile)) + align_up((size_t)fast_ub * sizeof(AdjustTile)) + align_up((size_t)(n_iv + 2) * 4) +
-                  align_up((size_t)(n_iv + 1) * 8) + 2 * align_up((size_t)(n_iv + 1) * 4) +
-                  align_up(n_iv * 8) + align_up((size_t)sw * 8) +
-                  align_up((size_t)2 * half * sw * 8) + (in_dev ? 0 : align_up(total_in * 8)) +
-                  (out_dev ? 0 : align_up(total_out * 8)) + (sw ? align_up(total_out * 8) : 0);
-    int rc = reserve_scratch(ctx, need);
+    AdjustTile *d_tiles = nullptr, *d_fast = nullptr;
+    int *d_todo = nullptr, *d_pre0 = nullptr, *d_pre1 = nullptr;
+    int64_t* d_offs = nullptr;
+    double *d_sub = nullptr, *d_coef = nullptr, *d_edge = nullptr, *d_staged = nullptr, *d_out = nullptr, *d_adj = nullptr;
+    Scratch s(ctx);
+    s.tmp(&d_tiles, (size_t)tiles_ub);
+    if (fast) {
+        s.tmp(&d_fast, (size_t)fast_ub);
+        s.tmp(&d_todo, (size_t)n_iv + 2);
+    }
+    s.tmp(&d_offs, (size_t)n_iv + 1);
+    s.tmp(&d_pre0, (size_t)n_iv + 1);
+    s.tmp(&d_pre1, (size_t)n_iv + 1);
+    if (edge_sub) s.tmp(&d_sub, n_iv);
+    if (sw) {
+        s.tmp(&d_coef, sw);
+        s.tmp(&d_edge, (size_t)2 * half * sw);
+        s.tmp(&d_adj, total_out);
+    }
+    if (!in_dev) s.tmp(&d_staged, total_in);
+    s.out(&d_out, out, total_out);
+    int rc = s.reserve();
     if (rc) return rc;
-    Arena a(ctx);
-    AdjustTile* d_tiles = a.take<AdjustTile>((size_t)tiles_ub);
-    AdjustTile* d_fast = fast ? a.take<AdjustTile>((size_t)fast_ub) : nullptr;
-    int* d_todo = fast ? a.take<int>((size_t)n_iv + 2) : nullptr;
-    int64_t* d_offs = a.take<int64_t>((size_t)n_iv + 1);
-    int* d_pre0 = a.take<int>((size_t)n_iv + 1);
-    int* d_pre1 = a.take<int>((size_t)n_iv + 1);
+    if (!sw) d_adj = d_out;
     {
         const size_t bytes = (size_t)(n_iv + 1) * 8;
         if (ctx->param_stage_bytes < bytes) {
@@ -719,17 +668,11 @@ int ftk_wps_adjust(ftk_ctx* ctx, const double* scores, const int64_t* offsets, i
     if (!n_fast) { d_fast = nullptr; d_todo = nullptr; }
     launch_adjust_tile_fill(ctx->stream, d_offs, (int)n_iv, W, tile, n_fast ? kAdjustFastTile : 0, d_pre0, d_pre1, d_tiles,
                             (int)n_tiles, d_fast, (int)n_fast);
-    double* d_sub = edge_sub ? a.take<double>(n_iv) : nullptr;
-    double* d_coef = sw ? a.take<double>(sw) : nullptr;
-    double* d_edge = sw ? a.take<double>((size_t)2 * half * sw) : nullptr;
     const double* d_in = scores;
     if (!in_dev) {
-        double* b = a.take<double>(total_in);
-        HIPCHK(ctx, hipMemcpyAsync(b, scores, total_in * 8, hipMemcpyHostToDevice, ctx->stream));
-        d_in = b;
+        HIPCHK(ctx, hipMemcpyAsync(d_staged, scores, total_in * 8, hipMemcpyHostToDevice, ctx->stream));
+        d_in = d_staged;
     }
-    double* d_out = out_dev ? out : a.take<double>(total_out);
-    double* d_adj = sw ? a.take<double>(total_out) : d_out;
     if (d_sub) HIPCHK(ctx, hipMemcpyAsync(d_sub, edge_sub, n_iv * 8, hipMemcpyHostToDevice, ctx->stream));
     if (sw) {
         HIPCHK(ctx, hipMemcpyAsync(d_coef, savgol_coef, (size_t)sw * 8, hipMemcpyHostToDevice, ctx->stream));
@@ -741,7 +684,5 @@ int ftk_wps_adjust(ftk_ctx* ctx, const double* scores, const int64_t* offsets, i
                          (int)n_iv);
     if (sw) launch_savgol(ctx->stream, d_adj, d_tiles, (int)n_tiles, d_coef, d_edge, sw, d_out);
     HIPCHK(ctx, hipGetLastError());
-    if (!out_dev) HIPCHK(ctx, hipMemcpyAsync(out, d_out, total_out * 8, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));  // tiles / coefficient arrays are pageable staging
-    return FTK_OK;
+    return s.finish(/*must_sync=*/true);  // (the coefficient arrays are pageable staging)
 }

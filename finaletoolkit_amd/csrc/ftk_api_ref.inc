@@ -1,4 +1,4 @@
-// Part of ftk_api.hip's translation unit (#included there, in this order: perbase, ref, comm) - reference images (`ftk_ref_*`), `ftk_motif_counts`, `ftk_ref_gc_counts`, `ftk_bgzf_inflate_device` (still inside the extern "C" block opened in ftk_api.hip; this part closes it).
+// Part of ftk_api.hip's translation unit (#included there, in this order: perbase, ref, comm, export) - reference images (`ftk_ref_*`), `ftk_motif_counts`, `ftk_ref_gc_counts`, `ftk_bgzf_inflate_device` (still inside the extern "C" block opened in ftk_api.hip; this part closes it).
 
 
 namespace {
@@ -233,23 +233,19 @@ int ftk_ref_gc_counts(ftk_ctx* ctx, int ref_id, const int64_t* range_lo, const i
             if (range_lo[i] < 0 || range_hi[i] > limit)
                 return fail(ctx, FTK_ERR_INVALID, "range %lld outside the reference image", (long long)i);
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    const bool out_dev = is_device_ptr(gc_out);
-    int rc = reserve_scratch(ctx, 3 * align_up(n * 8));
+    int64_t *b_lo = nullptr, *b_hi = nullptr, *d_out = nullptr;
+    Scratch s(ctx);
+    s.tmp(&b_lo, n);
+    s.tmp(&b_hi, n);
+    s.out(&d_out, gc_out, n);
+    int rc = s.reserve();
     if (rc) return rc;
-    Arena a(ctx);
-    int64_t* b_lo = a.take<int64_t>(n);
-    int64_t* b_hi = a.take<int64_t>(n);
-    int64_t* d_out = out_dev ? gc_out : a.take<int64_t>(n);
     const int64_t *d_lo, *d_hi;
     if ((rc = stage_in(ctx, range_lo, n, b_lo, &d_lo))) return rc;
     if ((rc = stage_in(ctx, range_hi, n, b_hi, &d_hi))) return rc;
     launch_gc_count(ctx->stream, (const uint8_t*)r.d, r.bytes, r.kind, d_lo, d_hi, (int)n, d_out);
     HIPCHK(ctx, hipGetLastError());
-    if (!out_dev) {
-        HIPCHK(ctx, hipMemcpyAsync(gc_out, d_out, n * 8, hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    }
-    return FTK_OK;
+    return s.finish();
 }
 
 // ---- DEFLATE on the device (csrc/ftk_inflate.hip) -------------------------------------------------------
@@ -288,15 +284,18 @@ int ftk_bgzf_inflate_device(ftk_ctx* ctx, const uint8_t* file_bytes, int64_t n, 
     if ((int64_t)total > cap) return fail(ctx, FTK_ERR_INVALID, "output holds %lld bytes, %lld needed", (long long)cap, (long long)total);
     if (tab.empty() || total == 0) return FTK_OK;
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    int rc = reserve_scratch(ctx, align_up((size_t)n + 8) + align_up(tab.size() * sizeof(tab[0])) + align_up(tab.size() * 4) +
-                                      align_up((size_t)total + 8192) + 4096);
+    uint8_t *d_comp = nullptr, *d_out = nullptr;
+    ftk::InflateBlock* d_tab = nullptr;
+    ftk::InflateStatus* d_st = nullptr;
+    uint32_t* d_crc = nullptr;
+    Scratch s(ctx);  // (`out` is a host array that takes its bytes only after the checks below: temporaries throughout)
+    s.tmp(&d_comp, (size_t)n + 8);
+    s.tmp(&d_tab, tab.size());
+    s.tmp(&d_st, 1);
+    s.tmp(&d_crc, tab.size());
+    s.tmp(&d_out, (size_t)total + 8192 + 4096);  // (rounded up to a 4 KB bound below: at least 8 KB stay behind `total`)
+    int rc = s.reserve();
     if (rc) return rc;
-    Arena a(ctx);
-    uint8_t* d_comp = a.take<uint8_t>((size_t)n + 8);
-    ftk::InflateBlock* d_tab = a.take<ftk::InflateBlock>(tab.size());
-    ftk::InflateStatus* d_st = a.take<ftk::InflateStatus>(1);
-    uint32_t* d_crc = a.take<uint32_t>(tab.size());
-    uint8_t* d_out = a.take<uint8_t>((size_t)total + 4096 + 16);
     d_out = (uint8_t*)(((uintptr_t)d_out + 4095) & ~(uintptr_t)4095);
     // The kernel addresses its input by 32-BIT BIT POSITIONS from the pointer it is given: a launch takes blocks whose
     // compressed bytes lie within 2^28 bytes of its first one (the streams' pieces are 48-96 MB; an image of more than

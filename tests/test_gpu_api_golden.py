@@ -461,3 +461,169 @@ class TestDeviceGC:  # next row: DELFI per-bin GC counted on the device
                 got = ref.gc_counts(engine, "chrG", starts, stops)
                 assert np.array_equal(got, want), path
                 assert [ref.gc_count("chrG", int(a), int(b)) for a, b in zip(starts[:40], stops[:40])] == want[:40].tolist()
+
+
+class TestHostAndDeviceOutputs:
+    """Every C-ABI call that takes an output as a host OR a device pointer gives the same arrays both ways (and with
+    some outputs on each side): the library binds each output to the caller's device array or to its own scratch plus
+    a copy back, and the two must not differ in anything but where the numbers end up."""
+    SIZE = 1_000_000
+    BINS = (20, 640)
+    GAPS = (400_000, 450_000, [(0, 10_000), (990_000, 1_000_000)])
+
+    @pytest.fixture(scope="class")
+    def torch(self, engine):
+        import torch
+        from finaletoolkit_amd import synth
+        engine.load_contig("hd", *synth.synth_contig(self.SIZE, depth=20.0, seed=77))
+        yield torch
+        engine.release("hd")
+
+    @staticmethod
+    def _dev(torch, shape, dtype):
+        t = torch.full(shape, -5, dtype=dtype, device="cuda:0")
+        torch.cuda.synchronize()  # (torch fills on ITS stream, the engine launches on its own)
+        return t
+
+    def _feature_outputs(self, torch, n, where):
+        """coverage, hist, overflow, short, long as host arrays ('h') or device tensors ('d'), one letter each."""
+        shapes = (((n,), np.int64, torch.int64), ((n, self.BINS[1]), np.uint32, torch.int32), ((n,), np.int64, torch.int64),
+                  ((n,), np.int64, torch.int64), ((n,), np.int64, torch.int64))
+        return [np.full(s, 3, nd) if w == "h" else self._dev(torch, s, td) for (s, nd, td), w in zip(shapes, where)]
+
+    @staticmethod
+    def _host(outs):
+        return [o if isinstance(o, np.ndarray) else o.cpu().numpy().view(np.uint32 if o.dtype.itemsize == 4 else np.int64)
+                for o in outs]
+
+    def _windows(self):
+        from finaletoolkit_amd import synth
+        rng = np.random.default_rng(3)
+        ws, we = synth.tiling_windows(self.SIZE, 50_000)
+        bl_s = np.sort(rng.integers(0, self.SIZE - 5000, 80)).astype(np.int32)
+        return ws, we, bl_s, (bl_s + rng.integers(100, 4000, 80)).astype(np.int32)
+
+    @pytest.mark.parametrize("where", ["hhhhh", "ddddd", "hddhd", "dhhdh"])
+    def test_window_features(self, engine, torch, where):
+        import ctypes as C
+        from finaletoolkit_amd import _lib as L
+        ws, we, bl_s, bl_e = self._windows()
+        want = engine.window_features("hd", ws, we, hist=self.BINS,
+                                      delfi=dict(quality_threshold=30, bl_start=bl_s, bl_end=bl_e, gaps=self.GAPS))
+        f, g = engine._filter("hd", 30, None, None, "midpoint"), L.make_gaps(self.GAPS)
+        o = self._feature_outputs(torch, len(ws), where)
+        engine._check(engine.lib.ftk_window_features(
+            engine.ctx, engine.contig_id("hd"), L.ptr(ws), L.ptr(we), len(ws), C.byref(f), L.ptr(o[0]), self.BINS[0],
+            self.BINS[1], L.ptr(o[1]), L.ptr(o[2]), 30, L.ptr(bl_s), L.ptr(bl_e), len(bl_s), C.byref(g), L.ptr(o[3]), L.ptr(o[4])))
+        engine.sync()
+        for got, key in zip(self._host(o), ("coverage", "hist", "overflow", "short", "long")):
+            assert np.array_equal(got, want[key]), (key, where)
+
+    @pytest.mark.parametrize("where", ["hhhhh", "ddddd", "dhdhd"])
+    def test_window_features_batch(self, engine, torch, where):
+        ws, we, bl_s, bl_e = self._windows()
+        want = engine.window_features("hd", ws, we, hist=self.BINS,
+                                      delfi=dict(quality_threshold=30, bl_start=bl_s, bl_end=bl_e, gaps=self.GAPS))
+        batch = engine.feature_batch([dict(name="hd", starts=ws, stops=we, bl_start=bl_s, bl_end=bl_e, gaps=self.GAPS)])
+        o = self._feature_outputs(torch, len(ws), where)
+        engine.window_features_batch(batch, coverage=o[0], hist=o[1], hist_bins=self.BINS, overflow=o[2], short=o[3], long=o[4])
+        engine.sync()
+        for got, key in zip(self._host(o), ("coverage", "hist", "overflow", "short", "long")):
+            assert np.array_equal(got, want[key]), (key, where)
+
+    @pytest.mark.parametrize("where", ["hhhhhh", "dddddd", "hddhdh"])
+    def test_wps_window_features(self, engine, torch, where):
+        ws, we, bl_s, bl_e = self._windows()
+        want = engine.window_features("hd", ws, we, hist=self.BINS,
+                                      delfi=dict(quality_threshold=30, bl_start=bl_s, bl_end=bl_e, gaps=self.GAPS))
+        want_wps = engine.wps("hd", 0, self.SIZE, self.SIZE)
+        o = self._feature_outputs(torch, len(ws), where[1:])
+        w = np.full(self.SIZE, 3, np.int64) if where[0] == "h" else self._dev(torch, (self.SIZE,), torch.int64)
+        engine.wps_window_features("hd", self.SIZE, 0, 50_000, len(ws), wps_out=w, coverage=o[0], hist=o[1], hist_bins=self.BINS,
+                                   overflow=o[2], bl_start=bl_s, bl_end=bl_e, gaps=self.GAPS, short=o[3], long=o[4])
+        engine.sync()
+        assert np.array_equal(self._host([w])[0], want_wps), where
+        for got, key in zip(self._host(o), ("coverage", "hist", "overflow", "short", "long")):
+            assert np.array_equal(got, want[key]), (key, where)
+
+    def test_per_base_calls(self, engine, torch):
+        """ftk_wps, ftk_wps_intervals, ftk_wps_batch, ftk_cleavage, ftk_cleavage_intervals, ftk_wps_adjust."""
+        from finaletoolkit_amd import _lib as L
+        cid, size = engine.contig_id("hd"), self.SIZE
+        host = engine.wps("hd", 100_000, 160_000, size)
+        d = self._dev(torch, (60_000,), torch.int64)
+        engine.wps("hd", 100_000, 160_000, size, out=d)
+        engine.sync()
+        assert np.array_equal(d.cpu().numpy(), host)
+
+        s = np.arange(5_000, 900_000, 9_000, dtype=np.int64)
+        e = s + np.tile(np.array([300, 4096, 5000, 1], np.int64), len(s))[:len(s)]
+        host_iv, offs = engine.wps_intervals("hd", s, e, size)
+        starts = np.ascontiguousarray(offs[:-1])
+        d = self._dev(torch, (int(offs[-1]),), torch.int64)
+        engine._check(engine.lib.ftk_wps_intervals(engine.ctx, cid, L.ptr(s), L.ptr(e), len(s), L.ptr(starts), size, 120, 120,
+                                                   180, 30, L.ptr(d)))
+        assert np.array_equal(d.cpu().numpy(), host_iv)
+
+        names, sizes = ["hd"] * 8, [size] * 8
+        h = np.full(int(offs[8]), 3, np.int64)
+        d = self._dev(torch, (int(offs[8]),), torch.int64)
+        engine.wps_batch(names, s[:8], e[:8], sizes, starts[:8], h)
+        engine.wps_batch(names, s[:8], e[:8], sizes, starts[:8], d)
+        engine.sync()
+        assert np.array_equal(h, host_iv[:int(offs[8])]) and np.array_equal(d.cpu().numpy(), h)
+
+        host_c = engine.cleavage("hd", 300_000, 309_000)
+        d = self._dev(torch, (9_000,), torch.float64)
+        engine.cleavage("hd", 300_000, 309_000, out=d)
+        engine.sync()
+        assert host_c.any() and np.array_equal(d.cpu().numpy(), host_c)
+
+        host_ci, offs_c = engine.cleavage_intervals("hd", s, e)
+        d = self._dev(torch, (int(offs_c[-1]),), torch.float64)
+        engine._check(engine.lib.ftk_cleavage_intervals(engine.ctx, cid, L.ptr(s), L.ptr(e), len(s), L.ptr(starts), L.LEN_OPEN,
+                                                        L.LEN_OPEN, 30, L.ptr(d)))
+        assert host_ci.any() and np.array_equal(d.cpu().numpy(), host_ci)
+
+        raw = host.astype(np.float64)
+        runs = np.array([0, 25_000, 60_000], np.int64)
+        for kw in (dict(savgol=True), dict(savgol=False, mean=True)):
+            host_a = engine.wps_adjust(raw, runs, 1000, **kw)
+            d = self._dev(torch, (len(host_a),), torch.float64)
+            engine.wps_adjust(raw, runs, 1000, out=d, **kw)
+            assert np.array_equal(d.cpu().numpy(), host_a), kw
+
+    def test_ref_gc_counts(self, engine, torch):
+        from finaletoolkit_amd import _lib as L
+        rng = np.random.default_rng(11)
+        packed = rng.integers(0, 256, 50_000, dtype=np.uint8)
+        rid = engine.ref_upload(("hd", "2bit"), packed, 1)
+        lo = np.sort(rng.integers(0, 190_000, 300)).astype(np.int64)
+        hi = lo + rng.integers(1, 10_000, 300)
+        host = engine.ref_gc_counts(rid, lo, hi)
+        d = self._dev(torch, (300,), torch.int64)
+        engine._check(engine.lib.ftk_ref_gc_counts(engine.ctx, rid, L.ptr(lo), L.ptr(hi), 300, L.ptr(d)))
+        engine.sync()
+        assert host.any() and np.array_equal(d.cpu().numpy(), host)
+
+    def test_merged_launch_host_scores_take_the_narrow_wire(self, engine, torch):
+        """A host-output ftk_window_features_wps of 2^22 positions or more: the merged launch's scores sit at the base of
+        the library's scratch and cross the link as int16; the features come back through the ordinary copies.  Which
+        route the library takes is its own choice and is not observable here: with its defaults 440 equal host windows
+        take the block path, so the launch is merged, and depth-5 scores fit 16 bits; should it decline either (FTK_FEAT_BLOCK,
+        FTK_WPS_NARROW_WIRE, a changed heuristic) the same numbers must arrive through ftk_wps and the plain copy."""
+        from finaletoolkit_amd import synth
+        size = (1 << 22) + 12_345
+        engine.load_contig("hd_long", *synth.synth_contig(size, depth=5.0, seed=78))
+        ws, we = synth.tiling_windows(size, 10_000)
+        d = self._dev(torch, (size,), torch.int64)
+        engine.wps("hd_long", 0, size, size, out=d)
+        engine.sync()
+        for where in ("hh", "hd"):  # scores on the host; the coverage with them, or left on the device
+            w = np.full(size, -1, np.int64)
+            cov = self._feature_outputs(torch, len(ws), where[1])[0]
+            engine.window_features_wps("hd_long", ws, we, w, 0, size, size, coverage=cov)
+            engine.sync()
+            assert np.array_equal(w, d.cpu().numpy()), where
+            assert np.array_equal(self._host([cov])[0], engine.window_counts("hd_long", ws, we, 30)), where
+        engine.release("hd_long")
