@@ -449,3 +449,16 @@ def bam_expected(path):
         a = np.array([kept[j] for j in order], np.int64).reshape(-1, 6)
         want[c] = tuple(a[:, k] for k in range(6)) + (np.array(order, np.int64),)
     return want, [sum(v[0] for v in per.values()), sum(v[1] for v in per.values())], rows, per
+
+
+def first_difference(a, b):
+    """None when the byte strings are equal, else the first offset at which they differ (or the shorter one ends).
+    For asserting on long strings: ``assert a == b`` makes the test runner diff them, which takes minutes at megabytes."""
+    if a == b:
+        return None
+    n = min(len(a), len(b))
+    step = 1 << 16
+    for at in range(0, n, step):
+        if a[at:at + step] != b[at:at + step]:
+            return next(at + k for k in range(min(step, n - at)) if a[at + k] != b[at + k])
+    return n
