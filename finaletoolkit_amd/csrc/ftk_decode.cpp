@@ -1545,6 +1545,7 @@ void ftk_host_free(void* p) {
 }  // extern "C"
 
 #include "ftk_stream_core.inc"  // the streaming decoder
+#include "ftk_stream_sets.inc"  // what the device routes share: buffer sets, pools, the staging of a piece
 #include "ftk_stream_text.inc"  // text streams
 #include "ftk_stream_bam.inc"  // BAM streams
 #include "ftk_stream_api.inc"  // the C entry points of the streams and the caches (`ftk_fragstream_*`, `ftk_cache_trim`, `ftk_fragfile_index_contigs`)

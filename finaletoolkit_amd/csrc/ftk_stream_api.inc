@@ -1,4 +1,4 @@
-// Part of ftk_decode.cpp's translation unit (#included there, in this order: core, text, bam, api) - the C entry points of the streams and the caches (`ftk_fragstream_*`, `ftk_cache_trim`, `ftk_fragfile_index_contigs`).
+// Part of ftk_decode.cpp's translation unit (#included there, in this order: core, sets, text, bam, api) - the C entry points of the streams and the caches (`ftk_fragstream_*`, `ftk_cache_trim`, `ftk_fragfile_index_contigs`).
 
 extern "C" {
 
@@ -54,19 +54,8 @@ int ftk_fragfile_index_contigs(const char* path, char* names_out, int64_t cap, i
             memcpy(one.data(), head.data(), bs);
             if (inflate_all(one, 1, &text) == FTK_OK) {
                 const char* b = (const char*)text.data();
-                const char* e = b + text.size();
-                while (b < e) {
-                    const char* nl = (const char*)memchr(b, '\n', (size_t)(e - b));
-                    const char* le = nl ? nl : e;
-                    if (le > b && *b != '#') {
-                        int tabs = 0;
-                        for (const char* x = b; x < le; ++x) tabs += (*x == '\t');
-                        *is_bed6_out = (tabs + 1) > 5;
-                        break;
-                    }
-                    if (!nl) break;
-                    b = nl + 1;
-                }
+                bool six = false;
+                if (sniff_bed6(b, b + text.size(), true, &six)) *is_bed6_out = six;
             }
         }
     }

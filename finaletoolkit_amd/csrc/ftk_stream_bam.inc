@@ -1,4 +1,4 @@
-// Part of ftk_decode.cpp's translation unit (#included there, in this order: core, text, bam, api) - BAM streams: `run_bam` (host record walk over speculative stretches) and `run_bam_device` (device inflate + the record parser of ftk_bamparse.hip; the record rule itself: ftk_bamrule.h).
+// Part of ftk_decode.cpp's translation unit (#included there, in this order: core, sets, text, bam, api) - BAM streams: `run_bam` (host record walk over speculative stretches) and `run_bam_device` (device inflate + the record parser of ftk_bamparse.hip; the record rule itself: ftk_bamrule.h).
 
 bool ftk_fragstream::run_bam(RawBuf& buf, size_t n_first) {
     StageClock clk(this);
@@ -46,19 +46,7 @@ bool ftk_fragstream::run_bam(RawBuf& buf, size_t n_first) {
     DevSet sets[kSlots];
     if (dinf)
         for (auto& S : sets) S = devset_pool().take(device);
-    struct Cleanup {
-        DevSet* s;
-        int device;
-        hipStream_t pst;
-        FrontStreams<kSlots>* streams;
-        bool on;
-        ~Cleanup() {
-            if (!on) return;
-            streams->settle_and_give();
-            (void)hipStreamSynchronize(pst);
-            for (int k = 0; k < kSlots; ++k) devset_pool().give(device, s[k]);
-        }
-    } cleanup{sets, device, pstream, &streams, dinf};
+    RingCleanup<kSlots> cleanup{sets, device, pstream, &streams, dinf};
     // Every third piece of the look-ahead is inflated by the host threads instead (straight into its slot's
     // page-locked output, while the GPU works on the two in front of it): the chip turns a 64 KB block of BAM over
     // every 2.7 us = 24 GB/s of records, the 16 threads manage 11 GB/s, and between record walks they have nothing
@@ -69,13 +57,7 @@ bool ftk_fragstream::run_bam(RawBuf& buf, size_t n_first) {
     }();
     bool slot_on_host[kSlots] = {};
     std::future<int> host_job[kSlots];  // the host threads' inflate of a slot's piece (from the slot's own copy of the bytes)
-    struct JobGuard {  // no job outlives the buffers it works on
-        std::future<int>* j;
-        ~JobGuard() {
-            for (int k = 0; k < kSlots; ++k)
-                if (j[k].valid()) (void)j[k].get();
-        }
-    } job_guard{host_job};
+    JobGuard job_guard{host_job, kSlots};
     auto submit = [&](Piece& pc, int index) -> bool {  // index: the piece's number among the submitted ones
         const int slot = index % kSlots;
         DevSet& S = sets[slot];
@@ -85,43 +67,17 @@ bool ftk_fragstream::run_bam(RawBuf& buf, size_t n_first) {
         if (slot_on_host[slot]) {
             if (!S.ensure(kRoom + pc.total + 64) || !S.ensure_host_comp(pc.used + 64))
                 return fail(FTK_ERR_OOM, "out of page-locked memory for the BAM piece");
-            {
-                const size_t used = pc.used;
-                const int nt = std::max(1, std::min(n_threads, (int)(used >> 20) + 1));
-                const uint8_t* src = buf.data();
-                uint8_t* dst = S.h_comp;
-                parallel_run(nt, [&](int t) {
-                    const size_t a = used * (size_t)t / nt, b2 = used * (size_t)(t + 1) / nt;
-                    memcpy(dst + a, src + a, b2 - a);
-                });
-            }
+            stage_bytes(S.h_comp, buf.data(), pc.used, n_threads);
             // (the job owns its block list; the bytes stay in the slot until the piece has been walked)
-            host_job[slot] = std::async(std::launch::async, [blocks = pc.blocks, comp = (const uint8_t*)S.h_comp,
-                                                             out = S.h_text + kRoom, nt = std::max(1, n_threads - 2)] {
-                return blocks.empty() ? (int)FTK_OK : inflate_block_list(comp, blocks, nt, out, true, true);  // CRCs checked like the GPU's pieces
-            });
+            host_job[slot] = start_host_inflate(pc.blocks, S.h_comp, S.h_text + kRoom, n_threads, -1, pc.used, -1);
             pc.slot = slot;
             return true;
         }
         if (!S.ensure(kRoom + pc.total + 64) || !S.ensure_inflate(pc.used, pc.blocks.size()) || !S.ensure_host_comp(pc.used + 64))
             return fail(FTK_ERR_OOM, "out of page-locked / device memory for the BAM piece");
-        {
-            const size_t used = pc.used;
-            const int nt = std::max(1, std::min(n_threads, (int)(used >> 20) + 1));
-            const uint8_t* src = buf.data();
-            uint8_t* dst = S.h_comp;
-            parallel_run(nt, [&](int t) {
-                const size_t a = used * (size_t)t / nt, b2 = used * (size_t)(t + 1) / nt;
-                memcpy(dst + a, src + a, b2 - a);
-            });
-        }
-        for (size_t i = 0; i < pc.blocks.size(); ++i) {
-            const Block& bl = pc.blocks[i];
-            S.h_tab[i] = {(uint32_t)bl.in_off, (uint32_t)bl.in_len, (uint32_t)(kRoom + bl.out_off), (uint32_t)bl.out_len};
-            const uint8_t* tr = buf.data() + bl.in_off + bl.in_len;
-            S.want_crc[i] = (uint32_t)tr[0] | ((uint32_t)tr[1] << 8) | ((uint32_t)tr[2] << 16) | ((uint32_t)tr[3] << 24);
-        }
-        S.n_tab = pc.blocks.size();
+        stage_bytes(S.h_comp, buf.data(), pc.used, n_threads);
+        S.set_block_table(pc.blocks, buf.data(), kRoom);
+        // (not enqueue_front: this route copies the text BACK for the host's record walk and records S.done)
         bool ok = hipMemsetAsync(S.d_ist, 0, sizeof(ftk::InflateStatus), pstream) == hipSuccess &&
                   (pc.used == 0 || hipMemcpyAsync(S.d_comp, S.h_comp, pc.used, hipMemcpyHostToDevice, pstream) == hipSuccess) &&
                   (pc.blocks.empty() || hipMemcpyAsync(S.d_tab, S.h_tab, pc.blocks.size() * sizeof(ftk::InflateBlock),
@@ -152,9 +108,9 @@ bool ftk_fragstream::run_bam(RawBuf& buf, size_t n_first) {
             (void)hipGetLastError();
             return fail(FTK_ERR_HIP, "the device inflate failed");
         }
-        if (S.h_ist->n_bad) return fail(FTK_ERR_FORMAT, "BGZF inflate failed");
-        for (size_t i = 0; i < S.n_tab; ++i)
-            if (S.h_crc[i] != S.want_crc[i]) return fail(FTK_ERR_FORMAT, "BGZF block CRC mismatch (device inflate)");
+        const DevSet::Inflate verdict = S.inflate_verdict();
+        if (verdict == DevSet::Inflate::bad_block) return fail(FTK_ERR_FORMAT, "BGZF inflate failed");
+        if (verdict == DevSet::Inflate::crc_mismatch) return fail(FTK_ERR_FORMAT, "BGZF block CRC mismatch (device inflate)");
         return true;
     };
     auto list_blocks = [&](Piece& pc) -> bool {
@@ -402,32 +358,6 @@ bool ftk_fragstream::run_bam(RawBuf& buf, size_t n_first) {
     return true;
 }
 
-// Sorted, device-resident BAM contig -> the consumer (the counterpart of emit_device for text contigs).
-bool ftk_fragstream::emit_device_bam(Contig&& ct) {
-    DevColumns& d = *ct.dev;
-    if (hipEventCreateWithFlags(&d.ready, hipEventDisableTiming) != hipSuccess || hipEventRecord(d.ready, pstream) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(FTK_ERR_HIP, "cannot record the contig's ready event");
-    }
-    std::unique_ptr<ftk_fragtable> t(new ftk_fragtable());
-    t->bam = true;
-    ct.p.rows = d.rows;
-    ct.p.start = d.start;
-    ct.p.end = d.end;
-    ct.p.mapq = d.mapq;
-    ct.p.strand = d.strand;
-    ct.p.r1s = d.r1s;
-    ct.p.r1e = d.r1e;
-    ct.p.ord = d.ord;
-    t->contigs.push_back(std::move(ct));
-    std::unique_lock<std::mutex> lk(mu);
-    cv.wait(lk, [&] { return stop || ready.size() < max_queued; });
-    if (stop) return false;
-    ready.push_back(t.release());
-    cv.notify_all();
-    return true;
-}
-
 bool ftk_fragstream::run_bam_device(RawBuf& buf, size_t n_first) {
     StageClock clk(this);
     const int device = inflate_device;
@@ -454,19 +384,10 @@ bool ftk_fragstream::run_bam_device(RawBuf& buf, size_t n_first) {
     DevSet sets[kSlots];
     for (auto& S : sets) S = devset_pool().take(device);
     uint8_t* d_wanted = nullptr;
-    struct Cleanup {
-        DevSet* s;
-        int device;
-        hipStream_t pst;
-        FrontStreams<kSlots>* streams;
-        uint8_t** wanted;
-        ~Cleanup() {
-            streams->settle_and_give();
-            (void)hipStreamSynchronize(pst);
-            for (int k = 0; k < kSlots; ++k) devset_pool().give(device, s[k]);
-            if (*wanted) (void)hipFree(*wanted);
-        }
-    } cleanup{sets, device, pstream, &streams, &d_wanted};
+    AtExit free_wanted{[&] {
+        if (d_wanted) (void)hipFree(d_wanted);
+    }};
+    RingCleanup<kSlots> cleanup{sets, device, pstream, &streams};
 
     struct Piece {
         size_t n = 0, used = 0, total = 0;
@@ -494,19 +415,8 @@ bool ftk_fragstream::run_bam_device(RawBuf& buf, size_t n_first) {
     // 6th - the default of round 4 - 0.234-0.249, 4th 0.31-0.33)
     const int host_share = host_share_env >= 0 ? host_share_env : (n_threads >= 8 ? 16 : 0);
     std::future<int> host_job[kSlots];
-    struct JobGuard {  // no job outlives the buffers it works on
-        std::future<int>* j;
-        ~JobGuard() {
-            for (int k = 0; k < kSlots; ++k)
-                if (j[k].valid()) (void)j[k].get();
-        }
-    } job_guard{host_job};
-    // (a GPU piece's compressed bytes go up straight from the page-locked read buffer; fill() lets that buffer rest
-    // until the copy is done - see buf_in_flight)
-    struct RestGuard {
-        ftk_fragstream* s;
-        ~RestGuard() { s->drop_resting(); }
-    } rest_guard{this};
+    JobGuard job_guard{host_job, kSlots};
+    RestGuard rest_guard{this};
     double t_jobwait = 0, t_front = 0, t_header = 0;  // FTK_DECODE_TIMING: what "other" is made of
     auto tick = [] { return std::chrono::steady_clock::now(); };
     auto since = [](std::chrono::steady_clock::time_point t0) {
@@ -560,68 +470,21 @@ bool ftk_fragstream::run_bam_device(RawBuf& buf, size_t n_first) {
             !S.ensure_inflate(pc.used, pc.blocks.size()) || (!direct && !S.ensure_host_comp(pc.used + 64)) ||
             !S.ensure_bam(kRoom + pc.total + 64, stretch_bytes))
             return fail(FTK_ERR_OOM, "out of page-locked / device memory for the BAM piece");
-        if (!direct && !job_reads) {
-            const size_t used = pc.used;
-            const int nt = std::max(1, std::min(n_threads, (int)(used >> 20) + 1));
-            const uint8_t* src = buf.data();
-            uint8_t* dst = S.h_comp;
-            parallel_run(nt, [&](int t) {
-                const size_t a = used * (size_t)t / nt, b2 = used * (size_t)(t + 1) / nt;
-                memcpy(dst + a, src + a, b2 - a);
-            });
-        }
-        for (size_t i = 0; i < pc.blocks.size(); ++i) {
-            const Block& bl = pc.blocks[i];
-            S.h_tab[i] = {(uint32_t)bl.in_off, (uint32_t)bl.in_len, (uint32_t)(kRoom + bl.out_off), (uint32_t)bl.out_len};
-            const uint8_t* tr = buf.data() + bl.in_off + bl.in_len;
-            S.want_crc[i] = (uint32_t)tr[0] | ((uint32_t)tr[1] << 8) | ((uint32_t)tr[2] << 16) | ((uint32_t)tr[3] << 24);
-        }
-        S.n_tab = pc.blocks.size();
+        if (!direct && !job_reads) stage_bytes(S.h_comp, buf.data(), pc.used, n_threads);
+        S.set_block_table(pc.blocks, buf.data(), kRoom);
+        pc.slot = slot;
         if (pc.on_host) {
             // (the job owns its block list; compressed bytes and output are the slot's page-locked buffers)
-            host_job[slot] = std::async(std::launch::async, [blocks = pc.blocks, comp = S.h_comp, out = S.h_text + kRoom,
-                                                             nt = std::max(1, n_threads - 2), fd = fileno(fp), used = pc.used,
-                                                             off = pc.file_off, job_reads] {
-                if (job_reads) {  // its own copy of the compressed bytes, four pread threads
-                    std::atomic<int> bad{0};
-                    std::vector<std::thread> th;
-                    auto part = [&](int t) {
-                        size_t a = used * (size_t)t / 4;
-                        const size_t e = used * (size_t)(t + 1) / 4;
-                        while (a < e) {
-                            const ssize_t r = pread(fd, comp + a, e - a, (off_t)(off + (long long)a));
-                            if (r <= 0) { bad.store(1); return; }
-                            a += (size_t)r;
-                        }
-                    };
-                    for (int t = 1; t < 4; ++t) th.emplace_back(part, t);
-                    part(0);
-                    for (auto& t : th) t.join();
-                    if (bad.load()) return (int)FTK_ERR_IO;
-                }
-                return blocks.empty() ? (int)FTK_OK : inflate_block_list(comp, blocks, nt, out, true, true);  // CRCs checked
-            });
-            pc.slot = slot;
+            host_job[slot] = start_host_inflate(pc.blocks, S.h_comp, S.h_text + kRoom, n_threads, fileno(fp), pc.used,
+                                                job_reads ? pc.file_off : -1);
             return true;
         }
-        // (the compressed bytes go up at once - nothing of the slot's previous piece uses d_comp any more - and only
-        // the inflate, which overwrites the text the appends may still read, waits for the slot's release)
-        bool ok = (pc.used == 0 || hipMemcpyAsync(S.d_comp, direct ? buf.data() : S.h_comp, pc.used, hipMemcpyHostToDevice, st) == hipSuccess) &&
-                  (!direct || hipEventRecord(up_ev, st) == hipSuccess) &&
-                  (!S.freed_valid || hipStreamWaitEvent(st, S.freed, 0) == hipSuccess) &&
-                  hipMemsetAsync(S.d_ist, 0, sizeof(ftk::InflateStatus), st) == hipSuccess &&
-                  (pc.blocks.empty() || hipMemcpyAsync(S.d_tab, S.h_tab, pc.blocks.size() * sizeof(ftk::InflateBlock),
-                                                       hipMemcpyHostToDevice, st) == hipSuccess);
+        const bool ok = enqueue_front(st, S, direct ? buf.data() : S.h_comp, pc.used, pc.blocks.size(), up_ev, /*vector_matches=*/true, nullptr);
         if (direct) buf_in_flight = up_ev;  // (fill() parks the buffer behind it)
-        if (ok) {
-            ftk::inflate_launch(st, S.d_comp, S.d_tab, (int)pc.blocks.size(), S.d_text, S.d_ist, S.d_crc, /*vector_matches=*/true);
-            ok = hipGetLastError() == hipSuccess && hipEventRecord(S.front, st) == hipSuccess;
-        }
         if (!ok) {
             (void)hipGetLastError();
             return fail(FTK_ERR_HIP, "cannot launch the device inflate");
         }
-        pc.slot = slot;
         return true;
     };
     // back of a piece (the parse stream, piece after piece): the record chain behind the previous piece's
@@ -636,11 +499,7 @@ bool ftk_fragstream::run_bam_device(RawBuf& buf, size_t n_first) {
             t_jobwait += since(t0);
             if (jrc != FTK_OK)
                 return fail(FTK_ERR_FORMAT, "BGZF inflate failed or block CRC mismatch (host share of a device stream)");
-            const bool up = (!S.freed_valid || hipStreamWaitEvent(st, S.freed, 0) == hipSuccess) &&
-                            hipMemsetAsync(S.d_ist, 0, sizeof(ftk::InflateStatus), st) == hipSuccess &&
-                            (pc.total == 0 || hipMemcpyAsync(S.d_text + kRoom, S.h_text + kRoom, pc.total, hipMemcpyHostToDevice, st) == hipSuccess) &&
-                            hipEventRecord(S.front, st) == hipSuccess;
-            if (!up) {
+            if (!upload_host_piece(st, S, kRoom, pc.total, nullptr)) {
                 (void)hipGetLastError();
                 return fail(FTK_ERR_HIP, "cannot send a host-inflated piece to the device");
             }
@@ -841,7 +700,7 @@ bool ftk_fragstream::run_bam_device(RawBuf& buf, size_t n_first) {
             if (hipEventCreateWithFlags(&U.ready, hipEventDisableTiming) == hipSuccess) (void)hipEventRecord(U.ready, pstream);
             cur.dev = sorted;
             emitted_refs.insert(cur_ref);
-            if (!emit_device_bam(std::move(cur))) return false;
+            if (!emit_device(std::move(cur), true)) return false;
         }
         cur = Contig{};
         have_cur = false;
@@ -877,9 +736,9 @@ bool ftk_fragstream::run_bam_device(RawBuf& buf, size_t n_first) {
         }
         clk.lap(1);
         S.pending = false;
-        if (!pc.on_host && S.h_ist->n_bad) return fail(FTK_ERR_FORMAT, "BGZF inflate failed");
-        for (size_t i = 0; i < S.n_tab; ++i)
-            if (S.h_crc[i] != S.want_crc[i]) return fail(FTK_ERR_FORMAT, "BGZF block CRC mismatch (device inflate)");
+        const DevSet::Inflate verdict = S.inflate_verdict();  // (a host-inflated piece: a cleared status, no table)
+        if (verdict == DevSet::Inflate::bad_block) return fail(FTK_ERR_FORMAT, "BGZF inflate failed");
+        if (verdict == DevSet::Inflate::crc_mismatch) return fail(FTK_ERR_FORMAT, "BGZF block CRC mismatch (device inflate)");
         const ftk::BamSummary& B = *S.h_bsum;
         if (B.carry_overflow || !B.consistent || B.n_runs > (uint32_t)ftk::kBamMaxRuns || B.n_rows > S.max_lines) {
             if (clk.on)

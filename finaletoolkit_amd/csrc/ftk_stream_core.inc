@@ -1,4 +1,4 @@
-// Part of ftk_decode.cpp's translation unit (#included there, in this order: core, text, bam, api) - the streaming decoder: pieces of whole BGZF blocks, the tabix / BAI index reader, `struct ftk_fragstream` (reader, read-ahead, slot ring bookkeeping, hand-over of finished contigs), the producer thread.
+// Part of ftk_decode.cpp's translation unit (#included there, in this order: core, sets, text, bam, api) - the streaming decoder: pieces of whole BGZF blocks, the tabix / BAI index reader, `struct ftk_fragstream` (reader, read-ahead, slot ring bookkeeping, hand-over of finished contigs), the producer thread.
 
 // ---------------------------------------------------------------------------------------
 // Streaming decoder: one contig at a time, decoded ahead of the consumer
@@ -426,7 +426,7 @@ struct ftk_fragstream {
     int device = -1;
     int inflate_device = -1;  // BAM streams opened with a device: where run_bam inflates the pieces
     hipStream_t pstream = nullptr;
-    bool emit_device(Contig&& ct);
+    bool emit_device(Contig&& ct, bool bam_rows);  // (ftk_stream_sets.inc)
     bool run_text_device(RawBuf& first, size_t first_n);
     // A row / comment line longer than the device carry (kTextCarryMax) cannot be moved from piece to piece on the
     // device: run_text_device then asks for a second pass over the file with the inflate on the host threads (whose
@@ -464,12 +464,17 @@ struct ftk_fragstream {
                 sw.lap("packer: pack");
             }
             if (!c.p.base) { fail(FTK_ERR_OOM, "out of host memory"); packer_ok = 0; return; }
-            std::unique_lock<std::mutex> lk(mu);
-            cv.wait(lk, [&] { return stop || ready.size() < max_queued; });
-            if (stop) { packer_ok = 0; return; }
-            ready.push_back(t.release());
-            cv.notify_all();
+            if (!queue_table(std::move(t))) packer_ok = 0;
         });
+        return true;
+    }
+    // a finished table into the consumer's queue, when it has room; false: the stream is being closed
+    bool queue_table(std::unique_ptr<ftk_fragtable> t) {
+        std::unique_lock<std::mutex> lk(mu);
+        cv.wait(lk, [&] { return stop || ready.size() < max_queued; });
+        if (stop) return false;
+        ready.push_back(t.release());
+        cv.notify_all();
         return true;
     }
     bool flush() {  // wait for the last contig to be queued
@@ -490,7 +495,6 @@ struct ftk_fragstream {
     // header larger than a piece) makes the stream start over on the host path (run_bam), which skips the contigs
     // already handed out (emitted_refs).
     bool run_bam_device(RawBuf& first, size_t first_n);
-    bool emit_device_bam(Contig&& ct);
     std::set<int> emitted_refs;
     // pieces a whole-file read will come to (0 for an index-driven read of a contig or region: short, and its length is
     // not the file's)

@@ -81,8 +81,8 @@ print("ok", order, n_dev)
 """
 
 
-def _child(path, threads=3, contig=None, **env):
-    args = [sys.executable, "-c", _CHILD.format(root=ROOT), path, str(threads)] + ([contig] if contig else [])
+def _child(path, threads=3, contig=None, script=_CHILD, **env):
+    args = [sys.executable, "-c", script.format(root=ROOT), path, str(threads)] + ([contig] if contig else [])
     r = subprocess.run(args, env=dict(os.environ, **env), capture_output=True, text=True, timeout=600)
     assert r.returncode == 0 and r.stdout.startswith("ok"), r.stdout + r.stderr[-3000:]
     return r.stdout + r.stderr
@@ -185,6 +185,54 @@ def test_device_rows_with_odd_rows_crlf_and_no_final_newline(tmp_path, bed6):
             assert np.array_equal(got[c][1][k].astype(np.int64), a[:, k]), (c, k)
     m = re.search(r"(\d+) pieces parsed on the device, (\d+) by the host", r.stderr)
     assert m and int(m.group(1)) >= 3 and int(m.group(2)) >= 3, r.stderr[-600:]  # both paths were taken
+
+
+_SNIFF_CHILD = """
+import sys
+sys.path.insert(0, {root!r})
+from tests.test_gpu_device_parse import _stream_device, _whole, _same
+from tests.test_stream_decoder import _stream
+path = sys.argv[1]
+want = _whole(path)
+dev, order, n_dev = _stream_device(path, threads=int(sys.argv[2]))
+host, host_order, _ = _stream(path, threads=int(sys.argv[2]))
+assert want["__bed6__"] == 1 and dev["__bed6__"] == 1 and host["__bed6__"] == 1, (want["__bed6__"], dev["__bed6__"], host["__bed6__"])
+_same(dev, want)
+_same(host, want)
+_same(dev, host)
+assert order == host_order
+print("ok", (order, n_dev, {{k: [c.tolist() for c in dev[k][1]] for k in order}}))
+"""
+
+
+def test_bed6_is_sniffed_behind_comments_and_from_a_last_row_without_line_end(tmp_path):
+    """The "BED6 or not" decision is taken from the first data row.  A BED6 file of 200 rows on two contigs whose first
+    three lines are '#' comments and whose last row has no line end, and a file that is ONE BED6 row without any
+    newline (the row the sniff reads is unterminated: it counts because the file ends there): the device route, the
+    device route with the inflate on the host threads and the host stream hand out the same BED6 tables, equal to the
+    whole-file decoder's and to the rows written."""
+    rng = np.random.default_rng(31)
+    want, lines = {}, ["#first comment", "#chrom\tstart\tstop\tname\tmapq\tstrand", "# third\tcomment\twith\ttabs"]
+    for c, n in (("chr1", 120), ("chr2", 80)):
+        s = np.sort(rng.integers(0, 5_000_000, n))
+        e = s + rng.integers(30, 600, n)
+        q = rng.integers(0, 61, n)
+        st = rng.integers(0, 2, n)
+        want[c] = [s, e, q, st]
+        lines += ["%s\t%d\t%d\tfrag%d\t%d\t%s" % (c, s[i], e[i], i, q[i], "+" if st[i] else "-") for i in range(n)]
+    many = str(tmp_path / "bed6_comments.frag.gz")
+    bgzf.write_bgzf(many, "\n".join(lines).encode(), level=1)  # no newline after the last row
+    one = str(tmp_path / "bed6_one_row.frag.gz")
+    bgzf.write_bgzf(one, b"chrX\t100\t267\tonly\t42\t+", level=1)
+    want_one = {"chrX": [np.array([100]), np.array([267]), np.array([42]), np.array([1])]}
+    for path, rows in ((many, want), (one, want_one)):
+        for env in (dict(), dict(FTK_DEVICE_INFLATE="0")):
+            out = _child(path, script=_SNIFF_CHILD, FTK_STREAM_PIECE="65536", **env)
+            order, n_dev, got = eval(out.splitlines()[0][3:])
+            assert order == list(rows) and n_dev == len(order), out[:200]
+            for c in order:
+                for a, b in zip(got[c], rows[c]):
+                    assert a == b.tolist(), (path, env, c)
 
 
 def test_sources_opened_from_text_files_use_the_device_rows(tmp_path):
