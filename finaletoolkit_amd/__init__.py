@@ -50,7 +50,8 @@ _FLAT_BY_MODULE = {
              "EndMotifsIntervals", "breakpoint_motifs", "region_breakpoint_motifs", "interval_breakpoint_motifs",
              "BreakpointMotifFreqs", "BreakpointMotifsIntervals", "CoverageResult", "FragLengthStats"),
     "utils": ("frag_generator", "frag_array", "frags_in_region", "agg_bw", "get_intervals", "overlaps", "gen_kmers",
-              "chrom_sizes_to_dict", "chrom_sizes_to_list", "reverse_complement", "frag_export", "frag_filter"),
+              "chrom_sizes_to_dict", "chrom_sizes_to_list", "reverse_complement", "frag_export", "frag_filter",
+              "frag_depth", "frag_depth_track"),
     "genome": ("GenomeGaps", "ContigGaps", "ucsc_hg19_gap_bed", "b37_gap_bed", "ucsc_hg38_gap_bed"),
     "io": ("Fragment", "AlignmentWrapper"),
 }

@@ -59,6 +59,7 @@ EXPORTS = [
     "ftk_comm_recv", "ftk_comm_join", "ftk_comm_destroy",
     "ftk_frags_format_rows", "ftk_bgzf_deflate_device", "ftk_frags_write",
     "ftk_mask_lds_intervals", "ftk_frags_mask_keep", "ftk_frags_format_rows_masked", "ftk_frags_write_masked",
+    "ftk_depth", "ftk_depth_runs", "ftk_format_bedgraph_runs",
 ]
 
 
@@ -210,6 +211,7 @@ def load() -> C.CDLL:
     lib.ftk_format_wig_i64.argtypes = [vp, i64, C.c_int, pp, pi64]
     lib.ftk_format_bedgraph_i64.argtypes = [C.c_char_p, vp, vp, i64, vp, C.c_int, pp, pi64]
     lib.ftk_format_bedgraph_f64.argtypes = [C.c_char_p, vp, vp, i64, vp, C.c_int, pp, pi64]
+    lib.ftk_format_bedgraph_runs.argtypes = [C.c_char_p, vp, vp, vp, i64, C.c_int, pp, pi64]
     lib.ftk_buffer_free.argtypes = [vp]
     lib.ftk_buffer_free.restype = None
     lib.ftk_format_frag_rows.argtypes = [C.c_char_p, vp, vp, vp, vp, i64, C.c_int, C.c_int, pp, pi64]
@@ -321,6 +323,8 @@ def load() -> C.CDLL:
     lib.ftk_frags_mask_keep.argtypes = [vp, C.c_int, pmask, vp, pi64]
     lib.ftk_frags_format_rows_masked.argtypes = lib.ftk_frags_format_rows.argtypes + [pmask]
     lib.ftk_frags_write_masked.argtypes = lib.ftk_frags_write.argtypes + [pmask]
+    lib.ftk_depth.argtypes = [vp, C.c_int, i64, i64, i32, i32, i32, vp]
+    lib.ftk_depth_runs.argtypes = [vp, C.c_int, i64, i64, i32, i32, i32, C.c_int, pp, pp, pp, pi64]
     lib.ftk_comm_unique_id.argtypes = [C.c_char_p]
     lib.ftk_comm_create.argtypes = [vp, C.c_int, C.c_int, C.c_char_p, C.POINTER(vp)]
     lib.ftk_comm_size.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]

@@ -1231,3 +1231,4 @@ static int wps_params(ftk_ctx* ctx, const ContigData& c, int64_t chrom_size, int
 #include "ftk_api_ref.inc"
 #include "ftk_api_comm.inc"
 #include "ftk_api_export.inc"
+#include "ftk_api_depth.inc"

@@ -317,6 +317,27 @@ int ftk_format_bedgraph_f64(const char* contig, const int64_t* iv_start, const i
                            [](char* p, double v) { return put_f64(p, v); });
 }
 
+int ftk_format_bedgraph_runs(const char* contig, const int32_t* run_start, const int32_t* run_end, const int32_t* run_depth,
+                             int64_t n, int n_threads, char** out, int64_t* out_len) {
+    if (!contig || !out || !out_len || n < 0 || (n > 0 && (!run_start || !run_end || !run_depth)))
+        return wfail(FTK_ERR_INVALID, "bad arguments");
+    const size_t cl = strlen(contig);
+    return format_rows(n, cl + 3 * 12 + 4, n_threads, out, out_len, [=](int64_t a, int64_t b, char* p) {
+        for (int64_t i = a; i < b; ++i) {
+            memcpy(p, contig, cl);
+            p += cl;
+            *p++ = '\t';
+            p = put_i64(p, run_start[i]);
+            *p++ = '\t';
+            p = put_i64(p, run_end[i]);
+            *p++ = '\t';
+            p = put_i64(p, run_depth[i]);
+            *p++ = '\n';
+        }
+        return p;
+    });
+}
+
 void ftk_buffer_free(void* p) { free(p); }
 
 int ftk_file_write(const char* path, const char* data, int64_t n, int gzip_level, int n_threads, int append) {

@@ -690,6 +690,40 @@ class Engine:
                                               L.ptr(res)))
         return res
 
+    # -- per-base depth track (csrc/ftk_depth.hip) ------------------------------------
+    @staticmethod
+    def _depth_args(start, stop, min_length, max_length, quality_threshold):
+        f = L.make_filter(quality_threshold, min_length, max_length)
+        return int(start), int(stop), f.min_len, f.max_len, f.mapq_min
+
+    def depth(self, name: str, start: int, stop: int, quality_threshold=30, min_length=None, max_length=None, out=None):
+        """Kept fragments covering each base of ``[start, stop)`` of resident contig ``name`` (``ftk_depth``): int32,
+        one value per base; ``out``: an int32 host array or device tensor / address of ``stop - start`` elements."""
+        n = max(int(stop) - int(start), 0)
+        res = self.result_array(n, np.int32) if out is None else out
+        dst = res if n or out is not None else np.empty(1, np.int32)  # (an empty region still has its arguments checked)
+        self._check(self.lib.ftk_depth(self.ctx, self.contig_id(name),
+                                       *self._depth_args(start, stop, min_length, max_length, quality_threshold), L.ptr(dst)))
+        return res
+
+    def depth_runs(self, name: str, start: int, stop: int, quality_threshold=30, min_length=None, max_length=None,
+                   include_zero=False):
+        """``(run_start, run_end, run_depth)`` int32: the maximal intervals of constant depth inside ``[start, stop)``,
+        run-length encoded on the device (``ftk_depth_runs``); runs of depth 0 only with ``include_zero``."""
+        ptrs = [C.c_void_p(), C.c_void_p(), C.c_void_p()]
+        n = C.c_int64()
+        self._check(self.lib.ftk_depth_runs(self.ctx, self.contig_id(name),
+                                            *self._depth_args(start, stop, min_length, max_length, quality_threshold),
+                                            int(bool(include_zero)), *[C.byref(p) for p in ptrs], C.byref(n)))
+        cols = []
+        for p in ptrs:
+            try:
+                cols.append(np.frombuffer(C.string_at(p.value, n.value * 4), np.int32).copy() if n.value else np.zeros(0, np.int32))
+            finally:
+                if p.value:
+                    self.lib.ftk_buffer_free(p.value)
+        return tuple(cols)
+
     # -- WPS post-processing --------------------------------------------------------
     def wps_adjust(self, scores, offsets, median_window_size=1000, mean=False, edge_sub=None, savgol_window_size=21,
                    savgol_poly_deg=2, savgol=True, out=None):

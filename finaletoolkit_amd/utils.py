@@ -301,6 +301,114 @@ def frag_filter(input_file, output_file, whitelist_file=None, blacklist_file=Non
                    workers, verbose, whitelist, blacklist, intersect_policy)
 
 
+_DEPTH_PLAIN, _DEPTH_GZ = (".bedgraph", ".bg"), (".bedgraph.gz", ".bg.gz")
+
+
+def frag_depth(input_file, contig, start=None, stop=None, quality_threshold: int = 30, min_length=None, max_length=None,
+               workers=None) -> np.ndarray:
+    """Per-base depth of ``contig:[start, stop)``: an int32 array with, for every base, the number of fragments with
+    ``frag_start <= base < frag_stop`` that pass ``mapq >= quality_threshold`` and ``min_length <= length <=
+    max_length`` (``ftk_depth``).  ``start=None``: 0.  ``stop=None``: the contig length of the BAM header, or for a
+    fragment file (whose index holds no lengths) the largest fragment end.  With both bounds given, a fragment file
+    is read through its index for the interval alone (``FragSource.require_interval``); a BAM is decoded for the
+    whole contig, because its index finds fragments by their read1 and a fragment can cover a base of the interval
+    while its read1 lies outside it."""
+    contig = str(contig)
+    a = 0 if start is None else int(start)
+    if a < 0 or (stop is not None and int(stop) < a):
+        raise ValueError(f"invalid coordinates: start ({a}), stop ({stop})")
+    src = open_source(input_file, workers)
+    eng = get_engine()
+    if stop is None or src.is_bam:
+        key = src.require(contig)
+        b = int(stop) if stop is not None else (src.lengths.get(contig) or eng.info(key)[2])
+    else:
+        b = int(stop)
+        key = src.require_interval(contig, a, b)
+    return eng.depth(key, a, max(a, b), quality_threshold, min_length, max_length)
+
+
+def frag_depth_track(input_file, output_file, contig=None, quality_threshold: int = 30, min_length=None, max_length=None,
+                     include_zero: bool = False, workers=None, verbose=False) -> dict:
+    """Write the depth track of ``input_file`` (see ``frag_depth``) as bedGraph rows ``contig start end depth``, one
+    per maximal interval of constant depth, for every contig in the order of the file (``contig``: that one alone;
+    with ``include_zero`` the rows of a contig wait in host memory until every contig in front of it has been
+    written).  The intervals are built on the GPU (``ftk_depth_runs``), contig by contig as the input is decoded, and only they
+    come back to the host.  ``output_file`` ends in ``.bedgraph`` / ``.bg`` (text) or ``.bedgraph.gz`` / ``.bg.gz``
+    (gzip).  Intervals of depth 0 are left out (``genomecov -bg``) unless ``include_zero`` (``-bga``), which makes the
+    rows tile each contig.  A contig spans ``[0, length)`` with the length of the BAM header, or up to its largest
+    fragment end for a fragment file; one without kept fragments writes nothing, or one row of depth 0 with
+    ``include_zero`` when its length is known.  Returns ``n_runs`` (rows written), ``n_fragments`` (fragments that
+    pass the MAPQ / length rule), ``bases_covered`` (bases of depth > 0) and ``max_depth``."""
+    import os
+    import sys
+    import time
+
+    from . import writers
+    from .source import ContigFeed
+    output_file = os.fspath(output_file)
+    zipped = output_file.endswith(_DEPTH_GZ)
+    if not zipped and not output_file.endswith(_DEPTH_PLAIN):
+        raise ValueError("output_file should have .bedgraph, .bg, .bedgraph.gz or .bg.gz as suffix")
+    level = writers.GZIP_LEVEL if zipped else 0
+    t0 = time.time()
+    eng = get_engine()
+    feed = ContigFeed(input_file, workers, names=None if contig is None else [str(contig)])
+    out = dict(n_runs=0, n_fragments=0, bases_covered=0, max_depth=0)
+    state = dict(first=True, next=0)
+    pending = {}  # include_zero: rows of contigs that became resident ahead of an earlier contig of the file
+
+    def emit(text):
+        with text:
+            text.write(output_file, level, append=not state["first"], threads=workers or 0)
+        state["first"] = False
+
+    def flush(src, everything):
+        # Contigs with fragments become resident in file order; the ones a BAM header lists without a single
+        # fragment only once the file has been read.  Without include_zero those write nothing, so rows go out as
+        # they arrive; with it every contig of the header has a row, and rows wait for the contigs in front of them.
+        names = src.contigs if contig is None else [str(contig)]
+        while state["next"] < len(names) and (names[state["next"]] in pending or everything):
+            text = pending.pop(names[state["next"]], None)
+            if text is not None:
+                emit(text)
+            state["next"] += 1
+
+    try:
+        for src, c in feed:
+            key = src.key(c)
+            length = src.lengths.get(c)
+            rs, re_, rd = eng.depth_runs(key, 0, length or eng.info(key)[2], quality_threshold, min_length, max_length,
+                                         include_zero)
+            if not length and not rd.any():  # nothing kept and no length to span: no row
+                rs, re_, rd = rs[:0], re_[:0], rd[:0]
+            text = writers.bedgraph_runs(c, rs, re_, rd, workers or 0)
+            if include_zero:
+                pending[c] = text
+                flush(src, False)
+            else:
+                emit(text)
+            kept = int(eng.window_counts(key, [None], [None], quality_threshold, min_length, max_length)[0])
+            out["n_runs"] += len(rs)
+            out["n_fragments"] += kept
+            out["bases_covered"] += int((re_ - rs)[rd > 0].sum(dtype=np.int64))
+            out["max_depth"] = max(out["max_depth"], int(rd.max()) if len(rd) else 0)
+            if verbose:
+                sys.stderr.write(f"frag_depth_track: {c}: {kept} fragments, {len(rs)} runs\n")
+        src = feed.finish()
+        flush(src, True)
+    except BaseException:
+        feed.close()
+        raise
+    if contig is not None and str(contig) not in feed.seen:
+        src.require(str(contig))  # not in the file: the ValueError of every other command
+    if state["first"]:
+        writers.write_text(output_file, b"", level)
+    if verbose:
+        sys.stderr.write(f"frag_depth_track: {out['n_runs']} runs in {time.time() - t0:.3f} s\n")
+    return out
+
+
 def agg_bw(input_file, interval_file, output_file, median_window_size: int = 1, mean: bool = False,
            verbose: bool = False) -> np.ndarray:
     """Aggregate a bigWig signal across strand-oriented intervals (reference: ``utils/_agg_bw.py:18-146``):

@@ -124,6 +124,16 @@ def bedgraph_batches(contig: str, starts, values, offsets=None, max_values: int 
         k = j
 
 
+def bedgraph_runs(contig: str, run_start, run_end, run_depth, threads: int = 0) -> TextBuffer:
+    """``contig  start  end  depth`` per run of a depth track (``Engine.depth_runs``; int32 columns)."""
+    s_ = np.ascontiguousarray(run_start, dtype=np.int32)
+    e_ = np.ascontiguousarray(run_end, dtype=np.int32)
+    d_ = np.ascontiguousarray(run_depth, dtype=np.int32)
+    if not (s_.ndim == 1 and s_.shape == e_.shape == d_.shape):
+        raise ValueError("run columns differ in length")
+    return _call("ftk_format_bedgraph_runs", str(contig).encode(), L.ptr(s_), L.ptr(e_), L.ptr(d_), len(s_), int(threads))
+
+
 def write_text(path: str, data: bytes, gzip_level: int = 0, append: bool = False, threads: int = 0):
     """Plain or gzip-member write of a Python bytes object (headers and other small pieces)."""
     lib = L.load()

@@ -421,6 +421,24 @@ int ftk_cleavage_intervals(ftk_ctx* ctx, int contig_id, const int64_t* iv_start,
                            const int64_t* out_offset, int32_t min_len, int32_t max_len, int32_t mapq_min,
                            double* prop_out);
 
+/* ---- per-base depth track ----------------------------------------------------------
+ * depth(b) of a base b of [start, stop) = fragments of the contig with start <= b < end, mapq >= mapq_min and
+ * min_len <= end - start <= max_len (FTK_LEN_OPEN = no bound): what `genomecov -bg` / a coverage track holds.
+ * Fragments that reach beyond the region count on its bases only; zero-length fragments cover nothing.
+ *   ftk_depth        one int32 per base into depth_out (stop - start values; a host or a device array)
+ *   ftk_depth_runs   the run-length encoding, built on the device: the maximal intervals of constant depth inside
+ *                    [start, stop) as run_start[i], run_end[i], run_depth[i] - sorted, disjoint, two runs that touch
+ *                    differ in depth.  include_zero == 0 omits the runs of depth 0 (-bg); otherwise they are kept and
+ *                    the runs tile the region (-bga).  The three arrays are library-owned host memory
+ *                    (ftk_buffer_free each; NULL when *n_runs == 0).
+ * start == stop is valid (no values, no runs).  FTK_ERR_INVALID: a NULL argument, start < 0, stop < start,
+ * stop >= 2^30. */
+int ftk_depth(ftk_ctx* ctx, int contig_id, int64_t start, int64_t stop, int32_t min_len, int32_t max_len,
+              int32_t mapq_min, int32_t* depth_out);
+int ftk_depth_runs(ftk_ctx* ctx, int contig_id, int64_t start, int64_t stop, int32_t min_len, int32_t max_len,
+                   int32_t mapq_min, int include_zero, int32_t** run_start, int32_t** run_end, int32_t** run_depth,
+                   int64_t* n_runs);
+
 /* ---- next row: WPS post-processing (adjust_wps) ---------------------
  * frag/_adjust_wps.py:25-50,119-140 for n_iv score runs laid end to end in `scores`
  * (run i = scores[offsets[i] .. offsets[i+1]), offsets is a host array of n_iv + 1):
@@ -600,6 +618,7 @@ int ftk_frags_write_masked(ftk_ctx* ctx, int contig_id, const char* name, int32_
  *   ftk_format_bedgraph_i64  "<contig>\t<pos>\t<pos+1>\t<v>\n" per value of every run
  *   ftk_format_bedgraph_f64  the same for float64 values printed as Python's repr(float) prints them
  *                            (shortest round-trip digits; exponent form outside 1e-4 <= |v| < 1e16)
+ *   ftk_format_bedgraph_runs "<contig>\t<start>\t<end>\t<depth>\n" per run of a depth track (ftk_depth_runs)
  *   ftk_file_write           data -> path (truncate or append); gzip_level > 0 writes gzip members of 1 MB
  *                            of text each, compressed in parallel (a valid multi-member .gz: gzip.open,
  *                            zcat, bgzip -d read it as one stream)
@@ -619,6 +638,8 @@ int ftk_format_bedgraph_i64(const char* contig, const int64_t* iv_start, const i
                             const int64_t* values, int n_threads, char** out, int64_t* out_len);
 int ftk_format_bedgraph_f64(const char* contig, const int64_t* iv_start, const int64_t* offsets, int64_t n_iv,
                             const double* values, int n_threads, char** out, int64_t* out_len);
+int ftk_format_bedgraph_runs(const char* contig, const int32_t* run_start, const int32_t* run_end,
+                             const int32_t* run_depth, int64_t n, int n_threads, char** out, int64_t* out_len);
 void ftk_buffer_free(void* p);
 int ftk_file_write(const char* path, const char* data, int64_t n, int gzip_level, int n_threads, int append);
 int ftk_gzip_members(const char* data, int64_t n, int gzip_level, int n_threads, char** out, int64_t* out_len);

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Kernel micro-bench on one synthetic contig (GPU box): times ftk_wps / window features with
-HIP events, interleaved repetitions.  usage: tools/kbench.py [contig_len] [reps]"""
+HIP events, interleaved repetitions.  usage: tools/kbench.py [contig_len] [reps]
+KBENCH=depth: the depth track (per base and run-length encoded) beside the cleavage profile of the same contig."""
 import os
 import sys
 
@@ -145,6 +146,36 @@ if "cleave" in which:
     f = lambda: eng._check(eng.lib.ftk_cleavage_intervals(eng.ctx, eng.contig_id("c"), L.ptr(s0), L.ptr(s1), 1, L.ptr(so),
                                                           L.LEN_OPEN, L.LEN_OPEN, 20, L.ptr(cl)))
     timeit(f, "cleavage whole contig", 10 * n + 8 * size)
+if "depth" in which:
+    # Depth track of the whole contig: per base into a device buffer (the launch alone), and as runs (the whole call: two
+    # tile passes, the scan between them, the 8-byte run count read back and the three run columns copied to the host).
+    # Algorithmic bytes: 9 B (start, end, mapq) per candidate of every tile - the fragments the position index hands the
+    # tile, counted here from the sorted starts - plus 4 B per base, or 12 B per run.
+    import ctypes as C
+    from finaletoolkit_amd import _lib as L
+    lmax = eng.info("c")[1]
+    hs = s.cpu().numpy().astype(np.int64)
+    t0 = np.arange(0, size, 4096, dtype=np.int64)
+    t1 = np.minimum(t0 + 4096, size)
+    lo = np.searchsorted(hs, (np.maximum(t0 - lmax, 0) >> 9) << 9, side="left")
+    hi = np.searchsorted(hs, ((t1 >> 9) + 1) << 9, side="left")
+    cand = int((hi - lo).sum())
+    dp = torch.empty(size, dtype=torch.int32, device=dev)
+    cl = torch.empty(size, dtype=torch.float64, device=dev)
+    runs = {}
+
+    def run_form(include_zero):
+        runs[include_zero] = len(eng.depth_runs("c", 0, size, 30, None, None, include_zero)[0])
+    run_form(False)
+    run_form(True)
+    print(f"depth: {n} fragments, {len(t0)} tiles, {cand} candidates ({cand / n:.2f} per fragment), runs {runs[False]} "
+          f"(with zero runs {runs[True]})", flush=True)
+    for _ in range(2):  # twice, interleaved with the comparison: the spread between the two passes is the noise
+        timeit(lambda: eng.depth("c", 0, size, 30, out=dp), "depth per base", 9 * cand + 4 * size)
+        timeit(lambda: run_form(False), "depth runs (whole call)", 2 * 9 * cand + 12 * runs[False])
+        timeit(lambda: run_form(True), "depth runs, include_zero", 2 * 9 * cand + 12 * runs[True])
+        timeit(lambda: eng.cleavage("c", 0, size, None, None, 30, out=cl), "cleavage (comparison)", 10 * cand + 8 * size)
+    print("depth checksum", int(dp.sum(dtype=torch.int64).item()), "max", int(dp.max().item()))
 if "gc" in which:
     rng = np.random.default_rng(6)
     packed = rng.integers(0, 256, (size + 3) // 4, dtype=np.uint8)
