@@ -30,6 +30,7 @@ FTK_ERR_UNSORTED = -8
 OPEN_LO = -(2 ** 31)
 OPEN_HI = 2 ** 31 - 1
 LEN_OPEN = -1
+GC_MAX_LEN = 1000  # FTK_GC_MAX_LEN
 POLICY = {"midpoint": 0, "any": 1}
 POLICY_FETCH = 2  # no intersect test: the index query alone (AlignmentWrapper.fetch)
 FETCH_TABIX = 0
@@ -60,6 +61,7 @@ EXPORTS = [
     "ftk_frags_format_rows", "ftk_bgzf_deflate_device", "ftk_frags_write",
     "ftk_mask_lds_intervals", "ftk_frags_mask_keep", "ftk_frags_format_rows_masked", "ftk_frags_write_masked",
     "ftk_depth", "ftk_depth_runs", "ftk_format_bedgraph_runs",
+    "ftk_frag_gc", "ftk_frag_gc_table", "ftk_ref_gc_table",
 ]
 
 
@@ -325,6 +327,9 @@ def load() -> C.CDLL:
     lib.ftk_frags_write_masked.argtypes = lib.ftk_frags_write.argtypes + [pmask]
     lib.ftk_depth.argtypes = [vp, C.c_int, i64, i64, i32, i32, i32, vp]
     lib.ftk_depth_runs.argtypes = [vp, C.c_int, i64, i64, i32, i32, i32, C.c_int, pp, pp, pp, pi64]
+    lib.ftk_frag_gc.argtypes = [vp, C.c_int, C.c_int, i32, i32, i32, vp]
+    lib.ftk_frag_gc_table.argtypes = [vp, C.c_int, C.c_int, i32, i32, i32, vp, pi64]
+    lib.ftk_ref_gc_table.argtypes = [vp, C.c_int, i64, i64, i32, i32, i64, vp]
     lib.ftk_comm_unique_id.argtypes = [C.c_char_p]
     lib.ftk_comm_create.argtypes = [vp, C.c_int, C.c_int, C.c_char_p, C.POINTER(vp)]
     lib.ftk_comm_size.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]

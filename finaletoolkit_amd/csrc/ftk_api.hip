@@ -1232,3 +1232,4 @@ static int wps_params(ftk_ctx* ctx, const ContigData& c, int64_t chrom_size, int
 #include "ftk_api_comm.inc"
 #include "ftk_api_export.inc"
 #include "ftk_api_depth.inc"
+#include "ftk_api_gcbias.inc"

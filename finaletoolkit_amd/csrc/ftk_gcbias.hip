@@ -1,0 +1,239 @@
+// Fragment length x GC tables (ftk_frag_gc, ftk_frag_gc_table, ftk_ref_gc_table): what deepTools computeGCBias, Griffin
+// and GCparagon measure.  gc(a, b) = G + C bases of seq[a:b] of a reference image resident in HBM, undefined when the
+// span leaves the contig, is longer than FTK_GC_MAX_LEN or holds an N base (2bit: a base of an N block; FASTA text: any
+// byte but ACGTacgt).
+//
+// frag_gc_kernel       one thread per fragment, grid-stride over the contig's start-sorted columns.  2bit: the span's
+//                      32-bit words (first base in the high bits once byte-swapped; G and C are the codes with the low
+//                      bit set, gc_count_kernel), the first and the last one masked, __popc of the rest - 11-12 words
+//                      for 167 bases, which neighbouring fragments share through the caches - and a binary search of
+//                      the N blocks; FASTA text: the bytes through the line geometry, case folded.  The same body
+//                      writes the int16 per fragment and / or counts the table: rows len_lo .. lds_hi in a workgroup's
+//                      own LDS block of 32-bit cells (a workgroup sees fewer than 2^31 fragments: no cell can wrap),
+//                      the rows above with 64-bit global atomics, the LDS block flushed with one global atomic per
+//                      non-zero cell.
+// ref_gc_table_kernel  one workgroup per (tiles, chunk of rows).  Per tile of kGcRefTile positions it builds, in LDS, the
+//                      prefix sums x[i] over the tile and a halo of the chunk's longest length of one packed word per
+//                      base: is-GC in the low half, is-N (or behind the contig's end) in the high half.  A window
+//                      [p, p + L) is then ONE subtraction, x[p + L] - x[p]: high half 0 = defined, low half = g.  A
+//                      thread owns one length and walks the sampled positions of its group (threads of a wave: adjacent
+//                      lengths, so x[p] is a broadcast, x[p + L] consecutive words and the LDS atomics go to different
+//                      rows).  The chunk's rows stay in LDS over all tiles of the workgroup and are flushed once.
+//
+// Both tables are packed in LDS: the row of length L holds g = 0 .. L only (ftk_gcbias.h).  Counts are integers, so
+// neither table depends on the order of arrival.
+#include <algorithm>
+
+#include "ftk_gcbias.h"
+
+namespace ftk {
+
+namespace {
+
+// rows [lo[c], lo[c + 1]) of the expected table belong to chunk c
+struct GcRefChunks {
+    int n;
+    short lo[kGcRefMaxChunks + 1];
+};
+
+constexpr int kGcRefPer = (kGcRefTile + FTK_GC_MAX_LEN + kGcRefThreads) / kGcRefThreads;  // bases per thread and tile
+constexpr int kGcRefXLen = kGcRefPer * kGcRefThreads + 8;                                 // words of x[] (>= tile + halo + 1)
+static_assert(kGcRefPer * kGcRefThreads >= kGcRefTile + FTK_GC_MAX_LEN, "a tile and its halo fit the threads' shares");
+
+__device__ __forceinline__ int tri(int L) { return L * (L + 1) / 2; }
+
+// does [a, b) touch an N block?  (sorted, disjoint: the first block that ends behind a)
+__device__ __forceinline__ bool span_has_n(const GcImage& im, int a, int b) {
+    int lo = 0, hi = im.n_nblk;
+    while (lo < hi) {
+        const int m = (lo + hi) >> 1;
+        if (im.nblk_end[m] <= a) lo = m + 1; else hi = m;
+    }
+    return lo < im.n_nblk && im.nblk_start[lo] < b;
+}
+
+// 0 <= a < b <= chrom_len, b - a <= FTK_GC_MAX_LEN.  -1: the span holds an N.
+__device__ __forceinline__ int span_gc_2bit(const GcImage& im, int a, int b) {
+    if (im.n_nblk && span_has_n(im, a, b)) return -1;
+    const uint32_t* w32 = reinterpret_cast<const uint32_t*>(im.img);  // (the block is 256-byte aligned and 32 bytes longer than the image)
+    const int w0 = a >> 4, w1 = (b - 1) >> 4;
+    int g = 0;
+    for (int w = w0; w <= w1; ++w) {
+        const uint32_t v = __builtin_bswap32(w32[w]) & 0x55555555u;  // base j of the word: bit 30 - 2 j
+        const int j0 = max(a - 16 * w, 0), j1 = min(b - 16 * w, 16);
+        uint32_t m = 0xffffffffu >> (2 * j0);
+        if (j1 < 16) m &= ~(0xffffffffu >> (2 * j1));
+        g += __popc(v & m);
+    }
+    return g;
+}
+
+__device__ __forceinline__ int span_gc_text(const GcImage& im, int a, int b) {
+    const int row = a / im.line_bases;
+    int col = a - row * im.line_bases;
+    long long off = (long long)row * im.line_width + col;
+    int g = 0;
+    bool bad = false;
+    for (int j = a; j < b; ++j) {
+        const int ch = im.img[off] & 0xDF;  // fold case
+        const bool gc = (ch == 'G') | (ch == 'C');
+        g += gc;
+        bad |= !(gc | (ch == 'A') | (ch == 'T'));
+        ++off;
+        if (++col == im.line_bases) { col = 0; off += im.line_width - im.line_bases; }
+    }
+    return bad ? -1 : g;
+}
+
+__global__ __launch_bounds__(kGcFragThreads) void frag_gc_kernel(ContigView cv, GcImage im, FragGcParams p, int n_lds_cells,
+                                                                 int16_t* __restrict__ gc_out,
+                                                                 unsigned long long* __restrict__ table,
+                                                                 unsigned long long* __restrict__ n_skipped) {
+    extern __shared__ uint32_t gc_cells[];  // table != nullptr: rows len_lo .. lds_hi, packed
+    __shared__ unsigned int skipped_s;
+    const int tid = threadIdx.x;
+    const int tri0 = tri(p.len_lo), pitch = p.len_hi + 1;
+    if (table) {
+        for (int i = tid; i < n_lds_cells; i += kGcFragThreads) gc_cells[i] = 0;
+        if (tid == 0) skipped_s = 0;
+        __syncthreads();
+    }
+    for (long long i = (long long)blockIdx.x * kGcFragThreads + tid; i < cv.n; i += (long long)gridDim.x * kGcFragThreads) {
+        const int a = cv.start[i], b = cv.end[i], L = b - a;
+        int g = -1;
+        if ((int)cv.mapq[i] >= p.mapq_min && L >= p.min_len && L <= p.max_len) {
+            if (a >= 0 && b <= im.chrom_len) g = im.kind == FTK_REF_2BIT ? span_gc_2bit(im, a, b) : span_gc_text(im, a, b);
+            if (table) {
+                if (g < 0) atomicAdd(&skipped_s, 1u);
+                else if (L <= p.lds_hi) atomicAdd(&gc_cells[tri(L) - tri0 + g], 1u);
+                else atomicAdd(&table[(long long)(L - p.len_lo) * pitch + g], 1ull);
+            }
+        }
+        if (gc_out) gc_out[i] = (int16_t)g;
+    }
+    if (!table) return;
+    __syncthreads();
+    const int lane = tid & 63, wv = tid >> 6;
+    for (int L = p.len_lo + wv; L <= p.lds_hi; L += kGcFragThreads / 64) {
+        const int base = tri(L) - tri0;
+        for (int g = lane; g <= L; g += 64) {
+            const uint32_t v = gc_cells[base + g];
+            if (v) atomicAdd(&table[(long long)(L - p.len_lo) * pitch + g], (unsigned long long)v);
+        }
+    }
+    if (tid == 0 && skipped_s) atomicAdd(n_skipped, (unsigned long long)skipped_s);
+}
+
+// is-GC (bit 0) / is-N or outside the contig (bit 16) of position q >= 0
+__device__ __forceinline__ uint32_t base_flags(const GcImage& im, int q) {
+    if (q >= im.chrom_len) return 0x10000u;
+    if (im.kind == FTK_REF_2BIT) {
+        if (im.n_nblk && span_has_n(im, q, q + 1)) return 0x10000u;
+        return (im.img[q >> 2] >> (6 - 2 * (q & 3))) & 1u;  // T=0 C=1 A=2 G=3
+    }
+    const int row = q / im.line_bases;
+    const int ch = im.img[(long long)row * im.line_width + (q - row * im.line_bases)] & 0xDF;
+    if ((ch == 'G') | (ch == 'C')) return 1u;
+    return ((ch == 'A') | (ch == 'T')) ? 0u : 0x10000u;
+}
+
+__global__ __launch_bounds__(kGcRefThreads) void ref_gc_table_kernel(GcImage im, int pos_lo, int pos_hi, int len_lo, int len_hi,
+                                                                     long long stride, GcRefChunks ch, int n_tiles,
+                                                                     unsigned long long* __restrict__ table) {
+    extern __shared__ uint32_t gc_lds[];
+    __shared__ uint32_t wsum[kGcRefThreads / 64];
+    uint32_t* x = gc_lds;                  // x[i] = flags of the tile's first i bases, summed
+    uint32_t* cells = gc_lds + kGcRefXLen;  // the chunk's rows, packed
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int L0 = ch.lo[blockIdx.y], L1 = ch.lo[blockIdx.y + 1] - 1, R = L1 - L0 + 1;
+    const int tri0 = tri(L0), n_cells = tri(L1 + 1) - tri0;
+    for (int i = tid; i < n_cells; i += kGcRefThreads) cells[i] = 0;
+    const int groups = kGcRefThreads / R, pg = tid / R;  // thread = (group of positions, length)
+    const int L = L0 + (tid - pg * R), row = tri(L) - tri0;
+    const int nx = kGcRefTile + L1;  // bases a window of the tile can reach
+    for (int tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+        const int tile_lo = pos_lo + tile * kGcRefTile, tile_hi = min(tile_lo + kGcRefTile, pos_hi);
+        __syncthreads();  // the tile before: every reader of x[] and wsum[] has finished (first tile: cells[] is zero)
+        uint32_t f[kGcRefPer], sum = 0;
+#pragma unroll
+        for (int k = 0; k < kGcRefPer; ++k) {
+            const int i = tid * kGcRefPer + k;
+            if (i < nx) sum += base_flags(im, tile_lo + i);
+            f[k] = sum;
+        }
+        uint32_t incl = sum;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const uint32_t t = __shfl_up(incl, o, 64);
+            if (lane >= o) incl += t;
+        }
+        if (lane == 63) wsum[wv] = incl;
+        __syncthreads();
+        uint32_t excl = incl - sum;
+        for (int w = 0; w < wv; ++w) excl += wsum[w];
+        if (tid == 0) x[0] = 0;
+#pragma unroll
+        for (int k = 0; k < kGcRefPer; ++k) {
+            const int i = tid * kGcRefPer + k;
+            if (i < nx) x[i + 1] = excl + f[k];
+        }
+        __syncthreads();
+        if (pg < groups) {
+            const long long first = ((long long)tile_lo + stride - 1) / stride * stride;  // the tile's first sampled position
+            for (long long q = first + pg * stride; q < tile_hi; q += groups * stride) {
+                const int i = (int)(q - tile_lo);
+                const uint32_t d = x[i + L] - x[i];  // (the low half never borrows: both halves only grow)
+                if (!(d >> 16)) atomicAdd(&cells[row + d], 1u);
+            }
+        }
+    }
+    __syncthreads();
+    const int pitch = len_hi + 1;
+    for (int l = L0 + wv; l <= L1; l += kGcRefThreads / 64) {
+        const int base = tri(l) - tri0;
+        for (int g = lane; g <= l; g += 64) {
+            const uint32_t v = cells[base + g];
+            if (v) atomicAdd(&table[(long long)(l - len_lo) * pitch + g], (unsigned long long)v);
+        }
+    }
+}
+
+}  // namespace
+
+void launch_frag_gc(hipStream_t s, int n_cu, const ContigView& cv, const GcImage& im, FragGcParams p, int16_t* gc_out,
+                    unsigned long long* table, unsigned long long* n_skipped) {
+    if (cv.n <= 0) return;
+    int n_cells = 0;
+    if (table) {
+        p.lds_hi = p.len_lo;
+        while (p.lds_hi < p.len_hi && gc_tri(p.lds_hi + 2) - gc_tri(p.len_lo) <= kGcFragLdsCells) ++p.lds_hi;
+        n_cells = (int)(gc_tri(p.lds_hi + 1) - gc_tri(p.len_lo));
+    }
+    const size_t lds = (size_t)n_cells * 4;
+    const long long blocks = ((long long)cv.n + kGcFragThreads - 1) / kGcFragThreads;
+    const long long resident = (long long)n_cu * (2 * lds <= (size_t)(152 << 10) ? 2 : 1);  // workgroups a CU's LDS and 32 wave slots hold
+    hipLaunchKernelGGL(frag_gc_kernel, dim3((unsigned)std::min(blocks, resident)), dim3(kGcFragThreads), lds, s, cv, im, p, n_cells,
+                       gc_out, table, n_skipped);
+}
+
+void launch_ref_gc_table(hipStream_t s, int n_cu, const GcImage& im, int pos_lo, int pos_hi, int len_lo, int len_hi,
+                         long long stride, unsigned long long* table) {
+    if (pos_hi <= pos_lo) return;
+    GcRefChunks ch{};
+    long long most = 0;
+    for (int lo = len_lo; lo <= len_hi;) {  // rows are taken while the chunk fits its LDS block
+        int hi = lo;
+        while (hi < len_hi && gc_tri(hi + 2) - gc_tri(lo) <= kGcRefLdsCells) ++hi;
+        most = std::max(most, gc_tri(hi + 1) - gc_tri(lo));
+        ch.lo[ch.n++] = (short)lo;
+        lo = hi + 1;
+    }
+    ch.lo[ch.n] = (short)(len_hi + 1);
+    const int n_tiles = (int)(((long long)pos_hi - pos_lo + kGcRefTile - 1) / kGcRefTile);
+    const int gx = std::max(1, std::min(n_tiles, n_cu / ch.n));
+    const size_t lds = ((size_t)kGcRefXLen + (size_t)most) * 4;
+    hipLaunchKernelGGL(ref_gc_table_kernel, dim3((unsigned)gx, (unsigned)ch.n), dim3(kGcRefThreads), lds, s, im, pos_lo, pos_hi,
+                       len_lo, len_hi, stride, ch, n_tiles, table);
+}
+
+}  // namespace ftk

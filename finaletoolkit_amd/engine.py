@@ -724,6 +724,40 @@ class Engine:
                     self.lib.ftk_buffer_free(p.value)
         return tuple(cols)
 
+    # -- fragment length x GC tables (csrc/ftk_gcbias.hip) -------------------------------
+    def frag_gc(self, name: str, rid: int, quality_threshold=30, min_length=None, max_length=None, out=None) -> np.ndarray:
+        """G + C bases of every fragment of resident contig ``name`` in reference image ``rid`` (``ftk_frag_gc``;
+        the image needs its layout): int16, one value per fragment in resident order, ``-1`` for a fragment that
+        fails the MAPQ / length rule, leaves the contig, is longer than 1000 bases or spans an N.  ``out``: an int16
+        host array or device tensor of as many elements as the contig has fragments."""
+        n = self.info(name)[0]
+        res = self.result_array(n, np.int16) if out is None else out
+        dst = res if n or out is not None else np.empty(1, np.int16)
+        f = L.make_filter(quality_threshold, min_length, max_length)
+        self._check(self.lib.ftk_frag_gc(self.ctx, self.contig_id(name), int(rid), f.min_len, f.max_len, f.mapq_min, L.ptr(dst)))
+        return res
+
+    def frag_gc_table(self, name: str, rid: int, len_lo: int, len_hi: int, quality_threshold=30):
+        """``(table, n_skipped)``: the observed length x GC table of resident contig ``name`` (``ftk_frag_gc_table``) -
+        ``table[L - len_lo, g]`` = fragments of length ``L`` with ``g`` G + C bases, int64 of shape
+        ``(len_hi - len_lo + 1, len_hi + 1)`` - and the fragments of those lengths whose GC count is undefined."""
+        shape = (max(int(len_hi) - int(len_lo) + 1, 1), max(int(len_hi) + 1, 1))
+        table = np.empty(shape, np.int64)
+        skipped = C.c_int64()
+        self._check(self.lib.ftk_frag_gc_table(self.ctx, self.contig_id(name), int(rid), int(len_lo), int(len_hi),
+                                               int(quality_threshold), L.ptr(table), C.byref(skipped)))
+        return table, int(skipped.value)
+
+    def ref_gc_table(self, rid: int, pos_lo: int, pos_hi: int, len_lo: int, len_hi: int, stride: int = 1) -> np.ndarray:
+        """The expected length x GC table of reference image ``rid`` (``ftk_ref_gc_table``): ``table[L - len_lo, g]`` =
+        positions ``p`` of ``[pos_lo, pos_hi)`` with ``p % stride == 0`` whose window ``[p, p + L)`` lies inside the
+        contig, holds no N and has ``g`` G + C bases."""
+        shape = (max(int(len_hi) - int(len_lo) + 1, 1), max(int(len_hi) + 1, 1))
+        table = np.empty(shape, np.int64)
+        self._check(self.lib.ftk_ref_gc_table(self.ctx, int(rid), int(pos_lo), int(pos_hi), int(len_lo), int(len_hi),
+                                              int(stride), L.ptr(table)))
+        return table
+
     # -- WPS post-processing --------------------------------------------------------
     def wps_adjust(self, scores, offsets, median_window_size=1000, mean=False, edge_sub=None, savgol_window_size=21,
                    savgol_poly_deg=2, savgol=True, out=None):

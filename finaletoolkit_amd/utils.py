@@ -9,7 +9,7 @@ from __future__ import annotations
 
 import itertools
 from pathlib import Path
-from typing import Generator, Tuple
+from typing import Generator, NamedTuple, Tuple
 
 import numpy as np
 
@@ -407,6 +407,123 @@ def frag_depth_track(input_file, output_file, contig=None, quality_threshold: in
     if verbose:
         sys.stderr.write(f"frag_depth_track: {out['n_runs']} runs in {time.time() - t0:.3f} s\n")
     return out
+
+
+class GCBias(NamedTuple):
+    """Result of ``frag_gc_bias``: tables of shape ``(max_length - min_length + 1, max_length + 1)``, row
+    ``L - min_length``, column ``g`` = G + C bases."""
+    min_length: int
+    max_length: int
+    observed: np.ndarray   # int64: fragments of length L with g G + C bases
+    expected: np.ndarray   # int64: reference windows of length L with g G + C bases
+    bias: np.ndarray       # float64: (observed / observed.sum()) / (expected / expected.sum())
+    n_fragments: int       # observed.sum()
+    n_skipped: int         # fragments of those lengths without a GC count (off the contig, or over an N)
+    skipped_contigs: tuple  # contigs of the input the reference does not hold
+
+
+def gc_bias_ratio(observed, expected) -> np.ndarray:
+    """``(observed / observed.sum()) / (expected / expected.sum())`` in float64: NaN where ``expected == 0``, all NaN
+    when either table sums to 0."""
+    obs = np.asarray(observed, dtype=np.float64)
+    exp = np.asarray(expected, dtype=np.float64)
+    if obs.shape != exp.shape:
+        raise ValueError("observed and expected differ in shape")
+    bias = np.full(obs.shape, np.nan)
+    so, se = obs.sum(), exp.sum()
+    if so > 0 and se > 0:
+        ok = exp > 0
+        bias[ok] = (obs[ok] / so) / (exp[ok] / se)
+    return bias
+
+
+def _check_gc_bias_args(output_file, min_length, max_length, stride, expected):
+    from . import _lib as L
+    from . import writers
+    if int(min_length) < 1 or int(max_length) < int(min_length) or int(max_length) > L.GC_MAX_LEN:
+        raise ValueError(f"invalid lengths: 1 <= min_length ({min_length}) <= max_length ({max_length}) <= {L.GC_MAX_LEN} is required")
+    if int(stride) < 1:
+        raise ValueError(f"invalid stride ({stride}): at least 1")
+    shape = (int(max_length) - int(min_length) + 1, int(max_length) + 1)
+    if expected is not None:
+        expected = np.asarray(expected)
+        if expected.shape != shape or expected.dtype.kind not in "iu":
+            raise ValueError(f"expected should be an integer array of shape {shape}")
+        expected = expected.astype(np.int64)
+    if output_file is not None and not str(output_file).endswith(writers.GC_BIAS_SUFFIXES):
+        raise ValueError("output_file should have .tsv or .tsv.gz as suffix")
+    return shape, expected
+
+
+def frag_gc_bias(input_file, reference_file, output_file=None, contig=None, min_length: int = 100, max_length: int = 220,
+                 quality_threshold: int = 30, stride: int = 1, expected=None, workers=None, verbose=False) -> GCBias:
+    """Fragment length x GC bias of ``input_file`` against ``reference_file`` (``.2bit`` or FASTA), the measurement of
+    deepTools ``computeGCBias``, Griffin and GCparagon, counted on the GPU contig by contig as the input is decoded.
+
+    ``observed[L - min_length, g]``: fragments with ``mapq >= quality_threshold`` and length ``L`` in ``[min_length,
+    max_length]`` whose reference span ``[start, end)`` holds ``g`` G / C bases (either case).  ``expected[...]``:
+    positions ``p`` of every contig with ``p % stride == 0`` whose window ``[p, p + L)`` holds ``g``.  A span or window
+    that leaves the contig or holds an N (2bit: the record's N blocks; FASTA: any base but ACGTacgt) counts nowhere;
+    such fragments are ``n_skipped``.  ``bias = (observed / observed.sum()) / (expected / expected.sum())``, NaN where
+    ``expected == 0``.  ``max_length`` is at most 1000.
+
+    ``stride``: the expected table samples every ``stride``-th position; at ``stride=1`` it takes every window of
+    every contig (see ``docs/experiments.md`` for what that costs).  ``expected``: an int64 table of the right shape
+    to use instead, e.g. an earlier result's ``.expected`` - it depends only on the reference, the lengths and the
+    stride.  Contigs of the input that the reference lacks are skipped with one ``UserWarning`` and listed in
+    ``skipped_contigs``.  ``output_file`` (``.tsv`` / ``.tsv.gz``): ``length gc observed expected bias`` rows of the
+    cells with ``observed > 0 or expected > 0``.
+
+    Per-fragment weights: with the contig resident (``key = open_source(input_file).require(contig)``) and its image
+    ``rid = ReferenceGenome(reference_file).device_image(engine, contig)``, ``g = engine.frag_gc(key, rid,
+    quality_threshold, min_length, max_length)`` holds each fragment's G + C (``-1``: not counted) and, with ``L`` its
+    length, ``weight = 1 / bias[L - min_length, g]``."""
+    import os
+    import sys
+    import time
+    import warnings
+
+    from . import writers
+    from .reference import ReferenceGenome
+    from .source import ContigFeed
+    shape, given = _check_gc_bias_args(output_file, min_length, max_length, stride, expected)
+    lo, hi, stride = int(min_length), int(max_length), int(stride)
+    t0 = time.time()
+    eng = get_engine()
+    feed = ContigFeed(input_file, workers, names=None if contig is None else [str(contig)])
+    observed = np.zeros(shape, np.int64)
+    exp_sum = np.zeros(shape, np.int64)
+    n_skipped, missing = 0, []
+    try:
+        with ReferenceGenome(reference_file) as ref:
+            for src, c in feed:
+                if c not in ref.chroms:
+                    missing.append(c)
+                    continue
+                rid = ref.device_image(eng, c, with_layout=True)
+                table, skipped = eng.frag_gc_table(src.key(c), rid, lo, hi, quality_threshold)
+                observed += table
+                n_skipped += skipped
+                if given is None:
+                    exp_sum += eng.ref_gc_table(rid, 0, ref.chroms[c], lo, hi, stride)
+                if verbose:
+                    sys.stderr.write(f"frag_gc_bias: {c}: {int(table.sum())} fragments, {skipped} skipped\n")
+            src = feed.finish()
+    except BaseException:
+        feed.close()
+        raise
+    if contig is not None and str(contig) not in feed.seen:
+        src.require(str(contig))  # not in the file: the ValueError of every other command
+    if missing:
+        warnings.warn("frag_gc_bias: contigs not in the reference were skipped: " + ", ".join(missing), UserWarning)
+    if given is not None:
+        exp_sum = given
+    res = GCBias(lo, hi, observed, exp_sum, gc_bias_ratio(observed, exp_sum), int(observed.sum()), int(n_skipped), tuple(missing))
+    if output_file is not None:
+        writers.write_gc_bias_table(os.fspath(output_file), lo, res.observed, res.expected, res.bias)
+    if verbose:
+        sys.stderr.write(f"frag_gc_bias: {res.n_fragments} fragments in {time.time() - t0:.3f} s\n")
+    return res
 
 
 def agg_bw(input_file, interval_file, output_file, median_window_size: int = 1, mean: bool = False,

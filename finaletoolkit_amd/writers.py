@@ -256,3 +256,30 @@ def write_length_stats(output_file: str, results, short_reads: int, lines=None) 
         lines = [f"{r[0]}\t{r[1]}\t{r[2]}\t{r[3]}\t{r[4]}\t{r[5]}\t{r[6]}\t{r[7]}\t{r[8]}\t{r[9]}\t{r[10]}" for r in results]
     body = "\n".join(lines)
     _emit(output_file, head + body + "\n", (".bed", ".bedgraph"), (".bed.gz",), message)
+
+
+GC_BIAS_SUFFIXES = (".tsv", ".tsv.gz")
+
+
+def gc_bias_text(min_length: int, observed, expected, bias) -> str:
+    """The rows of a length x GC table (``utils.frag_gc_bias``): the header ``length gc observed expected bias``, then one
+    row per cell with ``observed > 0 or expected > 0``, lengths ascending, the bias as ``repr(float)`` (``nan`` where it
+    is undefined)."""
+    observed = np.asarray(observed)
+    expected = np.asarray(expected)
+    bias = np.asarray(bias, dtype=np.float64)
+    if not (observed.ndim == 2 and observed.shape == expected.shape == bias.shape):
+        raise ValueError("observed, expected and bias differ in shape")
+    rows = ["length\tgc\tobserved\texpected\tbias\n"]
+    ri, gi = np.nonzero((observed > 0) | (expected > 0))
+    rows += [f"{int(r) + int(min_length)}\t{int(g)}\t{int(observed[r, g])}\t{int(expected[r, g])}\t{float(bias[r, g])!r}\n"
+             for r, g in zip(ri, gi)]
+    return "".join(rows)
+
+
+def write_gc_bias_table(output_file: str, min_length: int, observed, expected, bias) -> None:
+    """``gc_bias_text`` to ``output_file``: ``.tsv`` as text, ``.tsv.gz`` as gzip."""
+    message = "output_file should have .tsv or .tsv.gz as suffix"
+    if not output_file.endswith(GC_BIAS_SUFFIXES):
+        raise ValueError(message)
+    _emit(output_file, gc_bias_text(min_length, observed, expected, bias), (".tsv",), (".tsv.gz",), message)

@@ -511,6 +511,33 @@ int ftk_motif_counts(ftk_ctx* ctx, int contig_id, int ref_id, const int32_t* w_s
                      uint32_t* counts_out /* [n_win][4^k] */, int64_t* nfrag_out /* [n_win] or NULL */,
                      int64_t* err_out /* [n_win] */);
 
+/* ---- fragment length x GC tables (csrc/ftk_gcbias.hip) ---------------------------------------------
+ * What deepTools computeGCBias, Griffin and GCparagon measure.  A base IS GC when it is G, C, g or c.  A base IS N
+ * when, in a 2bit image, it lies inside one of the record's N blocks, or, in a FASTA image, it is any sequence byte
+ * other than ACGTacgt (line terminators are not bases).  gc(a, b) = GC bases of seq[a:b]; it is UNDEFINED when
+ * a < 0, b > chrom_len, b - a > FTK_GC_MAX_LEN or seq[a:b] holds an N base.  The image needs its geometry
+ * (ftk_ref_set_layout).
+ *   ftk_frag_gc        gc_out[i] = gc(start, end) of fragment i of the resident contig (resident order), or -1 when
+ *                      the fragment is not kept (mapq < mapq_min, length outside [min_len, max_len], FTK_LEN_OPEN =
+ *                      no bound) or its gc is undefined (lengths above FTK_GC_MAX_LEN and below 1 included).
+ *   ftk_frag_gc_table  observed: table[L - len_lo][g] = fragments with mapq >= mapq_min, L = end - start in
+ *                      [len_lo, len_hi] and gc(start, end) == g; *n_skipped = fragments that pass the MAPQ and length
+ *                      rule with gc undefined.
+ *   ftk_ref_gc_table   expected: table[L - len_lo][g] = positions p of [pos_lo, pos_hi) with p % stride == 0 (on the
+ *                      absolute coordinate: the tables of two halves of a range sum to the table of the range) and
+ *                      gc(p, p + L) == g.  pos_hi > chrom_len is allowed: such windows are undefined.
+ * Tables are int64, row-major, (len_hi - len_lo + 1) x (len_hi + 1), host or device; every cell is written by the
+ * call.  An empty contig or range gives zeros.  FTK_ERR_INVALID: a NULL pointer, a reference without layout,
+ * len_lo < 1, len_hi < len_lo, len_hi > FTK_GC_MAX_LEN, stride < 1, pos_lo < 0, pos_hi < pos_lo, chrom_len >= 2^30;
+ * FTK_ERR_NO_CONTIG: an unknown contig or reference. */
+#define FTK_GC_MAX_LEN 1000
+int ftk_frag_gc(ftk_ctx* ctx, int contig_id, int ref_id, int32_t min_len, int32_t max_len, int32_t mapq_min,
+                int16_t* gc_out /* n fragments of the contig; host or device */);
+int ftk_frag_gc_table(ftk_ctx* ctx, int contig_id, int ref_id, int32_t len_lo, int32_t len_hi, int32_t mapq_min,
+                      int64_t* table_out, int64_t* n_skipped);
+int ftk_ref_gc_table(ftk_ctx* ctx, int ref_id, int64_t pos_lo, int64_t pos_hi, int32_t len_lo, int32_t len_hi,
+                     int64_t stride, int64_t* table_out);
+
 /* ---- BGZF inflate on the device -------------------------------------------------------------------
  * The streaming decoder's host threads spend most of a fragment file's decode in DEFLATE; BGZF blocks are
  * independent streams of at most 64 KB of data, decoded here one wavefront per block (csrc/ftk_inflate.hip).

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Kernel micro-bench on one synthetic contig (GPU box): times ftk_wps / window features with
 HIP events, interleaved repetitions.  usage: tools/kbench.py [contig_len] [reps]
-KBENCH=depth: the depth track (per base and run-length encoded) beside the cleavage profile of the same contig."""
+KBENCH=depth: the depth track (per base and run-length encoded) beside the cleavage profile of the same contig.
+KBENCH=gcbias: the observed and the expected length x GC table (lengths 100-220) against a synthetic 2bit image."""
 import os
 import sys
 
@@ -176,6 +177,23 @@ if "depth" in which:
         timeit(lambda: run_form(True), "depth runs, include_zero", 2 * 9 * cand + 12 * runs[True])
         timeit(lambda: eng.cleavage("c", 0, size, None, None, 30, out=cl), "cleavage (comparison)", 10 * cand + 8 * size)
     print("depth checksum", int(dp.sum(dtype=torch.int64).item()), "max", int(dp.max().item()))
+if "gcbias" in which:
+    # Length x GC tables, lengths 100-220, against a random 2bit image of the contig with one N block: the whole calls
+    # (table zeroed, kernel, 214 KB table copied to the host).  Byte floors: observed = 9 B of columns (start, end, mapq)
+    # per fragment + the image once; expected = the image once (at any stride: every base is part of some window).
+    rng = np.random.default_rng(7)
+    packed = rng.integers(0, 256, (size + 3) // 4, dtype=np.uint8)
+    ridb = eng.ref_upload(("kb", "gcbias2bit"), packed, 1)
+    eng.ref_set_layout(ridb, size, 0, 0, [10_000_000], [10_050_000])
+    img = (size + 3) // 4
+    obs, skipped = eng.frag_gc_table("c", ridb, 100, 220, 30)
+    print(f"gcbias: {n} fragments, {int(obs.sum())} counted, {skipped} skipped, image {img} B", flush=True)
+    for _ in range(2):  # twice: the spread between the two passes is the noise
+        timeit(lambda: eng.frag_gc_table("c", ridb, 100, 220, 30), "observed table 100-220", 9 * n + img)
+        timeit(lambda: eng.ref_gc_table(ridb, 0, size, 100, 220, 1), "expected table, stride 1", img)
+        timeit(lambda: eng.ref_gc_table(ridb, 0, size, 100, 220, 16), "expected table, stride 16", img)
+    exp = eng.ref_gc_table(ridb, 0, size, 100, 220, 16)
+    print("gcbias checksum", int(obs.sum()), int(exp.sum()), "(share of the byte floor = GB/s above / the HBM rate)")
 if "gc" in which:
     rng = np.random.default_rng(6)
     packed = rng.integers(0, 256, (size + 3) // 4, dtype=np.uint8)
