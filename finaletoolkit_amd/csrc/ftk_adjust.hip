@@ -18,6 +18,7 @@
 // down, one up - and the two middle order statistics follow by O(1) steps from where they were.  A tile whose values
 // are not integers within a range of 256 marks its interval, and the sort kernel redoes the marked intervals: same
 // result, bit for bit (the medians are the same input values).  10 000 x 5 kb runs at W = 1000: 7.2 ms -> 0.52 ms.
+#include "ftk_device.h"
 #include "ftk_kernels.h"
 
 #include <algorithm>
@@ -389,16 +390,6 @@ __global__ __launch_bounds__(kAdjThreads) void savgol_kernel(const double* __res
 }
 
 }  // namespace
-
-__device__ __forceinline__ int wave_incl_scan_dpp(int x) {  // inclusive prefix sum over the 64 lanes (row shifts + row broadcasts)
-    x += __builtin_amdgcn_update_dpp(0, x, 0x111, 0xf, 0xf, false);
-    x += __builtin_amdgcn_update_dpp(0, x, 0x112, 0xf, 0xf, false);
-    x += __builtin_amdgcn_update_dpp(0, x, 0x114, 0xf, 0xf, false);
-    x += __builtin_amdgcn_update_dpp(0, x, 0x118, 0xf, 0xf, false);
-    x += __builtin_amdgcn_update_dpp(0, x, 0x142, 0xa, 0xf, false);
-    x += __builtin_amdgcn_update_dpp(0, x, 0x143, 0xc, 0xf, false);
-    return x;
-}
 
 // ---- the tile lists, built where they are used --------------------------------------------------------------------
 // (one 32-byte descriptor per tile: 40 000 + 10 000 of them for 10 000 runs of 5 kb were 1.6 MB of pageable uploads

@@ -186,6 +186,23 @@ int get_contig(ftk_ctx* ctx, int contig_id, ContigData** out) {
     return FTK_OK;
 }
 
+// A loaded reference image with its layout, as the kernels read it.
+int open_ref_view(ftk_ctx* ctx, int ref_id, RefView* rv) {
+    auto it = ctx->refs.find(ref_id);
+    if (it == ctx->refs.end()) return fail(ctx, FTK_ERR_NO_CONTIG, "reference image %d is not loaded", ref_id);
+    const ftk_ctx::RefImage& ri = it->second;
+    if (ri.chrom_len < 0) return fail(ctx, FTK_ERR_INVALID, "reference image %d has no layout (ftk_ref_set_layout)", ref_id);
+    rv->img = (const uint8_t*)ri.d;
+    rv->nblk_start = ri.d_nblk;
+    rv->nblk_end = ri.d_nblk ? ri.d_nblk + ri.n_nblk : nullptr;
+    rv->n_nblk = ri.n_nblk;
+    rv->kind = ri.kind;
+    rv->chrom_len = (int)ri.chrom_len;
+    rv->line_bases = ri.line_bases > 0 ? ri.line_bases : 1;
+    rv->line_width = ri.line_width > 0 ? ri.line_width : 1;
+    return FTK_OK;
+}
+
 void free_contig(ContigData& c) {
     if (c.base) (void)hipFree(c.base);
     if (c.r1) (void)hipFree(c.r1);

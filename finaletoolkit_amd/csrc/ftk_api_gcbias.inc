@@ -5,21 +5,11 @@
 
 namespace {
 
-// The reference half of the three calls: the image with its layout as the kernels take it.
-int open_gc_image(ftk_ctx* ctx, int ref_id, GcImage* im) {
-    auto it = ctx->refs.find(ref_id);
-    if (it == ctx->refs.end()) return fail(ctx, FTK_ERR_NO_CONTIG, "reference image %d is not loaded", ref_id);
-    const ftk_ctx::RefImage& ri = it->second;
-    if (ri.chrom_len < 0) return fail(ctx, FTK_ERR_INVALID, "reference image %d has no layout (ftk_ref_set_layout)", ref_id);
-    if (ri.chrom_len >= (1LL << 30)) return fail(ctx, FTK_ERR_INVALID, "chrom_len %lld reaches 2^30, the coordinate bound", (long long)ri.chrom_len);
-    im->img = (const uint8_t*)ri.d;
-    im->nblk_start = ri.d_nblk;
-    im->nblk_end = ri.d_nblk ? ri.d_nblk + ri.n_nblk : nullptr;
-    im->n_nblk = ri.n_nblk;
-    im->kind = ri.kind;
-    im->chrom_len = (int)ri.chrom_len;
-    im->line_bases = ri.line_bases > 0 ? ri.line_bases : 1;
-    im->line_width = ri.line_width > 0 ? ri.line_width : 1;
+// The reference half of the three calls: the image's view, its coordinates below the bound the kernels' int arithmetic needs.
+int open_gc_view(ftk_ctx* ctx, int ref_id, RefView* im) {
+    const int rc = open_ref_view(ctx, ref_id, im);
+    if (rc) return rc;
+    if (im->chrom_len >= (1 << 30)) return fail(ctx, FTK_ERR_INVALID, "chrom_len %lld reaches 2^30, the coordinate bound", (long long)im->chrom_len);
     return FTK_OK;
 }
 
@@ -39,9 +29,9 @@ int ftk_frag_gc(ftk_ctx* ctx, int contig_id, int ref_id, int32_t min_len, int32_
     if (!ctx) return fail(nullptr, FTK_ERR_INVALID, "ctx is NULL");
     if (!gc_out) return fail(ctx, FTK_ERR_INVALID, "gc_out is NULL");
     ContigData* c;
-    GcImage im;
+    RefView im;
     int rc = get_contig(ctx, contig_id, &c);
-    if (rc || (rc = open_gc_image(ctx, ref_id, &im))) return rc;
+    if (rc || (rc = open_gc_view(ctx, ref_id, &im))) return rc;
     if (c->n == 0) return FTK_OK;
     // (gc is undefined below 1 and above FTK_GC_MAX_LEN bases: the open bounds close there)
     FragGcParams p{};
@@ -63,9 +53,9 @@ int ftk_frag_gc_table(ftk_ctx* ctx, int contig_id, int ref_id, int32_t len_lo, i
     if (!ctx) return fail(nullptr, FTK_ERR_INVALID, "ctx is NULL");
     if (!table_out || !n_skipped) return fail(ctx, FTK_ERR_INVALID, "NULL output pointer");
     ContigData* c;
-    GcImage im;
+    RefView im;
     int rc = get_contig(ctx, contig_id, &c);
-    if (rc || (rc = open_gc_image(ctx, ref_id, &im)) || (rc = check_gc_lengths(ctx, len_lo, len_hi))) return rc;
+    if (rc || (rc = open_gc_view(ctx, ref_id, &im)) || (rc = check_gc_lengths(ctx, len_lo, len_hi))) return rc;
     const size_t cells = gc_table_cells(len_lo, len_hi);
     HIPCHK(ctx, hipSetDevice(ctx->device));
     int64_t *d_table = nullptr, *d_skipped = nullptr;
@@ -85,8 +75,8 @@ int ftk_ref_gc_table(ftk_ctx* ctx, int ref_id, int64_t pos_lo, int64_t pos_hi, i
                      int64_t* table_out) {
     if (!ctx) return fail(nullptr, FTK_ERR_INVALID, "ctx is NULL");
     if (!table_out) return fail(ctx, FTK_ERR_INVALID, "table_out is NULL");
-    GcImage im;
-    int rc = open_gc_image(ctx, ref_id, &im);
+    RefView im;
+    int rc = open_gc_view(ctx, ref_id, &im);
     if (rc || (rc = check_gc_lengths(ctx, len_lo, len_hi))) return rc;
     if (stride < 1) return fail(ctx, FTK_ERR_INVALID, "stride %lld is below 1", (long long)stride);
     if (pos_lo < 0 || pos_hi < pos_lo) return fail(ctx, FTK_ERR_INVALID, "positions [%lld, %lld) are not a range", (long long)pos_lo, (long long)pos_hi);

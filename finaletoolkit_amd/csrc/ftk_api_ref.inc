@@ -183,22 +183,12 @@ int ftk_motif_counts(ftk_ctx* ctx, int contig_id, int ref_id, const int32_t* w_s
                      int64_t n_win, const ftk_motif* motif, int32_t mapq_min, int32_t fetch_mode,
                      uint32_t* counts_out, int64_t* nfrag_out, int64_t* err_out) {
     if (!ctx) return fail(nullptr, FTK_ERR_INVALID, "ctx is NULL");
-    auto it = ctx->refs.find(ref_id);
-    if (it == ctx->refs.end()) return fail(ctx, FTK_ERR_NO_CONTIG, "reference image %d is not loaded", ref_id);
-    const ftk_ctx::RefImage& ri = it->second;
-    if (ri.chrom_len < 0) return fail(ctx, FTK_ERR_INVALID, "reference image %d has no layout (ftk_ref_set_layout)", ref_id);
+    MotifParams mp{};
+    const int rc = open_ref_view(ctx, ref_id, &mp);
+    if (rc) return rc;
     if (!motif) return fail(ctx, FTK_ERR_INVALID, "motif is NULL");
     if (motif->k < 1 || motif->k > 7) return fail(ctx, FTK_ERR_INVALID, "k must be in [1, 7]");
     if (n_win > 0 && (!counts_out || !err_out)) return fail(ctx, FTK_ERR_INVALID, "NULL output pointer");
-    MotifParams mp{};
-    mp.img = (const uint8_t*)ri.d;
-    mp.nblk_start = ri.d_nblk;
-    mp.nblk_end = ri.d_nblk ? ri.d_nblk + ri.n_nblk : nullptr;
-    mp.n_nblk = ri.n_nblk;
-    mp.kind = ri.kind;
-    mp.chrom_len = (int)ri.chrom_len;
-    mp.line_bases = ri.line_bases > 0 ? ri.line_bases : 1;
-    mp.line_width = ri.line_width > 0 ? ri.line_width : 1;
     mp.k = motif->k;
     mp.f_off = motif->fwd_offset;
     mp.r_off = motif->rev_offset;

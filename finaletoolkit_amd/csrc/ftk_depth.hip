@@ -22,28 +22,11 @@
 #include <climits>
 
 #include "ftk_depth.h"
+#include "ftk_device.h"
 
 namespace ftk {
 
 namespace {
-
-// inclusive prefix sum over the 64 lanes (row shifts + row broadcasts), as in ftk_kernels.hip
-__device__ __forceinline__ int wave_incl_scan_dpp(int x) {
-    x += __builtin_amdgcn_update_dpp(0, x, 0x111, 0xf, 0xf, false);
-    x += __builtin_amdgcn_update_dpp(0, x, 0x112, 0xf, 0xf, false);
-    x += __builtin_amdgcn_update_dpp(0, x, 0x114, 0xf, 0xf, false);
-    x += __builtin_amdgcn_update_dpp(0, x, 0x118, 0xf, 0xf, false);
-    x += __builtin_amdgcn_update_dpp(0, x, 0x142, 0xa, 0xf, false);
-    x += __builtin_amdgcn_update_dpp(0, x, 0x143, 0xc, 0xf, false);
-    return x;
-}
-
-// first fragment of the index bin of position q (which = 0) or of the bin behind it (which = 1), as cleave_bound
-__device__ __forceinline__ int depth_bound(const ContigView& cv, long long q, int which) {
-    if (q <= 0) return 0;
-    const long long kb = q >> kBinShift;
-    return kb >= cv.n_bins ? cv.n : cv.bin_idx[kb + which];
-}
 
 enum { kPerBase = 0, kCount = 1, kWrite = 2 };
 
@@ -60,7 +43,7 @@ __global__ __launch_bounds__(256) void depth_kernel(ContigView cv, DepthParams p
     const long long t0 = p.start + k * T;
     const int len_t = (int)(min(t0 + (long long)T, p.stop) - t0);
     // candidates: start < t0 + len_t, end >= t0 (a fragment that ends exactly at t0 lowers the depth there)
-    const int lo = depth_bound(cv, t0 - (long long)p.lmax, 0), hi = depth_bound(cv, t0 + len_t, 1);
+    const int lo = index_bound(cv, t0 - (long long)p.lmax, 0), hi = index_bound(cv, t0 + len_t, 1);
     int4* dd4 = reinterpret_cast<int4*>(dd);
 #pragma unroll
     for (int j = 0; j < NP; ++j) dd4[j * 256 + tid] = make_int4(0, 0, 0, 0);

@@ -1,0 +1,58 @@
+// Device-only primitives that more than one kernel file uses (included by .hip files only): the wave scan and the
+// position-index bound of the per-base tiles, and the reads of a reference image through
+// its RefView.  A new kernel file takes these from here.
+#pragma once
+
+#include "ftk_internal.h"
+
+namespace ftk {
+
+// inclusive prefix sum over the 64 lanes of a wave on DPP (row_shr 1/2/4/8 inside rows of 16, then row_bcast:15 /
+// row_bcast:31 across rows): no LDS traffic, where six dependent `__shfl_up` are six LDS permutes
+__device__ __forceinline__ int wave_incl_scan_dpp(int x) {
+    x += __builtin_amdgcn_update_dpp(0, x, 0x111, 0xf, 0xf, false);
+    x += __builtin_amdgcn_update_dpp(0, x, 0x112, 0xf, 0xf, false);
+    x += __builtin_amdgcn_update_dpp(0, x, 0x114, 0xf, 0xf, false);
+    x += __builtin_amdgcn_update_dpp(0, x, 0x118, 0xf, 0xf, false);
+    x += __builtin_amdgcn_update_dpp(0, x, 0x142, 0xa, 0xf, false);
+    x += __builtin_amdgcn_update_dpp(0, x, 0x143, 0xc, 0xf, false);
+    return x;
+}
+
+// first fragment of the position-index bin of q (which = 0) or of the bin behind it (which = 1): the conservative
+// candidate bounds of a tile, "start >= q" below and "start < q" above
+__device__ __forceinline__ int index_bound(const ContigView& cv, long long q, int which) {
+    if (q <= 0) return 0;
+    const long long kb = q >> kBinShift;
+    return kb >= cv.n_bins ? cv.n : cv.bin_idx[kb + which];
+}
+
+// ---- a reference image through its RefView ----------------------------------------------------------------------
+// does [a, b) touch one of the N blocks [lo, hi) of n_nblk?  (sorted, disjoint: the first block that ends behind a)
+__device__ __forceinline__ bool n_block_search(const int32_t* nblk_start, const int32_t* nblk_end, int n_nblk, int a, int b,
+                                               int lo, int hi) {
+    while (lo < hi) {
+        const int m = (lo + hi) >> 1;
+        if (nblk_end[m] <= a) lo = m + 1; else hi = m;
+    }
+    return lo < n_nblk && nblk_start[lo] < b;
+}
+__device__ __forceinline__ bool ref_has_n(const RefView& rv, int a, int b) {
+    return n_block_search(rv.nblk_start, rv.nblk_end, rv.n_nblk, a, b, 0, rv.n_nblk);
+}
+
+// FASTA text: the byte offset of base p and its column in the line; ref_text_next steps both to base p + 1
+__device__ __forceinline__ long long ref_text_offset(const RefView& rv, int p, int& col) {
+    const int row = p / rv.line_bases;
+    col = p - row * rv.line_bases;
+    return (long long)row * rv.line_width + col;
+}
+__device__ __forceinline__ void ref_text_next(const RefView& rv, long long& off, int& col) {
+    ++off;
+    if (++col == rv.line_bases) { col = 0; off += rv.line_width - rv.line_bases; }
+}
+
+// 2bit: the code of base p (T=0 C=1 A=2 G=3; G and C have the low bit set) out of the byte that holds it, img[p >> 2]
+__device__ __forceinline__ uint32_t twobit_code(uint32_t byte, int p) { return (byte >> (6 - 2 * (p & 3))) & 3u; }
+
+}  // namespace ftk

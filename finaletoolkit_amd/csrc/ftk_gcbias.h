@@ -16,17 +16,6 @@ constexpr int kGcRefMaxChunks = 64;
 
 inline long long gc_tri(long long L) { return L * (L + 1) / 2; }
 
-// One contig's reference image and its geometry (device pointers; ftk_ref_set_layout).
-struct GcImage {
-    const uint8_t* img;
-    const int32_t* nblk_start;  // 2bit: N blocks, sorted, disjoint
-    const int32_t* nblk_end;
-    int n_nblk;
-    int kind;  // FTK_REF_*
-    int chrom_len;
-    int line_bases, line_width;  // FASTA text geometry (>= 1)
-};
-
 struct FragGcParams {
     int min_len, max_len, mapq_min;  // the kept fragments (closed bounds, 1 <= min_len, max_len <= FTK_GC_MAX_LEN)
     int len_lo, len_hi;              // table rows (table != nullptr: equal to min_len, max_len)
@@ -35,11 +24,11 @@ struct FragGcParams {
 
 // gc_out (may be NULL): gc per fragment or -1.  table (may be NULL): (len_hi - len_lo + 1) x (len_hi + 1) int64 cells
 // the launch ADDS to, *n_skipped likewise (both zeroed by the caller).
-void launch_frag_gc(hipStream_t s, int n_cu, const ContigView& cv, const GcImage& im, FragGcParams p, int16_t* gc_out,
+void launch_frag_gc(hipStream_t s, int n_cu, const ContigView& cv, const RefView& im, FragGcParams p, int16_t* gc_out,
                     unsigned long long* table, unsigned long long* n_skipped);
 // table: as above, zeroed by the caller; positions p of [pos_lo, pos_hi) with p % stride == 0.
 // 0 <= pos_lo < pos_hi <= im.chrom_len.
-void launch_ref_gc_table(hipStream_t s, int n_cu, const GcImage& im, int pos_lo, int pos_hi, int len_lo, int len_hi,
+void launch_ref_gc_table(hipStream_t s, int n_cu, const RefView& im, int pos_lo, int pos_hi, int len_lo, int len_hi,
                          long long stride, unsigned long long* table);
 
 }  // namespace ftk

@@ -5,7 +5,7 @@
 //
 // frag_gc_kernel       one thread per fragment, grid-stride over the contig's start-sorted columns.  2bit: the span's
 //                      32-bit words (first base in the high bits once byte-swapped; G and C are the codes with the low
-//                      bit set, gc_count_kernel), the first and the last one masked, __popc of the rest - 11-12 words
+//                      bit set, twobit_code), the first and the last one masked, __popc of the rest - 11-12 words
 //                      for 167 bases, which neighbouring fragments share through the caches - and a binary search of
 //                      the N blocks; FASTA text: the bytes through the line geometry, case folded.  The same body
 //                      writes the int16 per fragment and / or counts the table: rows len_lo .. lds_hi in a workgroup's
@@ -24,6 +24,7 @@
 // neither table depends on the order of arrival.
 #include <algorithm>
 
+#include "ftk_device.h"
 #include "ftk_gcbias.h"
 
 namespace ftk {
@@ -42,19 +43,9 @@ static_assert(kGcRefPer * kGcRefThreads >= kGcRefTile + FTK_GC_MAX_LEN, "a tile 
 
 __device__ __forceinline__ int tri(int L) { return L * (L + 1) / 2; }
 
-// does [a, b) touch an N block?  (sorted, disjoint: the first block that ends behind a)
-__device__ __forceinline__ bool span_has_n(const GcImage& im, int a, int b) {
-    int lo = 0, hi = im.n_nblk;
-    while (lo < hi) {
-        const int m = (lo + hi) >> 1;
-        if (im.nblk_end[m] <= a) lo = m + 1; else hi = m;
-    }
-    return lo < im.n_nblk && im.nblk_start[lo] < b;
-}
-
 // 0 <= a < b <= chrom_len, b - a <= FTK_GC_MAX_LEN.  -1: the span holds an N.
-__device__ __forceinline__ int span_gc_2bit(const GcImage& im, int a, int b) {
-    if (im.n_nblk && span_has_n(im, a, b)) return -1;
+__device__ __forceinline__ int span_gc_2bit(const RefView& im, int a, int b) {
+    if (im.n_nblk && ref_has_n(im, a, b)) return -1;
     const uint32_t* w32 = reinterpret_cast<const uint32_t*>(im.img);  // (the block is 256-byte aligned and 32 bytes longer than the image)
     const int w0 = a >> 4, w1 = (b - 1) >> 4;
     int g = 0;
@@ -68,10 +59,9 @@ __device__ __forceinline__ int span_gc_2bit(const GcImage& im, int a, int b) {
     return g;
 }
 
-__device__ __forceinline__ int span_gc_text(const GcImage& im, int a, int b) {
-    const int row = a / im.line_bases;
-    int col = a - row * im.line_bases;
-    long long off = (long long)row * im.line_width + col;
+__device__ __forceinline__ int span_gc_text(const RefView& im, int a, int b) {
+    int col;
+    long long off = ref_text_offset(im, a, col);
     int g = 0;
     bool bad = false;
     for (int j = a; j < b; ++j) {
@@ -79,13 +69,12 @@ __device__ __forceinline__ int span_gc_text(const GcImage& im, int a, int b) {
         const bool gc = (ch == 'G') | (ch == 'C');
         g += gc;
         bad |= !(gc | (ch == 'A') | (ch == 'T'));
-        ++off;
-        if (++col == im.line_bases) { col = 0; off += im.line_width - im.line_bases; }
+        ref_text_next(im, off, col);
     }
     return bad ? -1 : g;
 }
 
-__global__ __launch_bounds__(kGcFragThreads) void frag_gc_kernel(ContigView cv, GcImage im, FragGcParams p, int n_lds_cells,
+__global__ __launch_bounds__(kGcFragThreads) void frag_gc_kernel(ContigView cv, RefView im, FragGcParams p, int n_lds_cells,
                                                                  int16_t* __restrict__ gc_out,
                                                                  unsigned long long* __restrict__ table,
                                                                  unsigned long long* __restrict__ n_skipped) {
@@ -125,19 +114,19 @@ __global__ __launch_bounds__(kGcFragThreads) void frag_gc_kernel(ContigView cv, 
 }
 
 // is-GC (bit 0) / is-N or outside the contig (bit 16) of position q >= 0
-__device__ __forceinline__ uint32_t base_flags(const GcImage& im, int q) {
+__device__ __forceinline__ uint32_t base_flags(const RefView& im, int q) {
     if (q >= im.chrom_len) return 0x10000u;
     if (im.kind == FTK_REF_2BIT) {
-        if (im.n_nblk && span_has_n(im, q, q + 1)) return 0x10000u;
-        return (im.img[q >> 2] >> (6 - 2 * (q & 3))) & 1u;  // T=0 C=1 A=2 G=3
+        if (im.n_nblk && ref_has_n(im, q, q + 1)) return 0x10000u;
+        return twobit_code(im.img[q >> 2], q) & 1u;
     }
-    const int row = q / im.line_bases;
-    const int ch = im.img[(long long)row * im.line_width + (q - row * im.line_bases)] & 0xDF;
+    int col;
+    const int ch = im.img[ref_text_offset(im, q, col)] & 0xDF;
     if ((ch == 'G') | (ch == 'C')) return 1u;
     return ((ch == 'A') | (ch == 'T')) ? 0u : 0x10000u;
 }
 
-__global__ __launch_bounds__(kGcRefThreads) void ref_gc_table_kernel(GcImage im, int pos_lo, int pos_hi, int len_lo, int len_hi,
+__global__ __launch_bounds__(kGcRefThreads) void ref_gc_table_kernel(RefView im, int pos_lo, int pos_hi, int len_lo, int len_hi,
                                                                      long long stride, GcRefChunks ch, int n_tiles,
                                                                      unsigned long long* __restrict__ table) {
     extern __shared__ uint32_t gc_lds[];
@@ -161,12 +150,7 @@ __global__ __launch_bounds__(kGcRefThreads) void ref_gc_table_kernel(GcImage im,
             if (i < nx) sum += base_flags(im, tile_lo + i);
             f[k] = sum;
         }
-        uint32_t incl = sum;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const uint32_t t = __shfl_up(incl, o, 64);
-            if (lane >= o) incl += t;
-        }
+        const uint32_t incl = (uint32_t)wave_incl_scan_dpp((int)sum);  // (the packed sums stay far below 2^31)
         if (lane == 63) wsum[wv] = incl;
         __syncthreads();
         uint32_t excl = incl - sum;
@@ -200,7 +184,7 @@ __global__ __launch_bounds__(kGcRefThreads) void ref_gc_table_kernel(GcImage im,
 
 }  // namespace
 
-void launch_frag_gc(hipStream_t s, int n_cu, const ContigView& cv, const GcImage& im, FragGcParams p, int16_t* gc_out,
+void launch_frag_gc(hipStream_t s, int n_cu, const ContigView& cv, const RefView& im, FragGcParams p, int16_t* gc_out,
                     unsigned long long* table, unsigned long long* n_skipped) {
     if (cv.n <= 0) return;
     int n_cells = 0;
@@ -216,7 +200,7 @@ void launch_frag_gc(hipStream_t s, int n_cu, const ContigView& cv, const GcImage
                        gc_out, table, n_skipped);
 }
 
-void launch_ref_gc_table(hipStream_t s, int n_cu, const GcImage& im, int pos_lo, int pos_hi, int len_lo, int len_hi,
+void launch_ref_gc_table(hipStream_t s, int n_cu, const RefView& im, int pos_lo, int pos_hi, int len_lo, int len_hi,
                          long long stride, unsigned long long* table) {
     if (pos_hi <= pos_lo) return;
     GcRefChunks ch{};

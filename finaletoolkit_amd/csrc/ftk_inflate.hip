@@ -29,6 +29,7 @@
 #include <map>
 #include <mutex>
 
+#include "ftk_device.h"
 #include "ftk_inflate.h"
 
 namespace ftk {
@@ -79,16 +80,6 @@ static_assert(kFarDist - 257 >= kGran - 1, "the sources of a far match must alre
 constexpr int kWinCap = kRing - kFarDist - 2;
 static_assert(kFarDist + kWinCap < kRing && kWinCap >= 258, "a window's literals must not overwrite a match's sources");
 static_assert(kFarDist - 256 - kWinCap >= kGran - 1, "the sources of a window's far matches must already be flushed");
-
-__device__ __forceinline__ int wave_incl_scan(int x) {  // inclusive prefix sum over the 64 lanes (DPP)
-    x += __builtin_amdgcn_update_dpp(0, x, 0x111, 0xf, 0xf, false);
-    x += __builtin_amdgcn_update_dpp(0, x, 0x112, 0xf, 0xf, false);
-    x += __builtin_amdgcn_update_dpp(0, x, 0x114, 0xf, 0xf, false);
-    x += __builtin_amdgcn_update_dpp(0, x, 0x118, 0xf, 0xf, false);
-    x += __builtin_amdgcn_update_dpp(0, x, 0x142, 0xa, 0xf, false);
-    x += __builtin_amdgcn_update_dpp(0, x, 0x143, 0xc, 0xf, false);
-    return x;
-}
 
 struct __align__(16) WaveLds {
     uint8_t ring[kRing];
@@ -823,7 +814,7 @@ __global__ __launch_bounds__(64) FTK_INFLATE_OCC void bgzf_inflate_kernel(const 
                     // count in registers; fetch() finds the owner of the t-th token of the super-window and loads the token
                     // from the owner's column - no copy into one stream
                     const int nvalid = lane < n_lanes ? ncatch + (ntok - first_valid) : 0;
-                    const int incl = wave_incl_scan(nvalid);
+                    const int incl = wave_incl_scan_dpp(nvalid);
                     const int n_tokens = __builtin_amdgcn_readlane(incl, 63);
                     const int my_first = incl - nvalid;                  // tokens in front of this lane's
                     LSTAT(2, n_tokens);
@@ -879,7 +870,7 @@ __global__ __launch_bounds__(64) FTK_INFLATE_OCC void bgzf_inflate_kernel(const 
                         unsigned mark = tok & 3u;
                         const unsigned mlen = (tok >> 2) & 511u, mdist = tok >> 11;
                         const int olen = mark == 3u ? (int)mlen : (int)mark;
-                        const int inc = wave_incl_scan(olen);
+                        const int inc = wave_incl_scan_dpp(olen);
                         const uint32_t off = (uint32_t)(inc - olen);
                         const uint32_t room = min((uint32_t)kLaneCap, A_end - A);
                         const uint64_t bad = __ballot(mark != 0u && ((uint32_t)inc > room || (mark == 3u && mdist > (A - out_off) + off)));
@@ -1118,7 +1109,7 @@ __global__ __launch_bounds__(64) FTK_INFLATE_OCC void bgzf_inflate_kernel(const 
                 const uint64_t on = __ballot(mark != 0u);
                 if (on) {
                     const int olen = mark == 3u ? (int)mlen : (int)mark;
-                    const int inc = wave_incl_scan(olen);
+                    const int inc = wave_incl_scan_dpp(olen);
                     const uint32_t off = (uint32_t)(inc - olen);
                     const uint32_t room = min((uint32_t)kWinCap, A_end - A);
                     // the first symbol that does not fit or points outside the block ends the window in front of it

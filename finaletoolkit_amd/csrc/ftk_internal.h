@@ -43,6 +43,18 @@ struct ContigView {
     int32_t r1_inside;
 };
 
+// One contig's reference image as the kernels read it (device pointers; ftk_ref_upload + ftk_ref_set_layout, filled by
+// open_ref_view).  The device helpers that read through it are in ftk_device.h.
+struct RefView {
+    const uint8_t* img;
+    const int32_t* nblk_start;  // 2bit: N blocks, sorted, disjoint
+    const int32_t* nblk_end;
+    int n_nblk;
+    int kind;  // FTK_REF_*
+    int chrom_len;
+    int line_bases, line_width;  // FASTA text geometry (>= 1)
+};
+
 struct ContigData {
     ContigView v{};
     void* base = nullptr;     // one allocation holding all columns

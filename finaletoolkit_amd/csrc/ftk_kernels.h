@@ -50,15 +50,8 @@ void launch_r1_inside(hipStream_t s, const int32_t* start, const int32_t* end, c
 void launch_plan(hipStream_t s, const ContigView& cv, const int32_t* ws, const int32_t* we, int n_win, int lmax,
                  int small_max, const WindowPlan& pl, int64_t* const zero[4]);
 
-// Where the motif pass reads its k-mers (device pointers) and which ends count.
-struct MotifParams {
-    const uint8_t* img;        // reference image of the contig (ftk_ref_upload)
-    const int32_t* nblk_start; // 2bit: N blocks, sorted
-    const int32_t* nblk_end;
-    int n_nblk;
-    int kind;                  // FTK_REF_*
-    int chrom_len;
-    int line_bases, line_width;  // FASTA text geometry
+// Where the motif pass reads its k-mers (the contig's reference image) and which ends count.
+struct MotifParams : RefView {
     int k, f_off, r_off;
     int both, neg, guard, rev_err;
 };

@@ -11,6 +11,7 @@
 //   * WPS (and the cleavage profile) build a per-tile difference array in LDS
 //     with ds_add, scan it on DPP and stream the scores out with non-temporal
 //     16-byte stores, 1 KB contiguous per store instruction.
+#include "ftk_device.h"
 #include "ftk_kernels.h"
 
 #include <cstdlib>
@@ -307,50 +308,34 @@ struct DelfiPred {
     }
 };
 
-// CH of the window-feature kernels: 0 no coverage filter, 1 coverage / histogram, 2 motif pass (any image, any k),
-// kMotifWord the motif pass on a 2bit image with k <= 13.
+// CH of the window-feature kernels: 0 no coverage filter, 1 coverage / histogram, 2 motif pass (general form: FASTA text, any
+// k; 2bit, k <= 13), kMotifWord the motif pass on a 2bit image with k <= 13 under ftk_motif_counts' own filter.
 constexpr int kMotifWord = 3;
 
 // k-mer starting at base `lo` of the reference image as a base-4 number in ACGT order
 // (gen_kmers order, utils/utils.py:388-410), or -1 when it holds anything but A/C/G/T
 // (upper- or lower-case: io/reference.py:171 upper-cases).  revcomp: the reverse complement's code.
 __device__ __forceinline__ int kmer_code(const MotifParams& M, int lo, bool revcomp) {
-    int code = 0;
     if (M.kind == FTK_REF_2BIT) {
-        // N blocks (sorted, disjoint): first block ending after lo
-        int a = 0, b = M.n_nblk;
-        while (a < b) {
-            const int m = (a + b) >> 1;
-            if (M.nblk_end[m] <= lo) a = m + 1; else b = m;
+        if (ref_has_n(M, lo, lo + M.k)) return -1;
+        // bases lo .. lo + k - 1 lie in at most four consecutive bytes (k <= 13; ftk_motif_counts, the one caller, admits
+        // k <= 7): ONE (unaligned) 4-byte load instead of a byte load per base (the image's block is at least 32 bytes
+        // longer than the image), the sixteen 2-bit groups translated at once, the k-mer cut out with a shift and a mask
+        typedef uint32_t __attribute__((aligned(1))) u32u;
+        const uint32_t be = __builtin_bswap32(*reinterpret_cast<const u32u*>(M.img + (lo >> 2)));  // first base on top
+        const uint32_t v1 = (be >> 1) & 0x55555555u, v0 = be & 0x55555555u;    // T=00 C=01 A=10 G=11
+        const uint32_t acgt = ((~(v1 ^ v0) & 0x55555555u) << 1) | (~v1 & 0x55555555u);  // -> A=00 C=01 G=10 T=11
+        const uint32_t mask = (1u << (2 * M.k)) - 1u;
+        uint32_t x = (acgt >> (32 - 2 * ((lo & 3) + M.k))) & mask;  // base 0 most significant
+        if (revcomp) {  // base j complemented at bits 2j: the 2-bit groups in reverse order, each XOR 3
+            uint32_t y = __brev(x) >> (32 - 2 * M.k);
+            y = ((y & 0x55555555u) << 1) | ((y >> 1) & 0x55555555u);
+            x = y ^ mask;
         }
-        if (a < M.n_nblk && M.nblk_start[a] < lo + M.k) return -1;
-        if (M.k <= 13) {
-            // bases lo .. lo + k - 1 lie in at most four consecutive bytes: ONE (unaligned) 4-byte load instead of a
-            // byte load per base (the image's block is at least 32 bytes longer than the image), the sixteen 2-bit
-            // groups translated at once, the k-mer cut out with a shift and a mask
-            typedef uint32_t __attribute__((aligned(1))) u32u;
-            const uint32_t be = __builtin_bswap32(*reinterpret_cast<const u32u*>(M.img + (lo >> 2)));  // first base on top
-            const uint32_t v1 = (be >> 1) & 0x55555555u, v0 = be & 0x55555555u;    // T=00 C=01 A=10 G=11
-            const uint32_t acgt = ((~(v1 ^ v0) & 0x55555555u) << 1) | (~v1 & 0x55555555u);  // -> A=00 C=01 G=10 T=11
-            const uint32_t mask = (1u << (2 * M.k)) - 1u;
-            uint32_t x = (acgt >> (32 - 2 * ((lo & 3) + M.k))) & mask;  // base 0 most significant
-            if (revcomp) {  // base j complemented at bits 2j: the 2-bit groups in reverse order, each XOR 3
-                uint32_t y = __brev(x) >> (32 - 2 * M.k);
-                y = ((y & 0x55555555u) << 1) | ((y >> 1) & 0x55555555u);
-                x = y ^ mask;
-            }
-            return (int)x;
-        }
-        for (int j = 0; j < M.k; ++j) {
-            const int p = lo + j;
-            const int v = (M.img[p >> 2] >> (6 - 2 * (p & 3))) & 3;   // T=0 C=1 A=2 G=3
-            const int base = (0x87 >> (2 * v)) & 3;                   // -> A=0 C=1 G=2 T=3 ({3,1,0,2} packed)
-            code = revcomp ? (code | ((3 - base) << (2 * j))) : (code * 4 + base);
-        }
-        return code;
+        return (int)x;
     }
-    int row = lo / M.line_bases, col = lo - row * M.line_bases;
-    long long off = (long long)row * M.line_width + col;
+    int code = 0, col;
+    long long off = ref_text_offset(M, lo, col);
     for (int j = 0; j < M.k; ++j) {
         const int ch = M.img[off] & 0xDF;
         int base;
@@ -360,8 +345,7 @@ __device__ __forceinline__ int kmer_code(const MotifParams& M, int lo, bool revc
         else if (ch == 'T') base = 3;
         else return -1;
         code = revcomp ? (code | ((3 - base) << (2 * j))) : (code * 4 + base);
-        ++off;
-        if (++col == M.line_bases) { col = 0; off += M.line_width - M.line_bases; }
+        ref_text_next(M, off, col);
     }
     return code;
 }
@@ -402,11 +386,7 @@ __device__ __forceinline__ void motif_window(const MotifParams& M, const ContigV
 // the one way there -- searches every block)
 __device__ __attribute__((noinline)) bool motif_n_search(const int32_t* nblk_start, const int32_t* nblk_end, int n_nblk,
                                                          int k, int p, int a, int b) {
-    while (a < b) {  // first block ending after p
-        const int m = (a + b) >> 1;
-        if (nblk_end[m] <= p) a = m + 1; else b = m;
-    }
-    return a < n_nblk && nblk_start[a] < p + k;
+    return n_block_search(nblk_start, nblk_end, n_nblk, p, p + k, a, b);
 }
 __device__ __forceinline__ bool motif_has_n(const MotifParams& M, int p, int o0, int o1, int g_lo, int g_hi) {
     int a = o0, b = o1;
@@ -1279,18 +1259,6 @@ __device__ __forceinline__ long long xcd_contiguous(unsigned orig, unsigned nwg)
     return (long long)base + orig / 8;
 }
 
-// inclusive scan across the 64 lanes of a wave (row_shr 1/2/4/8 inside rows of
-// 16, then row_bcast:15 / row_bcast:31 across rows)
-__device__ __forceinline__ int wave_incl_scan_dpp(int x) {
-    x += __builtin_amdgcn_update_dpp(0, x, 0x111, 0xf, 0xf, false);
-    x += __builtin_amdgcn_update_dpp(0, x, 0x112, 0xf, 0xf, false);
-    x += __builtin_amdgcn_update_dpp(0, x, 0x114, 0xf, 0xf, false);
-    x += __builtin_amdgcn_update_dpp(0, x, 0x118, 0xf, 0xf, false);
-    x += __builtin_amdgcn_update_dpp(0, x, 0x142, 0xa, 0xf, false);
-    x += __builtin_amdgcn_update_dpp(0, x, 0x143, 0xc, 0xf, false);
-    return x;
-}
-
 struct WpsTile {
     long long t0;        // first base
     long long fmin, fmax;  // fetch window of the owning interval (frag/_wps.py:156-157)
@@ -1375,9 +1343,7 @@ __device__ __forceinline__ void wps_block(const unsigned block_id, const unsigne
     // index (conservative): surplus candidates add nothing, their events clip.
     auto cand_bound = [&](const WpsTile& ti, int which) -> int {
         const long long q = which == 0 ? ti.t0 - 1 - hl - (long long)p.lmax : ti.t0 + ti.len_t + hr;
-        if (q <= 0) return 0;
-        const long long kb = q >> kBinShift;
-        return kb >= cv.n_bins ? cv.n : cv.bin_idx[kb + which];
+        return index_bound(cv, q, which);
     };
     // one fragment -> its +-1/+-2 events in the tile's difference array
     auto apply = [&](const WpsTile& ti, int par, int i, int fs, int fe, int q) {
@@ -1779,14 +1745,6 @@ __device__ __forceinline__ void cleave_tile(const ContigView& cv, const CleavePa
     }
 }
 
-// candidates of the bases [t0, t0 + len_t): fs < t0 + len_t and fe >= t0 (a - fragment ending exactly at t0 still
-// puts an end there)
-__device__ __forceinline__ int cleave_bound(const ContigView& cv, long long q, int which) {
-    if (q <= 0) return 0;
-    const long long kb = q >> kBinShift;
-    return kb >= cv.n_bins ? cv.n : cv.bin_idx[kb + which];
-}
-
 __global__ __launch_bounds__(256) void cleavage_kernel(ContigView cv, CleaveParams p, const int64_t* iv_start_,
                                                        const int64_t* iv_stop_, const int64_t* out_off_,
                                                        const int32_t* tile_iv, const int32_t* tile_k,
@@ -1816,9 +1774,10 @@ __global__ __launch_bounds__(256) void cleavage_kernel(ContigView cv, CleavePara
         for (int j = 0; j < H / 4 / 256; ++j) { a4[j * 256 + tid] = z; b4[j * 256 + tid] = z; }
         if (tid == 2) pre_s = 0;
     };
-    // The candidates' bounds: two reads of the position index at block-uniform addresses, taken by every thread (scalar
+    // The candidates of the bases [t0, t0 + len_t): fs < t0 + len_t and fe >= t0 (a - fragment ending exactly at t0 still
+    // puts an end there).  Their bounds: two reads of the position index at block-uniform addresses, taken by every thread (scalar
     // loads, under way while the arrays are cleared; no hand-over through LDS, one barrier instead of two).
-    const int lo = cleave_bound(cv, t0 - (long long)p.lmax, 0), hi = cleave_bound(cv, t0 + len_t, 1);
+    const int lo = index_bound(cv, t0 - (long long)p.lmax, 0), hi = index_bound(cv, t0 + len_t, 1);
     clear();
     __syncthreads();
     double* dst = out + out_off + k * T;
@@ -1831,7 +1790,7 @@ __global__ __launch_bounds__(256) void cleavage_kernel(ContigView cv, CleavePara
         const int len_h = min(len_t - half * H, H);
         if (len_h <= 0) break;
         __syncthreads();  // (the arrays of the first half are done with)
-        const int lo_h = cleave_bound(cv, th - (long long)p.lmax, 0), hi_h = cleave_bound(cv, th + len_h, 1);
+        const int lo_h = index_bound(cv, th - (long long)p.lmax, 0), hi_h = index_bound(cv, th + len_h, 1);
         clear();
         __syncthreads();
         cleave_tile<false, H>(cv, p, iv_start, iv_stop, th, len_h, lo_h, hi_h, dst + (long long)half * H, dd, en, pre_s, wtot);
@@ -1873,7 +1832,7 @@ __global__ __launch_bounds__(256) void gc_count_kernel(const uint8_t* __restrict
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 const int64_t pos = b * 4 + k;
-                if (pos >= lo && pos < hi) c += (v >> (6 - 2 * k)) & 1u;
+                if (pos >= lo && pos < hi) c += twobit_code(v, k) & 1u;
             }
             return c;
         };
