@@ -17,6 +17,7 @@
 #include <cstdlib>
 
 #include <algorithm>
+#include <type_traits>
 
 namespace ftk {
 
@@ -27,6 +28,18 @@ __device__ __forceinline__ int wave_reduce_add(int v) {
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
     return v;
+}
+
+// Largest m in [0, n) with at_or_below(m), a predicate that holds for a prefix of the indices and for m = 0: the
+// item of a batched launch that owns a row, by bisection on the items' first rows.
+template <class Pred>
+__device__ __forceinline__ int last_at_or_below(int n, Pred&& at_or_below) {
+    int lo = 0, hi = n;
+    while (hi - lo > 1) {
+        const int m = (lo + hi) >> 1;
+        if (at_or_below(m)) lo = m; else hi = m;
+    }
+    return lo;
 }
 
 // ---------------------------------------------------------------------------
@@ -269,6 +282,25 @@ struct WinPred {
     }
 };
 
+// frag/_delfi.py:455-462: a fragment [fs, fe) is blacklisted iff max{r1 : r0 <= fs, region inside the window} > fe.
+// [o0, o1) is the window's slice of the blacklist CSR: r0 the region starts (sorted), pm the running maximum of
+// the region stops.
+__device__ __forceinline__ bool blacklisted(const int32_t* r0, const int32_t* pm, int o0, int o1, int fs, int fe) {
+    int lo = o0, hi = o1;  // upper bound: first region with r0 > fs
+    while (lo < hi) {
+        const int m = (lo + hi) >> 1;
+        if (r0[m] <= fs) lo = m + 1; else hi = m;
+    }
+    return lo > o0 && pm[lo - 1] > fe;
+}
+
+// The window's slice [o0, o1) of the blacklist CSR (hoisted per window by the caller); empty without a blacklist.
+template <bool DF>
+__device__ __forceinline__ void blacklist_range(const int32_t* bl_off, int w, int& o0, int& o1) {
+    o0 = o1 = 0;
+    if (DF && bl_off) { o0 = bl_off[w]; o1 = bl_off[w + 1]; }
+}
+
 // frag/_delfi.py:443-472.  Returns 0 (skip), 1 (short) or 2 (long).  [o0, o1) is
 // the window's slice of the blacklist CSR (hoisted per window by the caller).
 // ContigGaps.in_tcmere (genome/gaps.py:217-237) is pre-reduced on the host to two
@@ -294,16 +326,7 @@ struct DelfiPred {
             ok &= (fs < we) & (fe > ws);
         }
         ok &= !((fe > cen0) & (fs < cen1)) & !((fe > tel0) & (fs < tel1));
-        if (o1 > o0) {  // (uniform per window) frag/_delfi.py:455-462: blacklisted iff max{r1 : r0 <= fs} > fe
-            if (ok) {
-                int lo = o0, hi = o1;  // upper bound: first region with r0 > fs
-                while (lo < hi) {
-                    const int m = (lo + hi) >> 1;
-                    if (bl_r0[m] <= fs) lo = m + 1; else hi = m;
-                }
-                if (lo > o0 && bl_pm[lo - 1] > fe) ok = false;
-            }
-        }
+        if (o1 > o0 && ok && blacklisted(bl_r0, bl_pm, o0, o1, fs, fe)) ok = false;  // (o1 > o0: uniform per window)
         return ok ? ((len >= 151) ? 2 : 1) : 0;
     }
 };
@@ -475,16 +498,7 @@ __device__ __forceinline__ void feat_element(const ContigView& cv, const FeatPar
             int y = (q - P.df_q) | (len - 100) | (220 - len) | t_mid | t_fetch;
             y |= (P.cen0 - fe) & (fs - P.cen1);      // not (fe > cen0 and fs < cen1)
             y |= (P.tel0 - fe) & (fs - P.tel1);
-            if (BL) {  // blacklisted iff max{r1 : r0 <= fs, region inside the window} > fe (:455-462)
-                if (y >= 0) {
-                    int lo = o0, hi = o1;  // upper bound: first region with r0 > fs
-                    while (lo < hi) {
-                        const int m = (lo + hi) >> 1;
-                        if (P.dp.bl_r0[m] <= fs) lo = m + 1; else hi = m;
-                    }
-                    if (lo > o0 && P.dp.bl_pm[lo - 1] > fe) y = -1;
-                }
-            }
+            if (BL && y >= 0 && blacklisted(P.dp.bl_r0, P.dp.bl_pm, o0, o1, fs, fe)) y = -1;
             a.sh += (unsigned)(y | (150 - len)) >> 31;
             a.lg += (unsigned)(y | (len - 151)) >> 31;
         }
@@ -721,8 +735,8 @@ __global__ __launch_bounds__(256) void feat_small_kernel(ContigView cv, const in
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
     }
-    int o0 = 0, o1 = 0;
-    if (DF && P.dp.bl_off) { o0 = P.dp.bl_off[w]; o1 = P.dp.bl_off[w + 1]; }
+    int o0, o1;
+    blacklist_range<DF>(P.dp.bl_off, w, o0, o1);
     if (CH == kMotifWord) motif_window(P.mp, cv, ws, we1 + 1, o0, o1);
     FeatAcc a;
     for (int i = lo + 4 * lane; i < hi; i += 256) {  // lo is a multiple of 4 (planner)
@@ -822,8 +836,8 @@ __global__ __launch_bounds__(256) void feat_large_kernel(ContigView cv, const in
         int ws, we1;
         window_bounds<CH>(ws_[w], we_[w], ws, we1);
         const int wlo = cand_lo[w], whi = cand_hi[w];
-        int o0 = 0, o1 = 0;
-        if (DF && P.dp.bl_off) { o0 = P.dp.bl_off[w]; o1 = P.dp.bl_off[w + 1]; }
+        int o0, o1;
+        blacklist_range<DF>(P.dp.bl_off, w, o0, o1);
         if (CH == kMotifWord) motif_window(P.mp, cv, ws, we1 + 1, o0, o1);
         const uint32_t c_end = min(c1, w_next);
         if (CH == kMotifWord) {  // this block's chunks of the window as one stream
@@ -967,8 +981,8 @@ __global__ __launch_bounds__(kFeatBS) void feat_block_kernel(ContigView cv, cons
     extern __shared__ uint32_t lds_hist[];
     __shared__ int red[5][kFeatBS / 64];
     const int w = blockIdx.x;
-    int o0 = 0, o1 = 0;
-    if (DF && P.dp.bl_off) { o0 = P.dp.bl_off[w]; o1 = P.dp.bl_off[w + 1]; }
+    int o0, o1;
+    blacklist_range<DF>(P.dp.bl_off, w, o0, o1);
     feat_block_body<kFeatBS, CH, DF, BAM>(cv, ws_[w], we_[w], lmax, P, o0, o1, (size_t)w, lds_hist, red);
 }
 
@@ -1023,16 +1037,7 @@ __device__ __forceinline__ void fast_element(const FeatParams& P, int fs, int fe
             y |= (P.cen0 - fe) & (fs - P.cen1);      // not (fe > cen0 and fs < cen1)
             y |= (P.tel0 - fe) & (fs - P.tel1);
         }
-        if (BL) {  // blacklisted iff max{r1 : r0 <= fs, region inside the window} > fe (:455-462)
-            if (y >= 0) {
-                int lo = o0, hi = o1;
-                while (lo < hi) {
-                    const int m = (lo + hi) >> 1;
-                    if (P.dp.bl_r0[m] <= fs) lo = m + 1; else hi = m;
-                }
-                if (lo > o0 && P.dp.bl_pm[lo - 1] > fe) y = -1;
-            }
-        }
+        if (BL && y >= 0 && blacklisted(P.dp.bl_r0, P.dp.bl_pm, o0, o1, fs, fe)) y = -1;
         a.rej += (unsigned)y >> 31;
         a.lg += (unsigned)(~y & (150 - len)) >> 31;  // passes and len >= 151
     }
@@ -1174,9 +1179,27 @@ __global__ __launch_bounds__(kFeatBS) void feat_fast_kernel(ContigView cv, const
     extern __shared__ uint32_t lds_hist[];
     __shared__ int red[5][kFeatBS / 64];
     const int w = blockIdx.x;
-    int o0 = 0, o1 = 0;
-    if (DF && P.dp.bl_off) { o0 = P.dp.bl_off[w]; o1 = P.dp.bl_off[w + 1]; }
+    int o0, o1;
+    blacklist_range<DF>(P.dp.bl_off, w, o0, o1);
     feat_fast_body<kFeatBS, CHK, HIST, DF, BAM>(cv, ws_[w], we_[w], lmax, P, o0, o1, (size_t)w, lds_hist, red);
+}
+
+// The block kernels for the windows of SEVERAL contigs in one launch (ftk_window_features_batch): block b owns
+// window b of the concatenated list; its item (contig view, windows, blacklist CSR, gap constants) is
+// found by bisection on the items' first rows; outputs are indexed by the global row.
+// batch_item: the item that owns global window gw, with the window's place w in it, the launch's parameters with
+// the item's gap constants and blacklist columns (Q) and the window's blacklist slice.
+template <bool DF>
+__device__ __forceinline__ const FeatItem& batch_item(const FeatItem* __restrict__ items, int n_items, int gw,
+                                                      const FeatParams& P, FeatParams& Q, int& w, int& o0, int& o1) {
+    const FeatItem& I = items[last_at_or_below(n_items, [&](int m) { return items[m].win_base <= gw; })];
+    w = gw - I.win_base;
+    Q = P;
+    Q.cen0 = I.cen0; Q.cen1 = I.cen1; Q.tel0 = I.tel0; Q.tel1 = I.tel1;
+    Q.dp.bl_r0 = I.bl_r0;
+    Q.dp.bl_pm = I.bl_pm;
+    blacklist_range<DF>(I.bl_off, w, o0, o1);
+    return I;
 }
 
 template <int kFeatBS, bool CHK, bool HIST, bool DF, bool BAM>
@@ -1185,53 +1208,22 @@ __global__ __launch_bounds__(kFeatBS) void feat_fast_batch_kernel(const FeatItem
     extern __shared__ uint32_t lds_hist[];
     __shared__ int red[5][kFeatBS / 64];
     const int gw = blockIdx.x;
-    int it = 0;
-    {
-        int lo = 0, hi = n_items;  // largest item with win_base <= gw
-        while (hi - lo > 1) {
-            const int m = (lo + hi) >> 1;
-            if (items[m].win_base <= gw) lo = m; else hi = m;
-        }
-        it = lo;
-    }
-    const FeatItem& I = items[it];
-    const int w = gw - I.win_base;
-    FeatParams Q = P;
-    Q.cen0 = I.cen0; Q.cen1 = I.cen1; Q.tel0 = I.tel0; Q.tel1 = I.tel1;
-    Q.dp.bl_r0 = I.bl_r0;
-    Q.dp.bl_pm = I.bl_pm;
-    int o0 = 0, o1 = 0;
-    if (DF && I.bl_off) { o0 = I.bl_off[w]; o1 = I.bl_off[w + 1]; }
+    FeatParams Q;
+    int w, o0, o1;
+    const FeatItem& I = batch_item<DF>(items, n_items, gw, P, Q, w, o0, o1);
     const ContigView cv = I.cv;
     feat_fast_body<kFeatBS, CHK, HIST, DF, BAM>(cv, I.ws[w], I.we[w], I.lmax, Q, o0, o1, (size_t)gw, lds_hist, red);
 }
 
-// The same for the windows of SEVERAL contigs in one launch (ftk_window_features_batch): block b owns
-// window b of the concatenated list; its item (contig view, windows, blacklist CSR, gap constants) is
-// found by bisection on the items' first rows; outputs are indexed by the global row.
 template <int kFeatBS, int CH, bool DF, bool BAM>
 __global__ __launch_bounds__(kFeatBS) void feat_batch_kernel(const FeatItem* __restrict__ items, int n_items,
                                                          FeatParams P) {
     extern __shared__ uint32_t lds_hist[];
     __shared__ int red[5][kFeatBS / 64];
     const int gw = blockIdx.x;
-    int it = 0;
-    {
-        int lo = 0, hi = n_items;  // largest item with win_base <= gw
-        while (hi - lo > 1) {
-            const int m = (lo + hi) >> 1;
-            if (items[m].win_base <= gw) lo = m; else hi = m;
-        }
-        it = lo;
-    }
-    const FeatItem& I = items[it];
-    const int w = gw - I.win_base;
-    FeatParams Q = P;
-    Q.cen0 = I.cen0; Q.cen1 = I.cen1; Q.tel0 = I.tel0; Q.tel1 = I.tel1;
-    Q.dp.bl_r0 = I.bl_r0;
-    Q.dp.bl_pm = I.bl_pm;
-    int o0 = 0, o1 = 0;
-    if (DF && I.bl_off) { o0 = I.bl_off[w]; o1 = I.bl_off[w + 1]; }
+    FeatParams Q;
+    int w, o0, o1;
+    const FeatItem& I = batch_item<DF>(items, n_items, gw, P, Q, w, o0, o1);
     const ContigView cv = I.cv;
     feat_block_body<kFeatBS, CH, DF, BAM>(cv, I.ws[w], I.we[w], I.lmax, Q, o0, o1, (size_t)gw, lds_hist, red);
 }
@@ -1308,12 +1300,7 @@ __device__ __forceinline__ void wps_block(const unsigned block_id, const unsigne
     // limits come from the item that owns it (bisection on the items' first tiles)
     long long b_start = 0, b_stop = 0, b_off = 0, b_tile0 = 0;
     if (BATCH) {
-        int lo = 0, hi = n_items;
-        while (hi - lo > 1) {
-            const int m = (lo + hi) >> 1;
-            if (items[m].tile_base <= tfirst) lo = m; else hi = m;
-        }
-        const WpsItem& I = items[lo];
+        const WpsItem& I = items[last_at_or_below(n_items, [&](int m) { return items[m].tile_base <= tfirst; })];
         cv = I.cv;
         p.chrom_size = I.chrom_size;
         p.lmax = I.lmax;
@@ -1411,14 +1398,7 @@ __device__ __forceinline__ void wps_block(const unsigned block_id, const unsigne
             y |= (F.tel0 - fe) & (fs - F.tel1);
             if (F.bl_off && y >= 0) {
                 const int o0 = F.bl_off[w], o1 = F.bl_off[w + 1];
-                if (o1 > o0) {
-                    int lo2 = o0, hi2 = o1;
-                    while (lo2 < hi2) {
-                        const int m = (lo2 + hi2) >> 1;
-                        if (F.bl_r0[m] <= fs) lo2 = m + 1; else hi2 = m;
-                    }
-                    if (lo2 > o0 && F.bl_pm[lo2 - 1] > fe) y = -1;
-                }
+                if (o1 > o0 && blacklisted(F.bl_r0, F.bl_pm, o0, o1, fs, fe)) y = -1;
             }
             const unsigned sb = (unsigned)(y | (150 - len)) >> 31, lb = (unsigned)(y | (len - 151)) >> 31;
             if (primary) { f_sh += sb; f_lg += lb; }
@@ -1618,8 +1598,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5, 5))) voi
         extern __shared__ uint32_t lds_hist[];
         __shared__ int red[5][4];
         const int w = blockIdx.x;
-        int o0 = 0, o1 = 0;
-        if (DF && P.dp.bl_off) { o0 = P.dp.bl_off[w]; o1 = P.dp.bl_off[w + 1]; }
+        int o0, o1;
+        blacklist_range<DF>(P.dp.bl_off, w, o0, o1);
         feat_fast_body<256, CHK, HIST, DF, BAM>(cv, ws_[w], we_[w], lmax, P, o0, o1, (size_t)w, lds_hist, red);
         return;
     }
@@ -2061,6 +2041,52 @@ static WinPred make_win_pred(const ftk_filter& f) {
                    f.fetch_mode == FTK_FETCH_BAM_READ1};
 }
 
+// Run-time booleans as template arguments: with_bools(fn, a, b, ...) calls fn(A, B, ...) with a std::true_type or
+// std::false_type per boolean, so a launch site is ONE hipLaunchKernelGGL inside a generic lambda (`A()` is a constant
+// expression there).  Every combination is instantiated: a site whose kernels exist for some combinations only
+// guards the launch with `if constexpr`.
+template <class Fn>
+static void with_bools(Fn&& fn) { fn(); }
+template <class Fn, class... Bools>
+static void with_bools(Fn&& fn, bool first, Bools... rest) {
+    if (first) with_bools([&](auto... c) { fn(std::true_type{}, c...); }, rest...);
+    else with_bools([&](auto... c) { fn(std::false_type{}, c...); }, rest...);
+}
+template <int V>
+using int_c = std::integral_constant<int, V>;
+
+// The launch parameters of a request.  The sign-test constants are clamped so that no difference in the element tests
+// can overflow (coordinates are < 2^30).  with_gaps = false (the batched launch): the gap constants and the
+// blacklist CSR stay zero, the kernel takes them from each item.
+static FeatParams make_feat_params(const FeatureRequest& r, bool with_gaps) {
+    FeatParams P{};
+    if (r.filter) {
+        const ftk_filter& f = *r.filter;
+        P.wp = make_win_pred(f);
+        P.ch_q = std::min(std::max(f.mapq_min, 0), 256);
+        P.ch_min = f.min_len < 0 ? 0 : std::min(f.min_len, 1 << 30);
+        P.ch_max = f.max_len < 0 ? (1 << 30) : std::min(f.max_len, 1 << 30);
+        P.is_any = f.policy == FTK_POLICY_ANY;
+    }
+    P.df_q = std::min(std::max(r.delfi_mapq_min, 0), 256);
+    if (with_gaps) {
+        int gc[4];
+        gap_constants(r.gaps, gc);
+        P.cen0 = gc[0]; P.cen1 = gc[1]; P.tel0 = gc[2]; P.tel1 = gc[3];
+        P.dp = DelfiPred{r.delfi_mapq_min, gc[0], gc[1], gc[2], gc[3], r.bl_off, r.bl_r0, r.bl_pm};
+    }
+    P.do_cov = r.cov_out != nullptr;
+    P.do_hist = r.hist_out != nullptr;
+    P.len_lo = r.len_lo;
+    P.n_bins = r.n_bins;
+    P.cov_out = r.cov_out;
+    P.hist_out = r.hist_out;
+    P.over_out = r.over_out;
+    P.short_out = r.short_out;
+    P.long_out = r.long_out;
+    return P;
+}
+
 // The FAST block kernels serve the common request: midpoint policy, no length bounds on the coverage /
 // histogram filter, and (when coverage and DELFI run together) one mapq cut for both.  FTK_FEAT_FAST=0
 // keeps the general kernels (tests run both).
@@ -2072,40 +2098,37 @@ static bool feat_fast_ok(const FeatParams& P, bool ch, bool df) {
     return true;
 }
 
+// What a FAST kernel receives: its shared mapq term is ch_q, the DELFI cut when DELFI runs alone.
+static FeatParams fast_params(FeatParams P, bool ch) {
+    if (!ch) P.ch_q = P.df_q;
+    return P;
+}
+
 template <int CH, bool DF, bool BAM>
 static bool launch_feat_t(hipStream_t s, int grid_large, const ContigView& cv, const int32_t* ws, const int32_t* we,
                           int n_win, const WindowPlan& pl, const FeatParams& P, bool small_path, int block_lmax,
                           int block_threads, const WpsTail* tail) {
-    const size_t lds1 = (CH && P.do_hist) ? (size_t)(P.n_bins + 1) * sizeof(uint32_t) : 0;  // + overflow bin
-    if (tail && tail->n_tiles > 0 && block_lmax >= 0 && CH < 2 && feat_fast_ok(P, CH != 0, DF) &&
-        (long long)n_win + tail->n_tiles < (1LL << 31)) {
-        // the merged launch: feature blocks first, the WPS tiles behind them (feat_then_wps_kernel)
-        FeatParams Pf = P;
-        if (!CH) Pf.ch_q = P.df_q;
-        const dim3 grid((unsigned)((long long)n_win + tail->n_tiles));
-#define FTK_MERGED(HIST, NT)                                                                                         \
-    hipLaunchKernelGGL((feat_then_wps_kernel<CH != 0, HIST, DF, BAM, NT>), grid, dim3(256), lds1, s, cv, ws, we, n_win, \
-                       block_lmax, Pf, tail->p, (long long)tail->n_tiles, tail->out)
-        if (CH && P.do_hist) { if (tail->p.nt_store) FTK_MERGED(true, true); else FTK_MERGED(true, false); }
-        else { if (tail->p.nt_store) FTK_MERGED(false, true); else FTK_MERGED(false, false); }
-#undef FTK_MERGED
-        return true;
-    }
+    const bool hist = CH && P.do_hist;
+    const size_t lds1 = hist ? (size_t)(P.n_bins + 1) * sizeof(uint32_t) : 0;  // + overflow bin
     if (block_lmax >= 0 && CH < 2 && feat_fast_ok(P, CH != 0, DF)) {
-#define FTK_FAST(BS)                                                                                                \
-    do {                                                                                                            \
-        if (CH && P.do_hist)                                                                                        \
-            hipLaunchKernelGGL((feat_fast_kernel<BS, CH != 0, true, DF, BAM>), dim3(n_win), dim3(BS), lds1, s, cv, ws, we,   \
-                               n_win, block_lmax, Pf);                                                              \
-        else                                                                                                        \
-            hipLaunchKernelGGL((feat_fast_kernel<BS, CH != 0, false, DF, BAM>), dim3(n_win), dim3(BS), lds1, s, cv, ws, we,  \
-                               n_win, block_lmax, Pf);                                                              \
-    } while (0)
-        FeatParams Pf = P;
-        if (!CH) Pf.ch_q = P.df_q;  // the shared mapq term
-        if (block_threads >= 512) FTK_FAST(512);
-        else FTK_FAST(256);
-#undef FTK_FAST
+        const FeatParams Pf = fast_params(P, CH != 0);
+        if (tail && tail->n_tiles > 0 && (long long)n_win + tail->n_tiles < (1LL << 31)) {
+            // the merged launch: feature blocks first, the WPS tiles behind them (feat_then_wps_kernel)
+            const dim3 grid((unsigned)((long long)n_win + tail->n_tiles));
+            with_bools([&](auto HIST, auto NT) {
+                hipLaunchKernelGGL((feat_then_wps_kernel<CH != 0, HIST(), DF, BAM, NT()>), grid, dim3(256), lds1, s, cv, ws,
+                                   we, n_win, block_lmax, Pf, tail->p, (long long)tail->n_tiles, tail->out);
+            }, hist, tail->p.nt_store != 0);
+            return true;
+        }
+        with_bools([&](auto HIST) {
+            if (block_threads >= 512)
+                hipLaunchKernelGGL((feat_fast_kernel<512, CH != 0, HIST(), DF, BAM>), dim3(n_win), dim3(512), lds1, s, cv,
+                                   ws, we, n_win, block_lmax, Pf);
+            else
+                hipLaunchKernelGGL((feat_fast_kernel<256, CH != 0, HIST(), DF, BAM>), dim3(n_win), dim3(256), lds1, s, cv,
+                                   ws, we, n_win, block_lmax, Pf);
+        }, hist);
         return false;
     }
     if (block_lmax >= 0) {
@@ -2136,51 +2159,29 @@ static bool launch_feat_t(hipStream_t s, int grid_large, const ContigView& cv, c
 bool launch_window_features(hipStream_t s, int grid_large, const ContigView& cv, const int32_t* ws, const int32_t* we,
                             int n_win, const WindowPlan& pl, const FeatureRequest& r, bool small_path, int block_lmax,
                             const WpsTail* tail) {
-    FeatParams P{};
+    FeatParams P = make_feat_params(r, true);
     const bool ch = r.cov_out || r.hist_out;
     const bool df = r.short_out != nullptr;
-    if (r.filter) P.wp = make_win_pred(*r.filter);
-    P.do_cov = r.cov_out != nullptr;
-    P.do_hist = r.hist_out != nullptr;
-    P.len_lo = r.len_lo;
-    P.n_bins = r.n_bins;
-    P.cov_out = r.cov_out;
-    P.hist_out = r.hist_out;
-    P.over_out = r.over_out;
-    P.short_out = r.short_out;
-    P.long_out = r.long_out;
-    {
-        int gc[4];
-        gap_constants(r.gaps, gc);
-        P.cen0 = gc[0]; P.cen1 = gc[1]; P.tel0 = gc[2]; P.tel1 = gc[3];
-        P.dp = DelfiPred{r.delfi_mapq_min, gc[0], gc[1], gc[2], gc[3], r.bl_off, r.bl_r0, r.bl_pm};
-        P.df_q = std::min(std::max(r.delfi_mapq_min, 0), 256);
-    }
-    if (r.filter) {
-        const ftk_filter& f = *r.filter;
-        P.ch_q = std::min(std::max(f.mapq_min, 0), 256);
-        P.ch_min = f.min_len < 0 ? 0 : std::min(f.min_len, 1 << 30);
-        P.ch_max = f.max_len < 0 ? (1 << 30) : std::min(f.max_len, 1 << 30);
-        P.is_any = f.policy == FTK_POLICY_ANY;
-    }
     const bool bam = cv.r1_start != nullptr && (!r.filter || r.filter->fetch_mode == FTK_FETCH_BAM_READ1);
-#define FTK_FEAT(CH, DF)                                                                              \
-    do {                                                                                              \
-        if (bam) merged = launch_feat_t<CH, DF, true>(s, grid_large, cv, ws, we, n_win, pl, P, small_path, block_lmax, r.block_threads, tail);  \
-        else merged = launch_feat_t<CH, DF, false>(s, grid_large, cv, ws, we, n_win, pl, P, small_path, block_lmax, r.block_threads, tail);     \
-    } while (0)
     bool merged = false;
-    if (r.motif) {
-        P.mp = *r.motif;
-        P.do_hist = 1;
-        // a 2bit image and k <= 13: the k-mer is cut out of one 4-byte load (its own instantiation: the general form's
-        // loops, unrolled with the window kernels, do not fit the instruction cache beside it)
-        if (P.mp.kind == FTK_REF_2BIT && P.mp.k <= 13 && P.is_any && P.ch_min <= 0 && P.ch_max >= (1 << 30)) FTK_FEAT(kMotifWord, false);
-        else FTK_FEAT(2, false);
-    } else if (ch && df) FTK_FEAT(1, true);
-    else if (ch) FTK_FEAT(1, false);
-    else if (df) FTK_FEAT(0, true);
-#undef FTK_FEAT
+    with_bools([&](auto BAM) {
+        constexpr bool kBam = BAM();
+        auto feat = [&](auto CH, auto DF) {
+            merged = launch_feat_t<CH(), DF(), kBam>(s, grid_large, cv, ws, we, n_win, pl, P, small_path, block_lmax,
+                                                    r.block_threads, tail);
+        };
+        if (r.motif) {
+            P.mp = *r.motif;
+            P.do_hist = 1;
+            // a 2bit image and k <= 13: the k-mer is cut out of one 4-byte load (its own instantiation: the general
+            // form's loops, unrolled with the window kernels, do not fit the instruction cache beside it)
+            if (P.mp.kind == FTK_REF_2BIT && P.mp.k <= 13 && P.is_any && P.ch_min <= 0 && P.ch_max >= (1 << 30))
+                feat(int_c<kMotifWord>{}, std::false_type{});
+            else feat(int_c<2>{}, std::false_type{});
+        } else if (ch && df) feat(int_c<1>{}, std::true_type{});
+        else if (ch) feat(int_c<1>{}, std::false_type{});
+        else if (df) feat(int_c<0>{}, std::true_type{});
+    }, bam);
     return merged;
 }
 
@@ -2204,55 +2205,24 @@ void gap_constants(const ftk_gaps& g, int out[4]) {
 
 void launch_window_features_batch(hipStream_t s, const FeatItem* d_items, int n_items, int total_win,
                                   const FeatureRequest& r, bool bam) {
-    FeatParams P{};
+    const FeatParams P = make_feat_params(r, false);
     const bool ch = r.cov_out || r.hist_out;
     const bool df = r.short_out != nullptr;
-    if (r.filter) {
-        const ftk_filter& f = *r.filter;
-        P.wp = make_win_pred(f);
-        P.ch_q = std::min(std::max(f.mapq_min, 0), 256);
-        P.ch_min = f.min_len < 0 ? 0 : std::min(f.min_len, 1 << 30);
-        P.ch_max = f.max_len < 0 ? (1 << 30) : std::min(f.max_len, 1 << 30);
-        P.is_any = f.policy == FTK_POLICY_ANY;
-    }
-    P.df_q = std::min(std::max(r.delfi_mapq_min, 0), 256);
-    P.do_cov = r.cov_out != nullptr;
-    P.do_hist = r.hist_out != nullptr;
-    P.len_lo = r.len_lo;
-    P.n_bins = r.n_bins;
-    P.cov_out = r.cov_out;
-    P.hist_out = r.hist_out;
-    P.over_out = r.over_out;
-    P.short_out = r.short_out;
-    P.long_out = r.long_out;
     const size_t lds1 = P.do_hist ? (size_t)(P.n_bins + 1) * sizeof(uint32_t) : 0;
     if (feat_fast_ok(P, ch, df)) {
-        FeatParams Pf = P;
-        if (!ch) Pf.ch_q = P.df_q;
-#define FTK_FASTB(CHK, HIST, DF)                                                                                   \
-    do {                                                                                                           \
-        if (bam) hipLaunchKernelGGL((feat_fast_batch_kernel<512, CHK, HIST, DF, true>), dim3(total_win), dim3(512), lds1, s, \
-                                    d_items, n_items, Pf);                                                         \
-        else hipLaunchKernelGGL((feat_fast_batch_kernel<512, CHK, HIST, DF, false>), dim3(total_win), dim3(512), lds1, s,    \
-                                d_items, n_items, Pf);                                                             \
-    } while (0)
-        if (ch && df) { if (P.do_hist) FTK_FASTB(true, true, true); else FTK_FASTB(true, false, true); }
-        else if (ch) { if (P.do_hist) FTK_FASTB(true, true, false); else FTK_FASTB(true, false, false); }
-        else if (df) FTK_FASTB(false, false, true);
-#undef FTK_FASTB
+        const FeatParams Pf = fast_params(P, ch);
+        with_bools([&](auto CHK, auto HIST, auto DF, auto BAM) {
+            if constexpr (CHK() || (DF() && !HIST()))  // coverage (with or without the histogram), DELFI, or both
+                hipLaunchKernelGGL((feat_fast_batch_kernel<512, CHK(), HIST(), DF(), BAM()>), dim3(total_win), dim3(512),
+                                   lds1, s, d_items, n_items, Pf);
+        }, ch, P.do_hist != 0, df, bam);
         return;
     }
-#define FTK_FEATB(CH, DF)                                                                                           \
-    do {                                                                                                            \
-        if (bam) hipLaunchKernelGGL((feat_batch_kernel<512, CH, DF, true>), dim3(total_win), dim3(512), lds1, s, d_items, \
-                                    n_items, P);                                                                    \
-        else hipLaunchKernelGGL((feat_batch_kernel<512, CH, DF, false>), dim3(total_win), dim3(512), lds1, s, d_items,   \
-                                n_items, P);                                                                        \
-    } while (0)
-    if (ch && df) FTK_FEATB(1, true);
-    else if (ch) FTK_FEATB(1, false);
-    else if (df) FTK_FEATB(0, true);
-#undef FTK_FEATB
+    with_bools([&](auto CHK, auto DF, auto BAM) {
+        if constexpr (CHK() || DF())
+            hipLaunchKernelGGL((feat_batch_kernel<512, CHK() ? 1 : 0, DF(), BAM()>), dim3(total_win), dim3(512), lds1, s,
+                               d_items, n_items, P);
+    }, ch, df, bam);
 }
 
 void launch_wps(hipStream_t s, const ContigView& cv, const WpsParams& p, int64_t n_tiles, const int64_t* iv_start,
@@ -2264,13 +2234,11 @@ void launch_wps(hipStream_t s, const ContigView& cv, const WpsParams& p, int64_t
     static const long long tpb_env = getenv("FTK_WPS_TPB") ? atoll(getenv("FTK_WPS_TPB")) : 0;
     const long long tpb = tpb_env > 0 ? tpb_env : 1;
     const long long grid = (n_tiles + tpb - 1) / tpb;
-#define FTK_WPS(MULTI, NT)                                                                                              \
-    hipLaunchKernelGGL((wps_stream_kernel<MULTI, false, false, NT>), dim3((unsigned)grid), dim3(256), 0, s, cv, p, iv_start, \
-                       iv_stop, out_off, tile_iv, tile_k, (long long)n_tiles, (int)tpb, out, (const WpsItem*)nullptr, 0,    \
-                       FusedParams{})
-    if (tpb == 1) { if (p.nt_store) FTK_WPS(false, true); else FTK_WPS(false, false); }
-    else { if (p.nt_store) FTK_WPS(true, true); else FTK_WPS(true, false); }
-#undef FTK_WPS
+    with_bools([&](auto MULTI, auto NT) {
+        hipLaunchKernelGGL((wps_stream_kernel<MULTI(), false, false, NT()>), dim3((unsigned)grid), dim3(256), 0, s, cv, p,
+                           iv_start, iv_stop, out_off, tile_iv, tile_k, (long long)n_tiles, (int)tpb, out,
+                           (const WpsItem*)nullptr, 0, FusedParams{});
+    }, tpb != 1, p.nt_store != 0);
 }
 
 // Whole-interval WPS with the window features of a regular bin tiling in the same pass.
@@ -2278,13 +2246,12 @@ void launch_wps_fused(hipStream_t s, const ContigView& cv, const WpsParams& p, i
                       int64_t* out) {
     if (n_tiles <= 0) return;
     const size_t lds = F.do_hist ? (size_t)(F.n_bins + 1) * 4 : 0;
-#define FTK_WPSF(NT)                                                                                               \
-    hipLaunchKernelGGL((wps_stream_kernel<false, false, true, NT>), dim3((unsigned)n_tiles), dim3(256), lds, s, cv, p, \
-                       (const int64_t*)nullptr, (const int64_t*)nullptr, (const int64_t*)nullptr,                      \
-                       (const int32_t*)nullptr, (const int32_t*)nullptr, (long long)n_tiles, 1, out,                   \
-                       (const WpsItem*)nullptr, 0, F)
-    if (p.nt_store) FTK_WPSF(true); else FTK_WPSF(false);
-#undef FTK_WPSF
+    with_bools([&](auto NT) {
+        hipLaunchKernelGGL((wps_stream_kernel<false, false, true, NT()>), dim3((unsigned)n_tiles), dim3(256), lds, s, cv, p,
+                           (const int64_t*)nullptr, (const int64_t*)nullptr, (const int64_t*)nullptr,
+                           (const int32_t*)nullptr, (const int32_t*)nullptr, (long long)n_tiles, 1, out,
+                           (const WpsItem*)nullptr, 0, F);
+    }, p.nt_store != 0);
 }
 
 // Several (contig, interval) items in one launch, one 4096-base tile per block.
@@ -2292,13 +2259,12 @@ void launch_wps_batch(hipStream_t s, const WpsParams& p, const WpsItem* d_items,
                       int64_t* out) {
     if (n_tiles <= 0) return;
     ContigView none{};
-#define FTK_WPSB(NT)                                                                                                \
-    hipLaunchKernelGGL((wps_stream_kernel<false, true, false, NT>), dim3((unsigned)n_tiles), dim3(256), 0, s, none, p,  \
-                       (const int64_t*)nullptr, (const int64_t*)nullptr, (const int64_t*)nullptr,                       \
-                       (const int32_t*)nullptr, (const int32_t*)nullptr, (long long)n_tiles, 1, out, d_items, n_items,  \
-                       FusedParams{})
-    if (p.nt_store) FTK_WPSB(true); else FTK_WPSB(false);
-#undef FTK_WPSB
+    with_bools([&](auto NT) {
+        hipLaunchKernelGGL((wps_stream_kernel<false, true, false, NT()>), dim3((unsigned)n_tiles), dim3(256), 0, s, none, p,
+                           (const int64_t*)nullptr, (const int64_t*)nullptr, (const int64_t*)nullptr,
+                           (const int32_t*)nullptr, (const int32_t*)nullptr, (long long)n_tiles, 1, out, d_items, n_items,
+                           FusedParams{});
+    }, p.nt_store != 0);
 }
 
 void launch_cleavage(hipStream_t s, const ContigView& cv, const CleaveParams& p, int64_t n_tiles,

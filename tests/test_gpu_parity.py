@@ -477,6 +477,75 @@ def test_batched_launches_equal_per_contig_calls(engine, data):
         engine.release(n)
 
 
+def test_batched_general_kernels_equal_per_contig_calls(engine):
+    """ftk_window_features_batch with requests the FAST kernels refuse -- length bounds, policy "any", two different
+    mapq cuts -- so that the general batch kernel (feat_batch_kernel) runs, and the FAST request as the control: every
+    output == the per-contig calls == the C oracle.  The first contig's windows: one with more than 16 x 512 candidates
+    (the 512-thread slab pipeline refills), one with fewer than 2 048 (one partial slab), an empty one, an inverted one
+    and one hanging over the contig start.  Tabix contigs for all four requests, BAM contigs (read1 columns) for the
+    first and the last."""
+    requests = dict(  # name -> (window filter, histogram?, DELFI mapq or None)
+        bounds=(dict(quality_threshold=30, min_length=120, max_length=200), True, 30),
+        any=(dict(quality_threshold=30, intersect_policy="any"), True, None),
+        two_cuts=(dict(quality_threshold=20), False, 30),
+        fast=(dict(quality_threshold=30), True, 30))
+    oracle_key = dict(quality_threshold="mapq_min", min_length="min_len", max_length="max_len", intersect_policy="policy")
+    rng = np.random.default_rng(23)
+    for bam in (False, True):
+        items, frs = [], []
+        # synth_contig's depth counts 300 bp per fragment: 70 gives the first contig its 14 000 fragments
+        for k, (size, depth) in enumerate(((60_000, 70.0), (20_000, 10.0))):
+            s, e, q, st = synth.synth_contig(size, depth=depth, seed=31 + k)
+            r1 = ()
+            if bam:  # read1 inside its fragment, as in the module's synBAM
+                rl = np.minimum(e - s, 100)
+                r1s = np.where(st == 1, s, e - rl).astype(np.int32)
+                r1 = (r1s, (r1s + rl).astype(np.int32))
+            name = f"gen{k}{'bam' if bam else ''}"
+            engine.load_contig(name, s, e, q, st, *r1)
+            frs.append(O.Frags(s, e, q, st, *r1))
+            if k == 0:
+                assert len(s) > 16 * 512 and np.searchsorted(s, 5_000 + 512) < 2_048
+                ws = np.array([0, 0, 1234, 40_000, -3_000], np.int32)
+                we = np.array([size, 5_000, 1234, 30_000, 2_000], np.int32)
+            else:
+                ws, we = synth.tiling_windows(size, 5_000)
+            bl_s = np.sort(rng.integers(0, size - 3_000, 6)).astype(np.int32)
+            bl_e = (bl_s + rng.integers(100, 2_500, 6)).astype(np.int32)
+            gaps = (size // 3, size // 3 + 4_000, [(0, 500), (size - 500, size)])
+            items.append(dict(name=name, starts=ws, stops=we, bl_start=bl_s, bl_end=bl_e, gaps=gaps))
+        for req in (("bounds", "fast") if bam else requests):
+            flt, with_hist, delfi_q = requests[req]
+            want = {}
+            for it, fr in zip(items, frs):  # the per-contig calls, each checked against the oracle
+                bl = dict(bl_start=it["bl_start"], bl_end=it["bl_end"], gaps=it["gaps"])
+                w = engine.window_features(it["name"], it["starts"], it["stops"], hist=(0, 601) if with_hist else None,
+                                           delfi=None if delfi_q is None else dict(quality_threshold=delfi_q, **bl), **flt)
+                oflt = {oracle_key[key]: v for key, v in flt.items()}
+                assert np.array_equal(w["coverage"], O.c_window_counts(fr, it["starts"], it["stops"], **oflt)), (bam, req)
+                if with_hist:
+                    h, o = O.c_fraglen_hist(fr, it["starts"], it["stops"], 0, 601, **oflt)
+                    assert np.array_equal(w["hist"], h) and np.array_equal(w["overflow"], o), (bam, req)
+                if delfi_q is not None:
+                    sh, lg, _ = O.c_delfi_counts(fr, it["starts"], it["stops"], delfi_q, it["bl_start"], it["bl_end"], it["gaps"])
+                    assert np.array_equal(w["short"], sh) and np.array_equal(w["long"], lg), (bam, req)
+                for key, v in w.items():
+                    want.setdefault(key, []).append(v)
+            batch = engine.feature_batch(items, **flt)
+            rows = batch["rows"]
+            out = dict(coverage=np.zeros(rows, np.int64))
+            if with_hist:
+                out.update(hist=np.zeros((rows, 601), np.uint32), hist_bins=(0, 601), overflow=np.zeros(rows, np.int64))
+            if delfi_q is not None:
+                out.update(delfi_q=delfi_q, short=np.zeros(rows, np.int64), long=np.zeros(rows, np.int64))
+            engine.window_features_batch(batch, **out)
+            assert set(want) == set(out) - {"hist_bins", "delfi_q"}, (bam, req)
+            for key, parts in want.items():
+                assert np.array_equal(out[key], np.concatenate(parts)), (bam, req, key)
+        for it in items:
+            engine.release(it["name"])
+
+
 @pytest.mark.parametrize("seed", [0, 1, 2, 3])
 def test_feature_fuzz_extreme_parameters(engine, data, seed):
     """Random filter / window / histogram parameters drawn from extreme values (open bounds, bounds beyond
