@@ -43,7 +43,7 @@ EXPORTS = [
     "ftk_ctx_set_stream", "ftk_ctx_sync", "ftk_timer_start", "ftk_timer_stop", "ftk_event_record",
     "ftk_event_elapsed_ms",
     "ftk_frags_from_host", "ftk_frags_from_device", "ftk_frags_set_read1", "ftk_frags_set_order", "ftk_frags_load_fraggz", "ftk_frags_load_bam", "ftk_frags_name",
-    "ftk_frags_info", "ftk_frags_release",
+    "ftk_frags_info", "ftk_frags_packed", "ftk_frags_release",
     "ftk_fragfile_decode", "ftk_bam_decode", "ftk_host_alloc", "ftk_host_alloc_pageable", "ftk_host_free", "ftk_cache_trim", "ftk_wps_async", "ftk_result_wait", "ftk_fragfile_index_contigs", "ftk_fragstream_open", "ftk_fragstream_open_device", "ftk_fragstream_open_region", "ftk_fragtable_is_device", "ftk_fragtable_ready_event", "ftk_fragtable_columns_to_host", "ftk_fragtable_read1_to_host", "ftk_fragstream_next", "ftk_fragstream_n_refs",
     "ftk_fragstream_ref_name", "ftk_fragstream_ref_length", "ftk_fragstream_close", "ftk_fragstream_stage_ms", "ftk_fragstream_skipped", "ftk_fragtable_skipped", "ftk_fragtable_error", "ftk_fragtable_is_bed6",
     "ftk_fragtable_n_contigs", "ftk_fragtable_contig_name", "ftk_fragtable_contig_length",
@@ -245,6 +245,7 @@ def load() -> C.CDLL:
     lib.ftk_frags_name.argtypes = [vp, C.c_int]
     lib.ftk_frags_name.restype = C.c_char_p
     lib.ftk_frags_info.argtypes = [vp, C.c_int, C.POINTER(i64), C.POINTER(i32), C.POINTER(i32)]
+    lib.ftk_frags_packed.argtypes = [vp, C.c_int, C.POINTER(i32), C.POINTER(i32), C.POINTER(i64)]
     lib.ftk_frags_release.argtypes = [vp, C.c_int]
     lib.ftk_fragfile_decode.argtypes = [C.c_char_p, C.c_char_p, C.c_int, C.POINTER(vp)]
     lib.ftk_bam_decode.argtypes = [C.c_char_p, C.c_char_p, C.c_int, C.POINTER(vp)]

@@ -259,15 +259,17 @@ int upload_common(ftk_ctx* ctx, int contig_id, const int32_t* start, const int32
     // leave the allocation
     size_t n_pad = ((size_t)n + 3) / 4 * 4 + 4;
     size_t b_i32 = align_up(n_pad * 4), b_u8 = align_up(n_pad);
-    size_t total = 2 * b_i32 + 2 * b_u8;
+    // the packed (length, mapq) words sit behind the four columns: the stats kernel below writes them, padding included
+    size_t wide = 2 * b_i32 + 2 * b_u8, total = wide + align_up(n_pad * 2);
     HIPCHK(ctx, hipMalloc(&c.base, total));
     char* base = (char*)c.base;
     int32_t* d_start = (int32_t*)base;
     int32_t* d_end = (int32_t*)(base + b_i32);
     uint8_t* d_mapq = (uint8_t*)(base + 2 * b_i32);
     uint8_t* d_strand = (uint8_t*)(base + 2 * b_i32 + b_u8);
+    uint16_t* d_lq = (uint16_t*)(base + wide);
     hipStream_t s = ctx->stream;
-    hipError_t e = hipMemsetAsync(c.base, 0, total, s);
+    hipError_t e = hipMemsetAsync(c.base, 0, wide, s);
     // padding fragments sit at 2^30, beyond every coordinate: no window test accepts them, so the
     // feature kernels process whole groups of four without bounds checks
     if (e == hipSuccess) e = hipMemsetD32Async((hipDeviceptr_t)(d_start + n), kPadCoord, n_pad - (size_t)n, s);
@@ -291,7 +293,7 @@ int upload_common(ftk_ctx* ctx, int contig_id, const int32_t* start, const int32
     if (!ctx->d_stats) e = hipMalloc(&ctx->d_stats, sizeof(FragStats));
     FragStats* d_st = (FragStats*)ctx->d_stats;
     if (e == hipSuccess) e = hipMemcpyAsync(d_st, &init, sizeof(init), hipMemcpyHostToDevice, s);
-    if (e == hipSuccess && n > 0) launch_stats(s, d_start, d_end, (int)n, d_st);
+    if (e == hipSuccess) launch_stats(s, d_start, d_end, d_mapq, d_lq, (int)n, (int)n_pad, d_st);  // (n = 0: the padding words alone)
     if (e == hipSuccess) e = hipMemcpyAsync(&h_st, d_st, sizeof(h_st), hipMemcpyDeviceToHost, s);
     // the last start (the largest: the columns are sorted) for the position index below - on the ctx stream with the
     // summary: a synchronous hipMemcpy here waited for whatever transfer the device had in flight, 7-29 ms per contig
@@ -337,6 +339,10 @@ int upload_common(ftk_ctx* ctx, int contig_id, const int32_t* start, const int32
     c.v.end = d_end;
     c.v.mapq = d_mapq;
     c.v.strand = d_strand;
+    // the packed column holds every fragment exactly when none is longer than kLqLenMax (0 <= len and 0 <= start were
+    // checked above); otherwise it stays unused and every kernel reads end and mapq
+    c.v.lq = c.max_len <= kLqLenMax ? d_lq : nullptr;
+    c.v.lq_len_max = kLqLenMax;
     c.v.r1_start = nullptr;
     c.v.r1_end = nullptr;
     c.v.order = nullptr;
@@ -714,6 +720,7 @@ int ftk_frags_set_read1(ftk_ctx* ctx, int contig_id, const int32_t* r1_start, co
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     c->v.r1_start = c->r1;
     c->v.r1_end = (int32_t*)((char*)c->r1 + b);
+    c->v.lq = nullptr;  // a contig with read1 columns keeps the wide kernels (their BAM forms have no packed variant)
     static const bool r1_always = getenv("FTK_R1_ALWAYS") && atoi(getenv("FTK_R1_ALWAYS")) != 0;  // tests: both code paths
     c->v.r1_inside = (bad == 0 && !r1_always) ? 1 : 0;
     return FTK_OK;
@@ -727,6 +734,17 @@ int ftk_frags_info(ftk_ctx* ctx, int contig_id, int64_t* n_out, int32_t* max_len
     if (n_out) *n_out = c->n;
     if (max_len_out) *max_len_out = c->max_len;
     if (max_end_out) *max_end_out = c->max_end;
+    return FTK_OK;
+}
+
+int ftk_frags_packed(ftk_ctx* ctx, int contig_id, int32_t* present_out, int32_t* len_max_out, int64_t* launches_out) {
+    if (!ctx) return fail(nullptr, FTK_ERR_INVALID, "ctx is NULL");
+    ContigData* c;
+    int rc = get_contig(ctx, contig_id, &c);
+    if (rc) return rc;
+    if (present_out) *present_out = c->v.lq != nullptr;
+    if (len_max_out) *len_max_out = c->v.lq_len_max;
+    if (launches_out) *launches_out = packed_launches();
     return FTK_OK;
 }
 

@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "ftk.h"
+#include "ftk_packed.h"
 
 namespace ftk {
 
@@ -23,11 +24,16 @@ constexpr int kPadCoord = 1 << 30;
 // Positions per WPS tile.
 constexpr int kWpsTile = 4096;
 
-// One contig's fragments, resident in HBM (start-sorted SoA, 10 B / fragment).
+// One contig's fragments, resident in HBM (start-sorted SoA, 10 B / fragment, + 2 B for the packed word).
+// lq: the packed (length, mapq) column, built with the load-time statistics (stats_kernel) and read INSTEAD of end and
+// mapq by the PACKED forms of the FAST feature blocks and the WPS tiles (6 B per fragment instead of 9).  Present only
+// when every fragment has 0 <= len <= lq_len_max and start >= 0, and the contig has no read1 columns; else nullptr and
+// every kernel reads the wide columns.  The word and which calls may use it: ftk_packed.h (packed_call_ok).
 struct ContigView {
     const int32_t* start;
     const int32_t* end;
     const uint8_t* mapq;
+    const uint16_t* lq;       // packed (length, mapq) words, or nullptr
     const uint8_t* strand;
     const int32_t* r1_start;  // BAM only (else nullptr)
     const int32_t* r1_end;
@@ -36,6 +42,7 @@ struct ContigView {
     int32_t n;                // fragments
     int32_t n_bins;
     int32_t max_len;          // longest fragment in the contig
+    int32_t lq_len_max;       // longest length lq can hold (kLqLenMax)
     // BAM: 1 when every fragment holds its read1 span (start <= r1_start < r1_end <= end; checked on the device by
     // ftk_frags_set_read1).  A fragment that lies inside a window then has its read1 inside it too, so the read1
     // fetch test (io/alignment.py:245) can only fail for fragments that cross a window bound and the kernels read

@@ -42,7 +42,13 @@ struct CleaveParams {
     int lmax;  // longest admissible fragment
 };
 
-void launch_stats(hipStream_t s, const int32_t* start, const int32_t* end, int n, FragStats* st);
+// lq (may be NULL): also writes the contig's packed (length, mapq) column (ContigView::lq), n_pad words of it (the ones
+// behind the n fragments are cleared)
+void launch_stats(hipStream_t s, const int32_t* start, const int32_t* end, const uint8_t* mapq, uint16_t* lq, int n,
+                  int n_pad, FragStats* st);
+// Calls that read the packed column instead of end / mapq so far in this process (a debug counter: tests tell the two
+// paths apart with it).
+long long packed_launches();
 void launch_bin_index(hipStream_t s, const int32_t* start, int n, int n_bins, int32_t* idx);
 // *bad |= 1 when some fragment does not hold its read1 span (ContigView::r1_inside)
 void launch_r1_inside(hipStream_t s, const int32_t* start, const int32_t* end, const int32_t* r1s, const int32_t* r1e,

@@ -17,6 +17,7 @@
 #include <cstdlib>
 
 #include <algorithm>
+#include <atomic>
 #include <type_traits>
 
 namespace ftk {
@@ -52,14 +53,26 @@ __device__ __forceinline__ int last_at_or_below(int n, Pred&& at_or_below) {
 // decoder's inflate waves hold five of a SIMD's wave slots and 410 of its 512 VGPRs on every CU - a 1 024-thread block
 // (four waves per SIMD at 68 VGPRs) could only start where inflate waves had retired and the kernel took 1.1-1.4 ms
 // beside them against 22 us alone (profiles/r4_a_genome_leg_kernel_stats.txt); one wave per SIMD fits at once.
+// lq (may be null): the contig's packed (length, mapq) column, written here because this pass holds every start and end
+// already - one more byte read and one 2-byte store per fragment, no pass of its own.  The words are written before the
+// summary is known; the host keeps the column only when the summary allows it (upload_common).  The words of the
+// padding fragments [n, n_pad) are cleared here too (length 0, mapq 0), which saves the load a fill launch.
 constexpr int kStatsThreads = 256;
-__global__ __launch_bounds__(kStatsThreads) void stats_kernel(const int32_t* start, const int32_t* end, int n, FragStats* st) {
+__global__ __launch_bounds__(kStatsThreads) void stats_kernel(const int32_t* start, const int32_t* end,
+                                                              const uint8_t* __restrict__ mapq,
+                                                              uint16_t* __restrict__ lq, int n, int n_pad,
+                                                              FragStats* st) {
     __shared__ int red[5][kStatsThreads / 64];
     int unsorted = 0, max_len = INT32_MIN, min_len = INT32_MAX, max_end = INT32_MIN, min_start = INT32_MAX;
-    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n_pad; i += gridDim.x * blockDim.x) {
+        if (i >= n) {
+            lq[i] = 0;
+            continue;
+        }
         int s = start[i], e = end[i];
         if (i > 0 && start[i - 1] > s) unsorted = 1;
         int len = e - s;
+        if (lq) lq[i] = (uint16_t)(min(max(len, 0), kLqLenSat) << kLqBits | min((int)mapq[i], kLqMapqSat));
         max_len = max(max_len, len);
         min_len = min(min_len, len);
         max_end = max(max_end, e);
@@ -1078,41 +1091,65 @@ __device__ __forceinline__ void fast_group(const ContigView& cv, const FeatParam
     for (int j = 0; j < 4; ++j) fast_element<CHK, HIST, DF, BL, GAPS>(P, fs[j], fe[j], x[j], o0, o1, h, a);
 }
 
-template <int kFeatBS, bool CHK, bool HIST, bool DF, bool BL, bool GAPS, bool BAM>
+// Four fragments in flight: their starts, ends and mapqs (36 B, three loads), or - PACKED - their starts and their four
+// packed (length, mapq) words (24 B, two loads; ContigView::lq).  get() hands out what fast_group takes either way:
+// end = start + (lq >> kLqBits), mapq = lq & kLqMapqSat (saturated: packed_call_ok admits no threshold above it).
+template <bool PACKED>
+struct FastSlab {
+    int4 s, e;
+    uchar4 q;
+    __device__ __forceinline__ void load(const ContigView& cv, int i) {
+        s = *reinterpret_cast<const int4*>(cv.start + i);
+        e = *reinterpret_cast<const int4*>(cv.end + i);
+        q = *reinterpret_cast<const uchar4*>(cv.mapq + i);
+    }
+    __device__ __forceinline__ void get(int4& s_, int4& e_, uchar4& q_) const { s_ = s; e_ = e; q_ = q; }
+};
+template <>
+struct FastSlab<true> {
+    int4 s;
+    uint2 l;  // lq[i .. i + 3]
+    __device__ __forceinline__ void load(const ContigView& cv, int i) {
+        s = *reinterpret_cast<const int4*>(cv.start + i);
+        l = *reinterpret_cast<const uint2*>(cv.lq + i);
+    }
+    __device__ __forceinline__ void get(int4& s_, int4& e_, uchar4& q_) const {
+        const unsigned w[4] = {l.x & 0xffffu, l.x >> 16, l.y & 0xffffu, l.y >> 16};
+        s_ = s;
+        e_ = make_int4(s.x + (int)(w[0] >> kLqBits), s.y + (int)(w[1] >> kLqBits), s.z + (int)(w[2] >> kLqBits),
+                       s.w + (int)(w[3] >> kLqBits));
+        q_ = make_uchar4(w[0] & kLqMapqSat, w[1] & kLqMapqSat, w[2] & kLqMapqSat, w[3] & kLqMapqSat);
+    }
+};
+
+template <int kFeatBS, bool CHK, bool HIST, bool DF, bool BL, bool GAPS, bool BAM, bool PACKED>
 __device__ __forceinline__ void fast_stream(const ContigView& cv, const FeatParams& P, int lo, int hi, int tid,
                                             const FastWin& W, int o0, int o1, uint32_t* h, FastAcc& a) {
-    int4 s4[4], e4[4];
-    uchar4 q4[4];
+    static_assert(!(PACKED && BAM), "a contig with read1 columns has no packed column");
+    FastSlab<PACKED> slab[4];
     const int i0 = lo + 4 * tid;
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
         const int i = i0 + u * (4 * kFeatBS);
-        if (i < hi) {
-            s4[u] = *reinterpret_cast<const int4*>(cv.start + i);
-            e4[u] = *reinterpret_cast<const int4*>(cv.end + i);
-            q4[u] = *reinterpret_cast<const uchar4*>(cv.mapq + i);
-        }
+        if (i < hi) slab[u].load(cv, i);
     }
     for (int base = i0; base < hi; base += 16 * kFeatBS) {
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
             const int i = base + u * (4 * kFeatBS);
             if (i < hi) {
-                const int4 s = s4[u], e = e4[u];
-                const uchar4 q = q4[u];
+                int4 s, e;
+                uchar4 q;
+                slab[u].get(s, e, q);
                 const int nxt = i + 16 * kFeatBS;
-                if (nxt < hi) {
-                    s4[u] = *reinterpret_cast<const int4*>(cv.start + nxt);
-                    e4[u] = *reinterpret_cast<const int4*>(cv.end + nxt);
-                    q4[u] = *reinterpret_cast<const uchar4*>(cv.mapq + nxt);
-                }
+                if (nxt < hi) slab[u].load(cv, nxt);
                 fast_group<CHK, HIST, DF, BL, GAPS, BAM>(cv, P, i, s, e, q, W, o0, o1, h, a);
             }
         }
     }
 }
 
-template <int kFeatBS, bool CHK, bool HIST, bool DF, bool BAM>
+template <int kFeatBS, bool CHK, bool HIST, bool DF, bool BAM, bool PACKED = false>
 __device__ __forceinline__ void feat_fast_body(const ContigView& cv, int ws_raw, int we_raw, int lmax,
                                                const FeatParams& P, int o0, int o1, size_t row, uint32_t* lds_hist,
                                                int (*red)[kFeatBS / 64]) {
@@ -1145,11 +1182,11 @@ __device__ __forceinline__ void feat_fast_body(const ContigView& cv, int ws_raw,
     FastAcc a;
     const bool bl = DF && o1 > o0;
     if (bl) {
-        if (gaps) fast_stream<kFeatBS, CHK, HIST, DF, true, true, BAM>(cv, P, lo, hi, tid, W, o0, o1, lds_hist, a);
-        else fast_stream<kFeatBS, CHK, HIST, DF, true, false, BAM>(cv, P, lo, hi, tid, W, o0, o1, lds_hist, a);
+        if (gaps) fast_stream<kFeatBS, CHK, HIST, DF, true, true, BAM, PACKED>(cv, P, lo, hi, tid, W, o0, o1, lds_hist, a);
+        else fast_stream<kFeatBS, CHK, HIST, DF, true, false, BAM, PACKED>(cv, P, lo, hi, tid, W, o0, o1, lds_hist, a);
     } else {
-        if (gaps) fast_stream<kFeatBS, CHK, HIST, DF, false, true, BAM>(cv, P, lo, hi, tid, W, o0, o1, lds_hist, a);
-        else fast_stream<kFeatBS, CHK, HIST, DF, false, false, BAM>(cv, P, lo, hi, tid, W, o0, o1, lds_hist, a);
+        if (gaps) fast_stream<kFeatBS, CHK, HIST, DF, false, true, BAM, PACKED>(cv, P, lo, hi, tid, W, o0, o1, lds_hist, a);
+        else fast_stream<kFeatBS, CHK, HIST, DF, false, false, BAM, PACKED>(cv, P, lo, hi, tid, W, o0, o1, lds_hist, a);
     }
     if (HIST) {
         __syncthreads();
@@ -1173,7 +1210,7 @@ __device__ __forceinline__ void feat_fast_body(const ContigView& cv, int ws_raw,
     }
 }
 
-template <int kFeatBS, bool CHK, bool HIST, bool DF, bool BAM>
+template <int kFeatBS, bool CHK, bool HIST, bool DF, bool BAM, bool PACKED>
 __global__ __launch_bounds__(kFeatBS) void feat_fast_kernel(ContigView cv, const int32_t* ws_, const int32_t* we_,
                                                         int n_win, int lmax, FeatParams P) {
     extern __shared__ uint32_t lds_hist[];
@@ -1181,7 +1218,7 @@ __global__ __launch_bounds__(kFeatBS) void feat_fast_kernel(ContigView cv, const
     const int w = blockIdx.x;
     int o0, o1;
     blacklist_range<DF>(P.dp.bl_off, w, o0, o1);
-    feat_fast_body<kFeatBS, CHK, HIST, DF, BAM>(cv, ws_[w], we_[w], lmax, P, o0, o1, (size_t)w, lds_hist, red);
+    feat_fast_body<kFeatBS, CHK, HIST, DF, BAM, PACKED>(cv, ws_[w], we_[w], lmax, P, o0, o1, (size_t)w, lds_hist, red);
 }
 
 // The block kernels for the windows of SEVERAL contigs in one launch (ftk_window_features_batch): block b owns
@@ -1273,12 +1310,16 @@ constexpr int kWpsPrefetch = 4;  // fragments per thread held in registers for t
 // `if (p.nt_store) nt-store else store` the two branches differ only in the !nontemporal metadata, and the optimiser
 // may sink them into ONE plain store (it did once this body became a device function: WPS 175 -> 197 us per launch,
 // the feature pass behind it 37 -> 53 us).
-template <bool MULTI, bool BATCH, bool FUSED, bool NT>
+// PACKED: the tile reads start and the packed (length, mapq) word of its candidates (ContigView::lq, 6 B per fragment
+// instead of 9); the word travels in the register that holds `end` otherwise and is unpacked where the fragment is
+// applied.  Single-contig, unfused tiles, one per block, only (the launches launch_wps and launch_feat_t make with it).
+template <bool MULTI, bool BATCH, bool FUSED, bool PACKED, bool NT>
 __device__ __forceinline__ void wps_block(const unsigned block_id, const unsigned n_blocks, ContigView cv, WpsParams p,
                                           const int64_t* iv_start_, const int64_t* iv_stop_, const int64_t* out_off_,
                                           const int32_t* tile_iv, const int32_t* tile_k, long long n_tiles,
                                           int tiles_per_block, int64_t* __restrict__ out,
                                           const WpsItem* __restrict__ items, int n_items, const FusedParams& F) {
+    static_assert(!(PACKED && (MULTI || BATCH || FUSED)), "the packed column serves one single-contig, unfused tile per block");
     constexpr int T = kWpsTile, NP = T / 1024, PF = kWpsPrefetch;
     extern __shared__ uint32_t fhist[];  // FUSED with a histogram: n_bins + 1 counters of the tile's first bin
     __shared__ int fcnt[4];              // FUSED: rejected (coverage, short, long) and processed fragments
@@ -1360,6 +1401,25 @@ __device__ __forceinline__ void wps_block(const unsigned block_id, const unsigne
         if (e < 0) atomicAdd(&pre_s[par], 1); else if (e < T) atomicAdd(&d[e], 1);
     };
 
+    // fragment i's registers: start; end - PACKED: its lq word; mapq - PACKED: unused (ok = false: an empty slot)
+    auto fetch = [&](int i, bool ok, int& fs, int& fe, int& q) {
+        fs = ok ? cv.start[i] : 0;
+        if (PACKED) {
+            fe = ok ? (int)cv.lq[i] : 0;
+            q = 0;
+        } else {
+            fe = ok ? cv.end[i] : 0;
+            q = ok ? (int)cv.mapq[i] : -1;
+        }
+    };
+    // PACKED: end and (saturated) mapq from the word
+    auto unpack = [&](int fs, int& fe, int& q) {
+        if (PACKED) {
+            q = fe & kLqMapqSat;
+            fe = fs + (fe >> kLqBits);
+        }
+    };
+
     // ---- FUSED: window features of the fragments that start in this tile -------------------------
     int f_w0 = 0, f_b1 = 0;              // first bin of the tile, start of the next bin
     int f_n = 0, f_cov = 0, f_sh = 0, f_lg = 0;  // processed / rejected counters of bin f_w0 (registers)
@@ -1438,10 +1498,7 @@ __device__ __forceinline__ void wps_block(const unsigned block_id, const unsigne
 #pragma unroll
     for (int k = 0; k < PF; ++k) {
         const int i = lo + tid + 256 * k;
-        const bool ok = i < hi;
-        pfs[k] = ok ? cv.start[i] : 0;
-        pfe[k] = ok ? cv.end[i] : 0;
-        pfq[k] = ok ? (int)cv.mapq[i] : -1;
+        fetch(i, i < hi, pfs[k], pfe[k], pfq[k]);
     }
 
     const int odd = p.odd, kk = p.hl;  // odd W: hl == k
@@ -1459,12 +1516,16 @@ __device__ __forceinline__ void wps_block(const unsigned block_id, const unsigne
         for (int k = 0; k < PF; ++k) {
             const int i = lo + tid + 256 * k;
             if (i < hi) {
-                apply(cur, par, i, pfs[k], pfe[k], pfq[k]);
-                if (FUSED) feature(cur.t0, cur.len_t, i, pfs[k], pfe[k], pfq[k]);
+                int fe = pfe[k], q = pfq[k];
+                unpack(pfs[k], fe, q);
+                apply(cur, par, i, pfs[k], fe, q);
+                if (FUSED) feature(cur.t0, cur.len_t, i, pfs[k], fe, q);
             }
         }
         for (int i = lo + PF * 256 + tid; i < hi; i += 256) {
-            const int fs = cv.start[i], fe = cv.end[i], q = cv.mapq[i];
+            int fs, fe, q;
+            fetch(i, true, fs, fe, q);
+            unpack(fs, fe, q);
             apply(cur, par, i, fs, fe, q);
             if (FUSED) feature(cur.t0, cur.len_t, i, fs, fe, q);
         }
@@ -1522,10 +1583,7 @@ __device__ __forceinline__ void wps_block(const unsigned block_id, const unsigne
 #pragma unroll
         for (int k = 0; k < PF; ++k) {
             const int i = lo2 + tid + 256 * k;
-            const bool ok = MULTI && i < hi2;
-            nfs[k] = ok ? cv.start[i] : 0;
-            nfe[k] = ok ? cv.end[i] : 0;
-            nfq[k] = ok ? (int)cv.mapq[i] : -1;
+            fetch(i, MULTI && i < hi2, nfs[k], nfe[k], nfq[k]);
         }
         // ---- scores -------------------------------------------------------------------
         int64_t* dst = out + cur.out_base;
@@ -1572,7 +1630,7 @@ __device__ __forceinline__ void wps_block(const unsigned block_id, const unsigne
     }
 }
 
-template <bool MULTI, bool BATCH, bool FUSED, bool NT>
+template <bool MULTI, bool BATCH, bool FUSED, bool PACKED, bool NT>
 __global__ __launch_bounds__(256) void wps_stream_kernel(ContigView cv, WpsParams p, const int64_t* iv_start_,
                                                          const int64_t* iv_stop_, const int64_t* out_off_,
                                                          const int32_t* tile_iv, const int32_t* tile_k,
@@ -1580,7 +1638,7 @@ __global__ __launch_bounds__(256) void wps_stream_kernel(ContigView cv, WpsParam
                                                          int64_t* __restrict__ out,
                                                          const WpsItem* __restrict__ items, int n_items,
                                                          FusedParams F) {
-    wps_block<MULTI, BATCH, FUSED, NT>(blockIdx.x, gridDim.x, cv, p, iv_start_, iv_stop_, out_off_, tile_iv, tile_k, n_tiles,
+    wps_block<MULTI, BATCH, FUSED, PACKED, NT>(blockIdx.x, gridDim.x, cv, p, iv_start_, iv_stop_, out_off_, tile_iv, tile_k, n_tiles,
                                    tiles_per_block, out, items, n_items, F);
 }
 
@@ -1590,7 +1648,7 @@ __global__ __launch_bounds__(256) void wps_stream_kernel(ContigView cv, WpsParam
 // retire (the feature pass's tail and the WPS ramp overlap instead of adding up), and WPS finds the contig's
 // columns in the Infinity Cache behind the feature blocks that just read them.  The two kinds of block share
 // nothing: results are those of the two separate launches.
-template <bool CHK, bool HIST, bool DF, bool BAM, bool NT>
+template <bool CHK, bool HIST, bool DF, bool BAM, bool PACKED, bool NT>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5, 5))) void feat_then_wps_kernel(ContigView cv, const int32_t* ws_, const int32_t* we_,
                                                             int n_win, int lmax, FeatParams P, WpsParams p,
                                                             long long n_tiles, int64_t* __restrict__ out) {
@@ -1600,10 +1658,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5, 5))) voi
         const int w = blockIdx.x;
         int o0, o1;
         blacklist_range<DF>(P.dp.bl_off, w, o0, o1);
-        feat_fast_body<256, CHK, HIST, DF, BAM>(cv, ws_[w], we_[w], lmax, P, o0, o1, (size_t)w, lds_hist, red);
+        feat_fast_body<256, CHK, HIST, DF, BAM, PACKED>(cv, ws_[w], we_[w], lmax, P, o0, o1, (size_t)w, lds_hist, red);
         return;
     }
-    wps_block<false, false, false, NT>(blockIdx.x - (unsigned)n_win, gridDim.x - (unsigned)n_win, cv, p, nullptr, nullptr,
+    wps_block<false, false, false, PACKED, NT>(blockIdx.x - (unsigned)n_win, gridDim.x - (unsigned)n_win, cv, p, nullptr, nullptr,
                                    nullptr, nullptr, nullptr, n_tiles, 1, out, nullptr, 0, FusedParams{});
 }
 
@@ -2006,9 +2064,11 @@ void launch_window_stats(hipStream_t s, const uint32_t* hist, int n_win, int n_b
     hipLaunchKernelGGL(window_stats_kernel, dim3((n_win + 3) / 4), dim3(256), 0, s, hist, n_win, n_bins, len_lo, short_cut, out);
 }
 
-void launch_stats(hipStream_t s, const int32_t* start, const int32_t* end, int n, FragStats* st) {
-    int blocks = min(1024, max(1, (n + kStatsThreads - 1) / kStatsThreads));
-    hipLaunchKernelGGL(stats_kernel, dim3(blocks), dim3(kStatsThreads), 0, s, start, end, n, st);
+void launch_stats(hipStream_t s, const int32_t* start, const int32_t* end, const uint8_t* mapq, uint16_t* lq, int n,
+                  int n_pad, FragStats* st) {
+    if (!lq) n_pad = n;
+    int blocks = min(1024, max(1, (n_pad + kStatsThreads - 1) / kStatsThreads));
+    hipLaunchKernelGGL(stats_kernel, dim3(blocks), dim3(kStatsThreads), 0, s, start, end, mapq, lq, n, n_pad, st);
 }
 
 void launch_bin_index(hipStream_t s, const int32_t* start, int n, int n_bins, int32_t* idx) {
@@ -2104,6 +2164,41 @@ static FeatParams fast_params(FeatParams P, bool ch) {
     return P;
 }
 
+// ---- the packed (length, mapq) column: which launches read it (the rule itself: packed_call_ok, ftk_packed.h) ----
+static std::atomic<long long> g_packed_launches{0};
+long long packed_launches() { return g_packed_launches.load(std::memory_order_relaxed); }
+
+// FTK_PACKED=0 keeps every launch on the wide columns (tests run both).
+static bool packed_allowed() {
+    static const int allow = getenv("FTK_PACKED") ? atoi(getenv("FTK_PACKED")) : 1;
+    return allow != 0;
+}
+
+// The comparisons of a FAST feature launch (P: what the kernel receives, fast_params) and / or a WPS launch.  (A contig
+// with read1 columns has no column: ftk_frags_set_read1 drops it.)
+static bool use_packed(const ContigView& cv, const FeatParams* P, bool hist, const WpsParams* w) {
+    if (!packed_allowed()) return false;
+    PackedCall c;
+    c.has_lq = cv.lq != nullptr;
+    if (P) {
+        c.feat = true;
+        c.feat_q = P->ch_q;  // the one mapq cut of the FAST kernels (coverage's, or DELFI's when it runs alone)
+        // feat_fast_ok admits no length bounds on the coverage / histogram filter: [0, 2^30]
+        c.hist = hist;
+        c.len_lo = P->len_lo;
+        c.n_bins = P->n_bins;
+    }
+    if (w) {
+        c.wps = true;
+        c.wps_q = w->mapq_min;
+        c.wps_min = w->min_len;
+        c.wps_max = w->max_len;
+    }
+    return packed_call_ok(c);
+}
+// beside every launch of a PACKED instantiation: the debug counter behind packed_launches()
+static void count_packed_launch() { g_packed_launches.fetch_add(1, std::memory_order_relaxed); }
+
 template <int CH, bool DF, bool BAM>
 static bool launch_feat_t(hipStream_t s, int grid_large, const ContigView& cv, const int32_t* ws, const int32_t* we,
                           int n_win, const WindowPlan& pl, const FeatParams& P, bool small_path, int block_lmax,
@@ -2115,20 +2210,27 @@ static bool launch_feat_t(hipStream_t s, int grid_large, const ContigView& cv, c
         if (tail && tail->n_tiles > 0 && (long long)n_win + tail->n_tiles < (1LL << 31)) {
             // the merged launch: feature blocks first, the WPS tiles behind them (feat_then_wps_kernel)
             const dim3 grid((unsigned)((long long)n_win + tail->n_tiles));
-            with_bools([&](auto HIST, auto NT) {
-                hipLaunchKernelGGL((feat_then_wps_kernel<CH != 0, HIST(), DF, BAM, NT()>), grid, dim3(256), lds1, s, cv, ws,
-                                   we, n_win, block_lmax, Pf, tail->p, (long long)tail->n_tiles, tail->out);
-            }, hist, tail->p.nt_store != 0);
+            with_bools([&](auto HIST, auto PACKED, auto NT) {
+                if constexpr (!(BAM && PACKED())) {
+                    hipLaunchKernelGGL((feat_then_wps_kernel<CH != 0, HIST(), DF, BAM, PACKED(), NT()>), grid, dim3(256),
+                                       lds1, s, cv, ws, we, n_win, block_lmax, Pf, tail->p, (long long)tail->n_tiles,
+                                       tail->out);
+                    if constexpr (PACKED()) count_packed_launch();
+                }
+            }, hist, !BAM && use_packed(cv, &Pf, hist, &tail->p), tail->p.nt_store != 0);
             return true;
         }
-        with_bools([&](auto HIST) {
-            if (block_threads >= 512)
-                hipLaunchKernelGGL((feat_fast_kernel<512, CH != 0, HIST(), DF, BAM>), dim3(n_win), dim3(512), lds1, s, cv,
-                                   ws, we, n_win, block_lmax, Pf);
-            else
-                hipLaunchKernelGGL((feat_fast_kernel<256, CH != 0, HIST(), DF, BAM>), dim3(n_win), dim3(256), lds1, s, cv,
-                                   ws, we, n_win, block_lmax, Pf);
-        }, hist);
+        with_bools([&](auto HIST, auto PACKED) {
+            if constexpr (!(BAM && PACKED())) {
+                if (block_threads >= 512)
+                    hipLaunchKernelGGL((feat_fast_kernel<512, CH != 0, HIST(), DF, BAM, PACKED()>), dim3(n_win), dim3(512),
+                                       lds1, s, cv, ws, we, n_win, block_lmax, Pf);
+                else
+                    hipLaunchKernelGGL((feat_fast_kernel<256, CH != 0, HIST(), DF, BAM, PACKED()>), dim3(n_win), dim3(256),
+                                       lds1, s, cv, ws, we, n_win, block_lmax, Pf);
+                if constexpr (PACKED()) count_packed_launch();
+            }
+        }, hist, !BAM && use_packed(cv, &Pf, hist, nullptr));
         return false;
     }
     if (block_lmax >= 0) {
@@ -2234,11 +2336,15 @@ void launch_wps(hipStream_t s, const ContigView& cv, const WpsParams& p, int64_t
     static const long long tpb_env = getenv("FTK_WPS_TPB") ? atoll(getenv("FTK_WPS_TPB")) : 0;
     const long long tpb = tpb_env > 0 ? tpb_env : 1;
     const long long grid = (n_tiles + tpb - 1) / tpb;
-    with_bools([&](auto MULTI, auto NT) {
-        hipLaunchKernelGGL((wps_stream_kernel<MULTI(), false, false, NT()>), dim3((unsigned)grid), dim3(256), 0, s, cv, p,
-                           iv_start, iv_stop, out_off, tile_iv, tile_k, (long long)n_tiles, (int)tpb, out,
-                           (const WpsItem*)nullptr, 0, FusedParams{});
-    }, tpb != 1, p.nt_store != 0);
+    // the packed column serves the one-tile-per-block form (the default; FTK_WPS_TPB is an experiment switch)
+    with_bools([&](auto MULTI, auto PACKED, auto NT) {
+        if constexpr (!(MULTI() && PACKED())) {
+            hipLaunchKernelGGL((wps_stream_kernel<MULTI(), false, false, PACKED(), NT()>), dim3((unsigned)grid), dim3(256),
+                               0, s, cv, p, iv_start, iv_stop, out_off, tile_iv, tile_k, (long long)n_tiles, (int)tpb, out,
+                               (const WpsItem*)nullptr, 0, FusedParams{});
+            if constexpr (PACKED()) count_packed_launch();
+        }
+    }, tpb != 1, tpb == 1 && use_packed(cv, nullptr, false, &p), p.nt_store != 0);
 }
 
 // Whole-interval WPS with the window features of a regular bin tiling in the same pass.
@@ -2247,7 +2353,7 @@ void launch_wps_fused(hipStream_t s, const ContigView& cv, const WpsParams& p, i
     if (n_tiles <= 0) return;
     const size_t lds = F.do_hist ? (size_t)(F.n_bins + 1) * 4 : 0;
     with_bools([&](auto NT) {
-        hipLaunchKernelGGL((wps_stream_kernel<false, false, true, NT()>), dim3((unsigned)n_tiles), dim3(256), lds, s, cv, p,
+        hipLaunchKernelGGL((wps_stream_kernel<false, false, true, false, NT()>), dim3((unsigned)n_tiles), dim3(256), lds, s, cv, p,
                            (const int64_t*)nullptr, (const int64_t*)nullptr, (const int64_t*)nullptr,
                            (const int32_t*)nullptr, (const int32_t*)nullptr, (long long)n_tiles, 1, out,
                            (const WpsItem*)nullptr, 0, F);
@@ -2260,7 +2366,7 @@ void launch_wps_batch(hipStream_t s, const WpsParams& p, const WpsItem* d_items,
     if (n_tiles <= 0) return;
     ContigView none{};
     with_bools([&](auto NT) {
-        hipLaunchKernelGGL((wps_stream_kernel<false, true, false, NT()>), dim3((unsigned)n_tiles), dim3(256), 0, s, none, p,
+        hipLaunchKernelGGL((wps_stream_kernel<false, true, false, false, NT()>), dim3((unsigned)n_tiles), dim3(256), 0, s, none, p,
                            (const int64_t*)nullptr, (const int64_t*)nullptr, (const int64_t*)nullptr,
                            (const int32_t*)nullptr, (const int32_t*)nullptr, (long long)n_tiles, 1, out, d_items, n_items,
                            FusedParams{});

@@ -125,6 +125,10 @@ int ftk_frags_set_read1(ftk_ctx* ctx, int contig_id, const int32_t* r1_start, co
  * ftk_frag_select return their rows in file order (pysam's iteration order) instead of start order. */
 int ftk_frags_set_order(ftk_ctx* ctx, int contig_id, const int32_t* order, int64_t n);
 int ftk_frags_info(ftk_ctx* ctx, int contig_id, int64_t* n_out, int32_t* max_len_out, int32_t* max_end_out);
+/* Read-only query of the contig's packed (length, mapq) column: *present_out = 1 when the contig holds it (every
+ * fragment is at most *len_max_out long and the contig has no read1 columns), *launches_out = calls of this process that
+ * read it instead of the end and mapq columns so far (FTK_PACKED=0 keeps that at zero).  Any pointer may be NULL. */
+int ftk_frags_packed(ftk_ctx* ctx, int contig_id, int32_t* present_out, int32_t* len_max_out, int64_t* launches_out);
 int ftk_frags_release(ftk_ctx* ctx, int contig_id);
 
 /* ---- fragment-file decoder (host only; no ctx / GPU needed) ---------------

@@ -2,11 +2,27 @@
 # Round profile collection on the GPU box (run from the repo root): kernel stats of bench.py, the two HBM PMC passes,
 # SQ counters of the window-feature kernels (standalone, chained launches), kernel stats of the file -> result legs.
 # usage: tools/profile_round.sh <out_dir under gpurun_out/>
+#        tools/profile_round.sh <out_dir> headline
+#   headline: only the bench's kernel stats and its two HBM counter passes (kernel_stats.txt, pmc_hbm.txt), each step
+#   under its own time limit and the next one only after it succeeded - the before / after pair of a change to the
+#   headline launch.  BENCH_ROOT names another tree whose bench.py runs instead, for the "before" side.
 set -u
+TREE=$(cd "$(dirname "$0")/.." && pwd)
 OUT=$GRAFT_REPO_ROOT/gpurun_out/$1
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 B="python3 $GRAFT_REPO_ROOT/bench.py --no-kernel-rows"
+[ -n "${BENCH_ROOT:-}" ] && B="python3 $BENCH_ROOT/bench.py --no-kernel-rows"
+if [ "${2:-}" = headline ]; then
+  timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- $B --steps 3 --warmup 1 --no-cpu-baseline --no-end-to-end > $OUT/bench_under_profiler.json 2> $OUT/stats.err || exit 1
+  timeout -k 10 400 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/pmc_fetch -- $B --steps 1 --warmup 0 --no-cpu-baseline --no-end-to-end > /dev/null 2> $OUT/pmc_fetch.err || exit 1
+  timeout -k 10 400 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $OUT/pmc_write -- $B --steps 1 --warmup 0 --no-cpu-baseline --no-end-to-end > /dev/null 2> $OUT/pmc_write.err || exit 1
+  cd $TREE
+  python tools/prof_summary.py stats $OUT/stats > $OUT/kernel_stats.txt
+  python tools/prof_summary.py pmc $OUT/pmc_fetch $OUT/pmc_write > $OUT/pmc_hbm.txt
+  rm -rf $OUT/stats $OUT/pmc_fetch $OUT/pmc_write
+  exit 0
+fi
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- $B --steps 3 --warmup 1 --no-cpu-baseline --no-end-to-end > $OUT/bench_under_profiler.json 2> $OUT/stats.err
 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/pmc_fetch -- $B --steps 1 --warmup 0 --no-cpu-baseline --no-end-to-end > /dev/null 2> $OUT/pmc_fetch.err
 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $OUT/pmc_write -- $B --steps 1 --warmup 0 --no-cpu-baseline --no-end-to-end > /dev/null 2> $OUT/pmc_write.err

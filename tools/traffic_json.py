@@ -4,6 +4,7 @@ step's dominant kernel, as MI355X_MICROARCH.md prescribes for gfx950 ((2 * FETCH
 separate --pmc passes).  bench.py reads the file for `roofline.traffic`.
 usage: tools/traffic_json.py profiles/r3_a_pmc_hbm.txt [kernel=feat_then_wps_kernel] > profiles/wps_traffic.json"""
 import json
+import re
 import sys
 
 path = sys.argv[1]
@@ -13,9 +14,10 @@ build = sys.argv[4] if len(sys.argv) > 4 else "build not recorded"  # e.g. "r5_c
 vals, calls = {}, {}
 for line in open(path):  # (fixed-width rows of tools/prof_summary.py: 70 characters of kernel name, then four fields)
     name, f = line[:70].rstrip(), line[70:].split()
-    # the step's launch is the tabix-fetch variant <CHK, HIST, DF, BAM = false, NT>; the BAM-mode variant in the same
-    # file comes from tools/kernel_rows.py
-    if len(f) == 4 and name.startswith(kernel) and "false, true>" in name.replace("false,true", "false, true") and f[0] in ("FETCH_SIZE", "WRITE_SIZE"):
+    # the step's launch is the tabix-fetch variant <CHK, HIST, DF, BAM = false, [PACKED,] NT = true>: the FOURTH template
+    # argument is false; the BAM-mode variant in the same file comes from tools/kernel_rows.py
+    args = re.findall(r"true|false", name[len(kernel):]) if name.startswith(kernel + "<") else []
+    if len(f) == 4 and len(args) >= 5 and args[3] == "false" and args[-1] == "true" and f[0] in ("FETCH_SIZE", "WRITE_SIZE"):
         vals[f[0]] = float(f[2])
         calls[f[0]] = int(f[1])
 fetch, write = vals["FETCH_SIZE"], vals["WRITE_SIZE"]
