@@ -31,6 +31,7 @@ OPEN_LO = -(2 ** 31)
 OPEN_HI = 2 ** 31 - 1
 LEN_OPEN = -1
 GC_MAX_LEN = 1000  # FTK_GC_MAX_LEN
+WEIGHT_ONE = 65536  # FTK_WEIGHT_ONE
 POLICY = {"midpoint": 0, "any": 1}
 POLICY_FETCH = 2  # no intersect test: the index query alone (AlignmentWrapper.fetch)
 FETCH_TABIX = 0
@@ -62,6 +63,7 @@ EXPORTS = [
     "ftk_mask_lds_intervals", "ftk_frags_mask_keep", "ftk_frags_format_rows_masked", "ftk_frags_write_masked",
     "ftk_depth", "ftk_depth_runs", "ftk_format_bedgraph_runs",
     "ftk_frag_gc", "ftk_frag_gc_table", "ftk_ref_gc_table",
+    "ftk_frags_set_weights", "ftk_frags_weights", "ftk_frags_set_gc_weights", "ftk_weighted_window_sums",
 ]
 
 
@@ -331,6 +333,10 @@ def load() -> C.CDLL:
     lib.ftk_frag_gc.argtypes = [vp, C.c_int, C.c_int, i32, i32, i32, vp]
     lib.ftk_frag_gc_table.argtypes = [vp, C.c_int, C.c_int, i32, i32, i32, vp, pi64]
     lib.ftk_ref_gc_table.argtypes = [vp, C.c_int, i64, i64, i32, i32, i64, vp]
+    lib.ftk_frags_set_weights.argtypes = [vp, C.c_int, vp, i64]
+    lib.ftk_frags_weights.argtypes = [vp, C.c_int, vp]
+    lib.ftk_frags_set_gc_weights.argtypes = [vp, C.c_int, C.c_int, i32, i32, i32, vp, vp]
+    lib.ftk_weighted_window_sums.argtypes = [vp, C.c_int, vp, vp, i64, C.POINTER(Filter), vp, vp]
     lib.ftk_comm_unique_id.argtypes = [C.c_char_p]
     lib.ftk_comm_create.argtypes = [vp, C.c_int, C.c_int, C.c_char_p, C.POINTER(vp)]
     lib.ftk_comm_size.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]

@@ -207,6 +207,7 @@ void free_contig(ContigData& c) {
     if (c.base) (void)hipFree(c.base);
     if (c.r1) (void)hipFree(c.r1);
     if (c.order) (void)hipFree(c.order);
+    if (c.weights) (void)hipFree(c.weights);
     if (c.bin_idx) (void)hipFree(c.bin_idx);
     c = ContigData{};
 }
@@ -1268,3 +1269,4 @@ static int wps_params(ftk_ctx* ctx, const ContigData& c, int64_t chrom_size, int
 #include "ftk_api_export.inc"
 #include "ftk_api_depth.inc"
 #include "ftk_api_gcbias.inc"
+#include "ftk_api_weights.inc"

@@ -1,6 +1,6 @@
 // Device-only primitives that more than one kernel file uses (included by .hip files only): the wave scan and the
 // position-index bound of the per-base tiles, and the reads of a reference image through
-// its RefView.  A new kernel file takes these from here.
+// its RefView (the G + C count of a span included).  A new kernel file takes these from here.
 #pragma once
 
 #include "ftk_internal.h"
@@ -54,5 +54,40 @@ __device__ __forceinline__ void ref_text_next(const RefView& rv, long long& off,
 
 // 2bit: the code of base p (T=0 C=1 A=2 G=3; G and C have the low bit set) out of the byte that holds it, img[p >> 2]
 __device__ __forceinline__ uint32_t twobit_code(uint32_t byte, int p) { return (byte >> (6 - 2 * (p & 3))) & 3u; }
+
+// first cell of row L of a packed length x GC table (ftk_gcbias.h), relative to row 0
+__device__ __forceinline__ int tri(int L) { return L * (L + 1) / 2; }
+
+// ---- G + C bases of a span [a, b) of the image (frag_gc_kernel, frag_gc_weight_kernel) --------------------------------
+// 0 <= a < b <= chrom_len, b - a <= FTK_GC_MAX_LEN.  -1: the span holds an N.
+__device__ __forceinline__ int span_gc_2bit(const RefView& im, int a, int b) {
+    if (im.n_nblk && ref_has_n(im, a, b)) return -1;
+    const uint32_t* w32 = reinterpret_cast<const uint32_t*>(im.img);  // (the block is 256-byte aligned and 32 bytes longer than the image)
+    const int w0 = a >> 4, w1 = (b - 1) >> 4;
+    int g = 0;
+    for (int w = w0; w <= w1; ++w) {
+        const uint32_t v = __builtin_bswap32(w32[w]) & 0x55555555u;  // base j of the word: bit 30 - 2 j
+        const int j0 = max(a - 16 * w, 0), j1 = min(b - 16 * w, 16);
+        uint32_t m = 0xffffffffu >> (2 * j0);
+        if (j1 < 16) m &= ~(0xffffffffu >> (2 * j1));
+        g += __popc(v & m);
+    }
+    return g;
+}
+
+__device__ __forceinline__ int span_gc_text(const RefView& im, int a, int b) {
+    int col;
+    long long off = ref_text_offset(im, a, col);
+    int g = 0;
+    bool bad = false;
+    for (int j = a; j < b; ++j) {
+        const int ch = im.img[off] & 0xDF;  // fold case
+        const bool gc = (ch == 'G') | (ch == 'C');
+        g += gc;
+        bad |= !(gc | (ch == 'A') | (ch == 'T'));
+        ref_text_next(im, off, col);
+    }
+    return bad ? -1 : g;
+}
 
 }  // namespace ftk

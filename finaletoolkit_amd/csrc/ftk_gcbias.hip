@@ -41,39 +41,6 @@ constexpr int kGcRefPer = (kGcRefTile + FTK_GC_MAX_LEN + kGcRefThreads) / kGcRef
 constexpr int kGcRefXLen = kGcRefPer * kGcRefThreads + 8;                                 // words of x[] (>= tile + halo + 1)
 static_assert(kGcRefPer * kGcRefThreads >= kGcRefTile + FTK_GC_MAX_LEN, "a tile and its halo fit the threads' shares");
 
-__device__ __forceinline__ int tri(int L) { return L * (L + 1) / 2; }
-
-// 0 <= a < b <= chrom_len, b - a <= FTK_GC_MAX_LEN.  -1: the span holds an N.
-__device__ __forceinline__ int span_gc_2bit(const RefView& im, int a, int b) {
-    if (im.n_nblk && ref_has_n(im, a, b)) return -1;
-    const uint32_t* w32 = reinterpret_cast<const uint32_t*>(im.img);  // (the block is 256-byte aligned and 32 bytes longer than the image)
-    const int w0 = a >> 4, w1 = (b - 1) >> 4;
-    int g = 0;
-    for (int w = w0; w <= w1; ++w) {
-        const uint32_t v = __builtin_bswap32(w32[w]) & 0x55555555u;  // base j of the word: bit 30 - 2 j
-        const int j0 = max(a - 16 * w, 0), j1 = min(b - 16 * w, 16);
-        uint32_t m = 0xffffffffu >> (2 * j0);
-        if (j1 < 16) m &= ~(0xffffffffu >> (2 * j1));
-        g += __popc(v & m);
-    }
-    return g;
-}
-
-__device__ __forceinline__ int span_gc_text(const RefView& im, int a, int b) {
-    int col;
-    long long off = ref_text_offset(im, a, col);
-    int g = 0;
-    bool bad = false;
-    for (int j = a; j < b; ++j) {
-        const int ch = im.img[off] & 0xDF;  // fold case
-        const bool gc = (ch == 'G') | (ch == 'C');
-        g += gc;
-        bad |= !(gc | (ch == 'A') | (ch == 'T'));
-        ref_text_next(im, off, col);
-    }
-    return bad ? -1 : g;
-}
-
 __global__ __launch_bounds__(kGcFragThreads) void frag_gc_kernel(ContigView cv, RefView im, FragGcParams p, int n_lds_cells,
                                                                  int16_t* __restrict__ gc_out,
                                                                  unsigned long long* __restrict__ table,

@@ -67,6 +67,8 @@ struct ContigData {
     void* base = nullptr;     // one allocation holding all columns
     int32_t* r1 = nullptr;    // optional allocation for read1 columns
     int32_t* order = nullptr; // optional allocation for the file-order column
+    uint32_t* weights = nullptr;  // optional allocation: one weight per fragment in units of 2^-16 (ftk_api_weights.inc); not in
+                                  // ContigView - the kernels that read it take the pointer as an argument of their own
     int32_t* bin_idx = nullptr;
     int64_t n = 0;
     int32_t max_len = 0;

@@ -758,6 +758,54 @@ class Engine:
                                               int(stride), L.ptr(table)))
         return table
 
+    # -- per-fragment weights and their sums per window (csrc/ftk_weights.hip) ----------
+    def set_weights(self, name: str, w):
+        """Attach one weight per fragment to resident contig ``name`` (``ftk_frags_set_weights``): uint32 in units of
+        2^-16 (``_lib.WEIGHT_ONE`` = 1.0), in resident order; a host array or a uint32 / int32 device tensor of as many
+        elements as the contig has fragments.  The column stays on the device until the contig is released or loaded
+        again."""
+        if not hasattr(w, "data_ptr"):
+            w = np.ascontiguousarray(w, dtype=np.uint32)
+        n = int(w.numel()) if hasattr(w, "numel") else len(w)
+        self._check(self.lib.ftk_frags_set_weights(self.ctx, self.contig_id(name), L.ptr(w), n))
+
+    def weights(self, name: str, out=None) -> np.ndarray:
+        """The weight column of resident contig ``name`` (``ftk_frags_weights``): uint32, one per fragment.  ``out``: a
+        host array or device tensor of as many 4-byte elements as the contig has fragments.  ``FtkError`` when the
+        contig has no column."""
+        n = self.info(name)[0]
+        res = np.empty(n, np.uint32) if out is None else out
+        dst = res if n or out is not None else np.empty(1, np.uint32)
+        self._check(self.lib.ftk_frags_weights(self.ctx, self.contig_id(name), L.ptr(dst)))
+        return res
+
+    def set_gc_weights(self, name: str, rid: int, len_lo: int, len_hi: int, table, quality_threshold=30) -> int:
+        """Weights from a length x GC table (``ftk_frags_set_gc_weights``): fragment ``i`` of resident contig ``name``
+        gets ``table[L - len_lo, g]`` when ``mapq >= quality_threshold``, its length ``L`` lies in ``[len_lo, len_hi]``
+        and its span has a GC count ``g`` in reference image ``rid`` (as ``frag_gc``), else 0.  ``table``: uint32 of
+        shape ``(len_hi - len_lo + 1, len_hi + 1)``, e.g. ``utils.gc_weights(bias)``.  Returns ``n_zero``: fragments
+        that pass the MAPQ / length rule and got weight 0.  Replaces a column already attached."""
+        table = np.ascontiguousarray(table, dtype=np.uint32)
+        if table.shape != (int(len_hi) - int(len_lo) + 1, int(len_hi) + 1):
+            raise ValueError(f"table should have shape {(int(len_hi) - int(len_lo) + 1, int(len_hi) + 1)}, not {table.shape}")
+        n_zero = C.c_int64()
+        self._check(self.lib.ftk_frags_set_gc_weights(self.ctx, self.contig_id(name), int(rid), int(len_lo), int(len_hi),
+                                                      int(quality_threshold), L.ptr(table), C.byref(n_zero)))
+        return int(n_zero.value)
+
+    def weighted_window_sums(self, name: str, starts: Sequence, stops: Sequence, quality_threshold=30, min_length=None,
+                             max_length=None, intersect_policy="midpoint"):
+        """``(sums, n_weighted)`` int64 per window (``ftk_weighted_window_sums``): the sum of the weights, in units of
+        2^-16, of the fragments ``window_counts`` counts for the window under the same arguments, and how many of
+        them have a weight above 0."""
+        ws, we = _win(starts, L.OPEN_LO), _win(stops, L.OPEN_HI)
+        f = self._filter(name, quality_threshold, min_length, max_length, intersect_policy)
+        sums = np.zeros(len(ws), np.int64)
+        n_weighted = np.zeros(len(ws), np.int64)
+        self._check(self.lib.ftk_weighted_window_sums(self.ctx, self.contig_id(name), L.ptr(ws), L.ptr(we), len(ws),
+                                                      C.byref(f), L.ptr(sums), L.ptr(n_weighted)))
+        return sums, n_weighted
+
     # -- WPS post-processing --------------------------------------------------------
     def wps_adjust(self, scores, offsets, median_window_size=1000, mean=False, edge_sub=None, savgol_window_size=21,
                    savgol_poly_deg=2, savgol=True, out=None):

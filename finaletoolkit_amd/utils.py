@@ -17,7 +17,7 @@ from .exceptions import InvalidInputError
 from .source import get_engine, open_source
 
 __all__ = ["chrom_sizes_to_list", "chrom_sizes_to_dict", "get_intervals", "overlaps", "frags_in_region", "frag_generator",
-           "frag_array", "frag_export", "frag_filter", "read_region_mask", "agg_bw", "gen_kmers", "reverse_complement", "validate_compatible_contigs", "valid_interval",
+           "frag_array", "frag_export", "frag_filter", "frag_gc_coverage", "gc_weights", "read_gc_bias_table", "read_region_mask", "agg_bw", "gen_kmers", "reverse_complement", "validate_compatible_contigs", "valid_interval",
            "_none_eq", "_none_geq", "_none_leq"]
 
 FragTuple = Tuple[str, int, int, int, bool]
@@ -474,10 +474,9 @@ def frag_gc_bias(input_file, reference_file, output_file=None, contig=None, min_
     ``skipped_contigs``.  ``output_file`` (``.tsv`` / ``.tsv.gz``): ``length gc observed expected bias`` rows of the
     cells with ``observed > 0 or expected > 0``.
 
-    Per-fragment weights: with the contig resident (``key = open_source(input_file).require(contig)``) and its image
-    ``rid = ReferenceGenome(reference_file).device_image(engine, contig)``, ``g = engine.frag_gc(key, rid,
-    quality_threshold, min_length, max_length)`` holds each fragment's G + C (``-1``: not counted) and, with ``L`` its
-    length, ``weight = 1 / bias[L - min_length, g]``."""
+    Per-fragment weights ``1 / bias[L - min_length, g]`` and the GC-corrected coverage of intervals they give:
+    ``frag_gc_coverage`` (which takes this result, or its TSV, as ``bias``); ``gc_weights`` turns the bias table into the
+    weight table ``Engine.set_gc_weights`` attaches to a resident contig."""
     import os
     import sys
     import time
@@ -523,6 +522,174 @@ def frag_gc_bias(input_file, reference_file, output_file=None, contig=None, min_
         writers.write_gc_bias_table(os.fspath(output_file), lo, res.observed, res.expected, res.bias)
     if verbose:
         sys.stderr.write(f"frag_gc_bias: {res.n_fragments} fragments in {time.time() - t0:.3f} s\n")
+    return res
+
+
+def gc_weights(bias, min_bias: float = 0.05) -> np.ndarray:
+    """The weight table of a bias table (a ``GCBias`` or a float array): uint32 in units of 2^-16, ``floor(65536 / bias +
+    0.5)`` per cell, 0 where the bias is NaN or below ``min_bias`` (a cell with hardly any observed fragments would
+    otherwise give each of them a huge weight).  ``min_bias`` is at least 2^-15, which keeps every weight within 2^31
+    units."""
+    if not float(min_bias) >= 2.0 ** -15:
+        raise ValueError(f"invalid min_bias ({min_bias}): at least 2**-15")
+    b = np.asarray(bias.bias if isinstance(bias, GCBias) else bias, dtype=np.float64)
+    out = np.zeros(b.shape, np.uint32)
+    ok = ~np.isnan(b) & (b >= float(min_bias))
+    out[ok] = np.floor(65536.0 / b[ok] + 0.5).astype(np.uint32)
+    return out
+
+
+def read_gc_bias_table(path, min_length: int, max_length: int) -> GCBias:
+    """The ``GCBias`` of a TSV written by ``frag_gc_bias`` / ``writers.write_gc_bias_table`` (``.gz``: gzip) for the
+    lengths ``[min_length, max_length]``.  The file holds ``repr(float)`` of every bias, so the tables come back exactly;
+    cells it does not list are ``0 / 0 / nan``.  A row of another length, or with more G + C than ``max_length``, raises
+    ``ValueError``.  ``n_skipped`` is 0 and ``skipped_contigs`` empty: the file does not hold them."""
+    import gzip
+    import os
+    lo, hi = int(min_length), int(max_length)
+    if lo < 1 or hi < lo:
+        raise ValueError(f"invalid lengths: 1 <= min_length ({min_length}) <= max_length ({max_length}) is required")
+    shape = (hi - lo + 1, hi + 1)
+    observed, expected, bias = np.zeros(shape, np.int64), np.zeros(shape, np.int64), np.full(shape, np.nan)
+    path = os.fspath(path)
+    with (gzip.open(path, "rt") if path.endswith(".gz") else open(path, "r")) as fh:
+        head = fh.readline().rstrip("\n").split("\t")
+        if head != ["length", "gc", "observed", "expected", "bias"]:
+            raise ValueError(f"{path}: not a length x GC bias table (header {head})")
+        for line in fh:
+            if not line.strip():
+                continue
+            length, g, o, e, b = line.rstrip("\n").split("\t")
+            length, g = int(length), int(g)
+            if not (lo <= length <= hi and 0 <= g <= hi):
+                raise ValueError(f"{path}: row length {length}, gc {g} lies outside the lengths [{lo}, {hi}]")
+            observed[length - lo, g], expected[length - lo, g], bias[length - lo, g] = int(o), int(e), float(b)
+    return GCBias(lo, hi, observed, expected, bias, int(observed.sum()), 0, ())
+
+
+class GCCoverage(NamedTuple):
+    """Result of ``frag_gc_coverage``, one entry per interval of the interval file, in its order."""
+    intervals: list           # (contig, start, stop, name)
+    count: np.ndarray         # int64: fragments the interval counts (``frag.coverage``'s number)
+    corrected: np.ndarray     # float64: the sum of their weights; NaN on a contig the reference lacks
+    n_weighted: np.ndarray    # int64: those with a weight above 0
+    n_zero: int               # fragments of the visited contigs that pass the MAPQ / length rule and got weight 0
+    skipped_contigs: tuple    # contigs with intervals that the reference does not hold
+
+
+_GC_COVERAGE_SUFFIXES = (".bed", ".bed.gz")
+
+
+def _check_gc_coverage_args(output_file, bias, min_length, max_length, intersect_policy, min_bias, stride):
+    _check_gc_bias_args(None, min_length, max_length, stride, None)
+    _check_policy(intersect_policy)
+    if not float(min_bias) >= 2.0 ** -15:
+        raise ValueError(f"invalid min_bias ({min_bias}): at least 2**-15")
+    if output_file is not None and not str(output_file).endswith(_GC_COVERAGE_SUFFIXES):
+        raise ValueError("output_file should have .bed or .bed.gz as suffix")
+    if isinstance(bias, GCBias) and (bias.min_length, bias.max_length) != (int(min_length), int(max_length)):
+        raise ValueError(f"the bias table holds lengths [{bias.min_length}, {bias.max_length}], not "
+                         f"[{min_length}, {max_length}]")
+
+
+def frag_gc_coverage(input_file, reference_file, interval_file, output_file=None, bias=None, min_length: int = 100,
+                     max_length: int = 220, quality_threshold: int = 30, intersect_policy: str = "midpoint",
+                     min_bias: float = 0.05, stride: int = 1, workers=None, verbose=False) -> GCCoverage:
+    """GC-bias-corrected fragment coverage of every interval of ``interval_file`` (BED): what Griffin, ichorCNA-style
+    copy-number work and DELFI-style features start from, with the correction applied per FRAGMENT, so no bin-level
+    LOESS is involved.
+
+    Every fragment with ``mapq >= quality_threshold`` and a length ``L`` in ``[min_length, max_length]`` whose reference
+    span holds ``g`` G / C bases weighs ``1 / bias[L - min_length, g]`` (``gc_weights``: rounded to units of 2^-16; 0
+    where the bias is undefined or below ``min_bias``, and for a span that leaves the contig or holds an N).  Per
+    interval, ``count`` is the number of such fragments the interval counts under ``intersect_policy`` (the number
+    ``frag.coverage`` reports with the same arguments), ``corrected`` the sum of their weights and ``n_weighted`` how
+    many of them weigh more than 0.  The weights are summed as integers on the GPU, contig by contig as the input is
+    decoded (``Engine.set_gc_weights``, ``Engine.weighted_window_sums``), so ``corrected`` is exact and does not
+    depend on the order of the fragments.
+
+    ``bias``: a ``GCBias`` (from ``frag_gc_bias``), the path of its TSV (``read_gc_bias_table``), or ``None`` - then
+    ``frag_gc_bias(input_file, reference_file, ...)`` runs first with the same lengths, MAPQ cut and ``stride``.  A
+    ``GCBias`` of other lengths raises ``ValueError``.
+
+    No further normalisation is applied.  With ``1 / bias`` of the SAME sample the weights of all fragments sum to
+    ``n_fragments * (share of the expected windows whose cell has observed fragments)`` - each cell contributes
+    ``observed * (expected / expected.sum()) / (observed / observed.sum())`` - so the mean weight is close to 1 and
+    ``corrected`` stays on the scale of ``count``; it falls below 1 by the cells ``min_bias`` removes.
+
+    Contigs with intervals that the reference lacks: one ``UserWarning``, their intervals keep their ``count`` and get
+    ``corrected = nan``.  An interval on a contig the input lacks raises ``ValueError``, as in ``frag.coverage``.
+    ``output_file`` (``.bed`` / ``.bed.gz``): rows ``contig start stop name count corrected`` in the interval file's
+    order, ``corrected`` with six decimals or ``nan``."""
+    import os
+    import sys
+    import time
+    import warnings
+
+    from . import _lib as L
+    from . import writers
+    from .reference import ReferenceGenome
+    from .source import ContigFeed
+    _check_gc_coverage_args(output_file, bias, min_length, max_length, intersect_policy, min_bias, stride)
+    lo, hi = int(min_length), int(max_length)
+    t0 = time.time()
+    if bias is None:
+        with warnings.catch_warnings():  # (contigs the reference lacks are reported once, below)
+            warnings.filterwarnings("ignore", message="frag_gc_bias: contigs not in the reference", category=UserWarning)
+            bias = frag_gc_bias(input_file, reference_file, None, None, lo, hi, quality_threshold, stride, None, workers, verbose)
+    elif not isinstance(bias, GCBias):
+        bias = read_gc_bias_table(bias, lo, hi)
+    table = gc_weights(bias, min_bias)
+    intervals = get_intervals(interval_file)
+    by_contig: dict[str, list[int]] = {}
+    for i, iv in enumerate(intervals):
+        by_contig.setdefault(iv[0], []).append(i)
+    starts = np.array([iv[1] for iv in intervals], dtype=np.int64)
+    stops = np.array([iv[2] for iv in intervals], dtype=np.int64)
+    count = np.zeros(len(intervals), np.int64)
+    units = np.zeros(len(intervals), np.int64)
+    n_weighted = np.zeros(len(intervals), np.int64)
+    no_reference = np.zeros(len(intervals), bool)
+    n_zero, missing, left = 0, [], dict(by_contig)
+    eng = get_engine()
+    feed = ContigFeed(input_file, workers, names=list(by_contig))
+    try:
+        with ReferenceGenome(reference_file) as ref:
+            for src, c in feed:
+                idx = left.pop(c, None)
+                if idx is None:
+                    continue
+                key = src.key(c)
+                idx = np.asarray(idx, dtype=np.int64)
+                order = idx[np.argsort(starts[idx], kind="stable")]
+                ws, we = starts[order].astype(np.int32), stops[order].astype(np.int32)
+                args = (quality_threshold, lo, hi, intersect_policy)
+                count[order] = eng.window_counts(key, ws, we, *args)
+                if c not in ref.chroms:
+                    missing.append(c)
+                    no_reference[order] = True
+                    continue
+                rid = ref.device_image(eng, c, with_layout=True)
+                zeros = eng.set_gc_weights(key, rid, lo, hi, table, quality_threshold)
+                units[order], n_weighted[order] = eng.weighted_window_sums(key, ws, we, *args)
+                n_zero += zeros
+                if verbose:
+                    sys.stderr.write(f"frag_gc_coverage: {c}: {len(order)} intervals, {zeros} fragments of weight 0\n")
+            src = feed.finish()
+    except BaseException:
+        feed.close()
+        raise
+    for c in left:  # contigs the file does not hold: the ValueError of frag.coverage
+        src.require(c)
+    if missing:
+        warnings.warn("frag_gc_coverage: contigs not in the reference were not corrected: " + ", ".join(missing), UserWarning)
+    corrected = units / float(L.WEIGHT_ONE)
+    corrected[no_reference] = np.nan
+    res = GCCoverage(intervals, count, corrected, n_weighted, int(n_zero), tuple(missing))
+    if output_file is not None:
+        writers.write_gc_coverage_rows(os.fspath(output_file), intervals, count, corrected)
+    if verbose:
+        sys.stderr.write(f"frag_gc_coverage: {len(intervals)} intervals in {time.time() - t0:.3f} s\n")
     return res
 
 

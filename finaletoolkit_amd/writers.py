@@ -283,3 +283,14 @@ def write_gc_bias_table(output_file: str, min_length: int, observed, expected, b
     if not output_file.endswith(GC_BIAS_SUFFIXES):
         raise ValueError(message)
     _emit(output_file, gc_bias_text(min_length, observed, expected, bias), (".tsv",), (".tsv.gz",), message)
+
+
+def write_gc_coverage_rows(output_file: str, intervals, count, corrected) -> None:
+    """``contig start stop name count corrected`` per interval (``utils.frag_gc_coverage``), ``corrected`` with six
+    decimals or ``nan``; ``.bed`` as text, ``.bed.gz`` as gzip."""
+    message = "output_file should have .bed or .bed.gz as suffix"
+    if not output_file.endswith((".bed", ".bed.gz")):
+        raise ValueError(message)
+    text = "".join([f"{c}\t{a}\t{b}\t{n}\t{int(k)}\t{'nan' if x != x else format(float(x), '.6f')}\n"
+                    for (c, a, b, n), k, x in zip(intervals, count, corrected)])
+    _emit(output_file, text, (".bed",), (".bed.gz",), message)

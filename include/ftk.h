@@ -542,6 +542,36 @@ int ftk_frag_gc_table(ftk_ctx* ctx, int contig_id, int ref_id, int32_t len_lo, i
 int ftk_ref_gc_table(ftk_ctx* ctx, int ref_id, int64_t pos_lo, int64_t pos_hi, int32_t len_lo, int32_t len_hi,
                      int64_t stride, int64_t* table_out);
 
+/* ---- per-fragment weights and their sums per window (csrc/ftk_weights.hip) -------------------------
+ * A resident contig can carry ONE weight per fragment: a uint32 in units of 2^-16 (FTK_WEIGHT_ONE = 1.0), in resident
+ * order, kept on the device until ftk_frags_release or until the contig id is loaded again.  Window sums are int64
+ * sums of those units (fewer than 2^31 fragments times a weight below 2^32 cannot overflow), so every result is exact
+ * and independent of the order of arrival.
+ *   ftk_frags_set_weights     attaches an arbitrary column: n = the contig's fragment count, w a host or device array.
+ *   ftk_frags_weights         reads the column back into a host or device array of as many elements;
+ *                             FTK_ERR_INVALID ("... no weights column") when the contig has none.
+ *   ftk_frags_set_gc_weights  GC-bias weights: w[i] = table[L - len_lo][g] for a fragment with mapq >= mapq_min,
+ *                             L = end - start in [len_lo, len_hi] and g = gc(start, end) defined as for ftk_frag_gc
+ *                             (above); every other fragment gets 0.  `table` is a HOST array of shape
+ *                             [len_hi - len_lo + 1][len_hi + 1], the layout of ftk_frag_gc_table's output; lengths and
+ *                             image as there (1 <= len_lo <= len_hi <= FTK_GC_MAX_LEN, a layout, chrom_len < 2^30).
+ *                             *n_zero_out (host or device) = fragments that pass the MAPQ and length rule and got
+ *                             weight 0: gc undefined, or a table cell of 0.  Replaces a column already attached.
+ *   ftk_weighted_window_sums  sum_out[i] = sum of w over the fragments ftk_window_counts counts for window i under the
+ *                             same filter `f` - FTK_POLICY_FETCH is accepted too: the index query alone;
+ *                             n_weighted_out[i] (may be NULL) = how many of them have w > 0.  Windows are host
+ *                             arrays, may overlap and come in any order, FTK_OPEN_LO / FTK_OPEN_HI as there; outputs
+ *                             are host or device arrays and are overwritten.  n_win == 0 is FTK_OK; a contig without
+ *                             a column is FTK_ERR_INVALID.
+ * A failing call writes to none of its outputs. */
+#define FTK_WEIGHT_ONE 65536u
+int ftk_frags_set_weights(ftk_ctx* ctx, int contig_id, const uint32_t* w, int64_t n);
+int ftk_frags_weights(ftk_ctx* ctx, int contig_id, uint32_t* w_out);
+int ftk_frags_set_gc_weights(ftk_ctx* ctx, int contig_id, int ref_id, int32_t len_lo, int32_t len_hi, int32_t mapq_min,
+                             const uint32_t* table, int64_t* n_zero_out);
+int ftk_weighted_window_sums(ftk_ctx* ctx, int contig_id, const int32_t* w_start, const int32_t* w_end, int64_t n_win,
+                             const ftk_filter* f, int64_t* sum_out, int64_t* n_weighted_out /* may be NULL */);
+
 /* ---- BGZF inflate on the device -------------------------------------------------------------------
  * The streaming decoder's host threads spend most of a fragment file's decode in DEFLATE; BGZF blocks are
  * independent streams of at most 64 KB of data, decoded here one wavefront per block (csrc/ftk_inflate.hip).

@@ -2,7 +2,8 @@
 """Kernel micro-bench on one synthetic contig (GPU box): times ftk_wps / window features with
 HIP events, interleaved repetitions.  usage: tools/kbench.py [contig_len] [reps]
 KBENCH=depth: the depth track (per base and run-length encoded) beside the cleavage profile of the same contig.
-KBENCH=gcbias: the observed and the expected length x GC table (lengths 100-220) against a synthetic 2bit image."""
+KBENCH=gcbias: the observed and the expected length x GC table (lengths 100-220) against a synthetic 2bit image.
+KBENCH=gcweights: the GC weight column (lengths 100-220) and its sums per window beside ftk_window_counts on the same windows."""
 import os
 import sys
 
@@ -194,6 +195,45 @@ if "gcbias" in which:
         timeit(lambda: eng.ref_gc_table(ridb, 0, size, 100, 220, 16), "expected table, stride 16", img)
     exp = eng.ref_gc_table(ridb, 0, size, 100, 220, 16)
     print("gcbias checksum", int(obs.sum()), int(exp.sum()), "(share of the byte floor = GB/s above / the HBM rate)")
+if "gcweights" in which:
+    # GC weights, lengths 100-220, against the 2bit image of KBENCH=gcbias: the weights call (table packed and uploaded,
+    # kernel, the 8-byte count read back), then the weighted sums and, on the same windows in the same run, the window
+    # counts that are their yardstick - over the 100 kb tiling and over one whole-contig window, outputs on the device.
+    # Byte floors: weights = 9 B read (start, end, mapq) + 4 B written per fragment + the image once; sums = 13 B (start,
+    # end, mapq, weight) per candidate - the fragments the position index hands each window, counted here from the
+    # sorted starts; counts = 9 B per candidate.
+    rng = np.random.default_rng(7)
+    packed = rng.integers(0, 256, (size + 3) // 4, dtype=np.uint8)
+    ridw = eng.ref_upload(("kb", "gcbias2bit"), packed, 1)
+    eng.ref_set_layout(ridw, size, 0, 0, [10_000_000], [10_050_000])
+    img = (size + 3) // 4
+    table = rng.integers(1, 1 << 20, (121, 221), dtype=np.int64).astype(np.uint32)
+    lmax = eng.info("c")[1]
+    hs = s.cpu().numpy().astype(np.int64)
+    lo = np.searchsorted(hs, (np.maximum(ws.astype(np.int64) - lmax, 0) >> 9) << 9, side="left")
+    hi = np.searchsorted(hs, ((we.astype(np.int64) >> 9) + 1) << 9, side="left")
+    cand = int((hi - lo).sum())
+    one_lo, one_hi = np.array([0], np.int32), np.array([size], np.int32)
+    import ctypes as C
+    from finaletoolkit_amd import _lib as L
+    flt = L.make_filter(30, None, None, "midpoint")
+    d_sum = torch.zeros(len(ws), dtype=torch.int64, device=dev)
+    d_cnt = torch.zeros(len(ws), dtype=torch.int64, device=dev)
+
+    def sums(a, b):
+        eng._check(eng.lib.ftk_weighted_window_sums(eng.ctx, eng.contig_id("c"), L.ptr(a), L.ptr(b), len(a), C.byref(flt),
+                                                    L.ptr(d_sum), L.ptr(d_cnt)))
+    n_zero = eng.set_gc_weights("c", ridw, 100, 220, table, 30)
+    print(f"gcweights: {n} fragments, {n_zero} of weight 0, {len(ws)} windows with {cand} candidates ({cand / n:.2f} per "
+          f"fragment), image {img} B", flush=True)
+    for _ in range(2):  # twice: the spread between the two passes is the noise
+        timeit(lambda: eng.set_gc_weights("c", ridw, 100, 220, table, 30), "gc weights 100-220", 13 * n + img)
+        timeit(lambda: sums(ws, we), "weighted sums 100kb", 13 * cand)
+        timeit(lambda: eng.window_counts("c", ws, we, 30, out=cov), "window_counts 100kb", 9 * cand)
+        timeit(lambda: sums(one_lo, one_hi), "weighted sums one window", 13 * n)
+        timeit(lambda: eng.window_counts("c", one_lo, one_hi, 30, out=cov[:1]), "window_counts one window", 9 * n)
+    sums(ws, we)
+    print("gcweights checksum", int(d_sum.sum().item()), int(d_cnt.sum().item()), "counts", int(eng.window_counts("c", ws, we, 30).sum()))
 if "gc" in which:
     rng = np.random.default_rng(6)
     packed = rng.integers(0, 256, (size + 3) // 4, dtype=np.uint8)
