@@ -555,7 +555,7 @@ __device__ __forceinline__ void feat_element(const ContigView& cv, const FeatPar
 // worth of bool flags live as 64-bit lane masks in SGPRs, spill to VGPR lanes, and the pass turns issue-bound on the
 // readlane / mask traffic (134 VALU + 79 SALU instructions per fragment in the first form of this function).
 // ws / we1 are the CLAMPED bounds (window_bounds<1>); the filter is the motif pass' own (policy ANY, no length
-// bounds: ftk_motif_counts), so the window test is overlap + mapq (+ read1 overlap for a BAM fetch).
+// bounds: ftk_motif_counts), so the window test is mapq + overlap (tabix) or mapq + read1's overlap (a BAM fetch).
 // EDGE = false: the window's reach (motif_reach) lies inside the contig, so no k-mer of a FETCHED fragment can start
 // outside it and the two range tests are left out (chosen per window; never for a BAM fetch, whose read1 may poke out).
 template <bool BAM, int N, bool EDGE = true>
@@ -569,8 +569,11 @@ __device__ __forceinline__ void motif_prep(const ContigView& cv, const FeatParam
     const int last = M.chrom_len - M.k;              // last base a k-mer may start at
 #pragma unroll
     for (int j = 0; j < N; ++j) {
-        int x = (q[j] - P.ch_q) | (fe[j] - 1 - ws) | (we1 - fs[j]) | (hi - 1 - idx[j]);
+        // the index query alone decides: the fragment's overlap for tabix, read1's for a BAM (io/alignment.py:245) --
+        // there a read1 that pokes out of its fragment fetches it for a window the fragment itself does not touch
+        int x = (q[j] - P.ch_q) | (hi - 1 - idx[j]);
         if (BAM) x |= (we1 - cv.r1_start[min(idx[j], hi - 1)]) | (cv.r1_end[min(idx[j], hi - 1)] - 1 - ws);
+        else x |= (fe[j] - 1 - ws) | (we1 - fs[j]);
         n_ok += __popcll(__ballot(x >= 0));  // (scalar unit) fetched fragments of the wave
         if (M.guard > 0) x |= (fs[j] - M.guard) | (M.chrom_len - 1 - M.guard - fs[j]);
         int u_fwd = M.both ? 0 : -1;
@@ -2275,6 +2278,9 @@ bool launch_window_features(hipStream_t s, int grid_large, const ContigView& cv,
         if (r.motif) {
             P.mp = *r.motif;
             P.do_hist = 1;
+            // every FETCHED fragment counts (frag/_end_motifs.py:120): for a BAM the general form tests read1's overlap
+            // and not the fragment's (for tabix the two policies are one test; motif_prep states the same rule)
+            if (kBam) P.wp.policy = FTK_POLICY_FETCH;
             // a 2bit image and k <= 13: the k-mer is cut out of one 4-byte load (its own instantiation: the general
             // form's loops, unrolled with the window kernels, do not fit the instruction cache beside it)
             if (P.mp.kind == FTK_REF_2BIT && P.mp.k <= 13 && P.is_any && P.ch_min <= 0 && P.ch_max >= (1 << 30))

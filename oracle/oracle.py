@@ -18,6 +18,7 @@ tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg import this.
 from __future__ import annotations
 
 import ctypes as C
+import functools
 import os
 import subprocess
 
@@ -454,6 +455,12 @@ def _py_sequence(seq, start, stop):
     return seq[start:stop].upper()
 
 
+@functools.lru_cache(maxsize=None)
+def _gen_kmers(k):
+    import itertools
+    return tuple("".join(t) for t in itertools.product("ACGT", repeat=k))
+
+
 def py_region_motifs(rows, seq, start, stop, k, kind="end", both_strands=True, negative_strand=False,
                      quality_threshold=20):
     """Counts per k-mer in gen_kmers order for one region.  ``rows``: the contig's
@@ -461,10 +468,9 @@ def py_region_motifs(rows, seq, start, stop, k, kind="end", both_strands=True, n
     absent from the genome).  kind "end": k-mer at [fs, fs+k) and revcomp of [fe-k, fe);
     kind "breakpoint": [fs-k//2, fs+k//2) and revcomp of [fe-k//2, fe+k//2) with the contig-end guard.
     Raises RuntimeError where the reference does (end motifs, both strands, 3' k-mer off the contig)."""
-    import itertools
     if both_strands and negative_strand:
         raise ValueError("Cannot have both both_strands and negative_strand.")
-    kmers = ["".join(t) for t in itertools.product("ACGT", repeat=k)]
+    kmers = _gen_kmers(k)
     counts = dict.fromkeys(kmers, 0)
     h = k // 2
     chrom_len = len(seq) if seq is not None else 0

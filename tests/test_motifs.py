@@ -311,9 +311,7 @@ def test_gpu_many_equal_windows_take_the_block_kernels(engine, kind, tmp_path):
 
 
 def _end_both_no_raise(rws, s, a, b, k, q):
-    """both-strands end motifs where no 3' k-mer leaves the contig (fe >= k holds for all rows here
-    except possibly tiny fragments at the contig start: those raise in the reference, so they are
-    counted by the strand-wise calls instead)."""
-    fwd = O.py_region_motifs([(x, y, m, 1) for x, y, m, _ in rws], s, a, b, k, "end", False, False, q)
-    rev = O.py_region_motifs([r for r in rws if r[1] - k >= 0], s, a, b, k, "end", False, True, q)
-    return fwd + rev
+    """both-strands end motifs where the reference raises on a 3' k-mer off the contig (tiny fragments at the contig
+    start here): the strand-wise split of tests/motif_edges.py, counts only."""
+    from tests.motif_edges import end_both_split
+    return end_both_split(rws, s, a, b, k, q)[0]
