@@ -1,0 +1,120 @@
+// Site-aggregated midpoint profiles (ftk_site_profile): for every site (centre c, flip flag, group) the fragments that
+// pass the MAPQ / length rule and whose midpoint m = (start + end) >> 1 lies in [c - H, c + H) are counted, and their
+// weights summed, in bin (m - c + H) / b of the site's group - bin n_bins - 1 - k for a flipped site.  Sums and counts
+// are integers, so no result depends on the order of arrival.
+//
+// site_profile_kernel  one workgroup per RUN of sites; the host sorted the sites by (group, centre) and cut the list
+//                      into runs that stay inside one group (site_run_sites).  The run's profile lives in LDS: n_bins
+//                      64-bit sums and n_bins 32-bit counts (12 bytes per bin, 48 KiB at most).  A wave takes one site
+//                      at a time; its candidate range comes from the 512-bp index as weighted_window_kernel takes its
+//                      own: [index_bound(c - H - lmax), index_bound(c + H, 1)).  The lanes stride over the candidates,
+//                      kSiteUnroll loads in flight per lane and column, with coalesced reads of start, end and mapq (9
+//                      bytes per candidate; 13 with the weight, which is read only when weights are used).  The
+//                      predicate is branch-free; the bin's quotient is estimated in float (d + H < 2^21 is exact
+//                      there) and corrected by one step either way, so it is the integer quotient.  A passing
+//                      candidate adds to its bin with LDS atomics; without weights the sum is the count times
+//                      FTK_WEIGHT_ONE and only the count is kept.  At the end of the run the non-zero bins go to the
+//                      zeroed outputs of the run's group with one 64-bit global atomic each.
+#include <algorithm>
+
+#include "ftk_device.h"
+#include "ftk_siteprofile.h"
+
+namespace ftk {
+
+namespace {
+
+constexpr int kSiteUnroll = 4;
+
+template <bool WEIGHTED>
+__global__ __launch_bounds__(kSiteThreads) void site_profile_kernel(ContigView cv, const uint32_t* __restrict__ weights,
+                                                                    const uint32_t* __restrict__ site,
+                                                                    const int32_t* __restrict__ run_off,
+                                                                    const int32_t* __restrict__ run_group, SiteProfileParams p,
+                                                                    unsigned long long* __restrict__ sum_out,
+                                                                    unsigned long long* __restrict__ cnt_out) {
+    extern __shared__ unsigned long long sum_s[];  // n_bins sums (WEIGHTED only), then n_bins counts
+    unsigned int* cnt_s = reinterpret_cast<unsigned int*>(sum_s + p.n_bins);
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    for (int k = tid; k < p.n_bins; k += kSiteThreads) {
+        sum_s[k] = 0;
+        cnt_s[k] = 0;
+    }
+    __syncthreads();
+    const int s0 = run_off[blockIdx.x], s1 = run_off[blockIdx.x + 1];
+    const int H = p.half_width, b = p.bin_size;
+    const float rinv = 1.0f / (float)b;
+    for (int si = s0 + wv; si < s1; si += kSiteThreads / 64) {
+        const uint32_t word = site[si];
+        const int c = (int)(word & ~kSiteFlipBit);
+        const bool flip = (word & kSiteFlipBit) != 0;
+        const int lo = index_bound(cv, (long long)c - H - p.lmax, 0);
+        int hi = index_bound(cv, (long long)c + H, 1);
+        if (hi < lo) hi = lo;
+        for (int base = lo; base < hi; base += 64 * kSiteUnroll) {
+            int fs[kSiteUnroll], fe[kSiteUnroll], q[kSiteUnroll];
+            uint32_t wt[kSiteUnroll];
+            bool valid[kSiteUnroll];
+#pragma unroll
+            for (int u = 0; u < kSiteUnroll; ++u) {
+                const int j = base + u * 64 + lane;  // (hi <= n < 2^31 - 1024: no overflow)
+                valid[u] = j < hi;
+                const int i = valid[u] ? j : base;  // (lo <= base < hi <= n: a fragment of the contig)
+                fs[u] = cv.start[i];
+                fe[u] = cv.end[i];
+                q[u] = cv.mapq[i];
+                wt[u] = WEIGHTED ? weights[i] : 0u;
+            }
+#pragma unroll
+            for (int u = 0; u < kSiteUnroll; ++u) {
+                const int len = fe[u] - fs[u];
+                const int mid = (int)(((unsigned)fs[u] + (unsigned)fe[u]) >> 1);  // coordinates < 2^30
+                const int d = mid - c;
+                const bool ok = valid[u] & (q[u] >= p.mapq_min) & (len >= p.min_len) & (len <= p.max_len) & (d >= -H) & (d < H);
+                const int x = ok ? d + H : 0;  // 0 <= x < 2 H <= 2^21
+                int k = (int)((float)x * rinv);  // within one of x / b
+                const int r = x - k * b;
+                k += (r >= b) - (r < 0);
+                if (flip) k = p.n_bins - 1 - k;
+                if (ok) {  // 0 <= k < n_bins
+                    atomicAdd(&cnt_s[k], 1u);
+                    if (WEIGHTED) atomicAdd(&sum_s[k], (unsigned long long)wt[u]);
+                }
+            }
+        }
+    }
+    __syncthreads();
+    const size_t row = (size_t)run_group[blockIdx.x] * (size_t)p.n_bins;
+    for (int k = tid; k < p.n_bins; k += kSiteThreads) {
+        const unsigned long long n = cnt_s[k];
+        const unsigned long long w = WEIGHTED ? sum_s[k] : n * FTK_WEIGHT_ONE;
+        if (w) atomicAdd(&sum_out[row + k], w);
+        if (cnt_out && n) atomicAdd(&cnt_out[row + k], n);
+    }
+}
+
+}  // namespace
+
+long long site_run_sites(int n_cu, long long n_sites, long long n_frag, int max_end, const SiteProfileParams& p) {
+    const double reach = 2.0 * p.half_width + p.lmax + 2.0 * (1 << kBinShift);  // what the index hands one site
+    const double est = std::max(1.0, std::min((double)n_frag, (double)n_frag / std::max(max_end, 1) * reach));
+    long long per_run = (long long)((double)kSiteRunCandidates / est) + 1;
+    per_run = std::min(per_run, (n_sites + kSiteRunsPerCu * n_cu - 1) / (kSiteRunsPerCu * n_cu));
+    per_run = std::min(per_run, (long long)(0xffffffffLL / std::max(n_frag, 1LL)));
+    return std::max(per_run, 1LL);
+}
+
+void launch_site_profile(hipStream_t s, const ContigView& cv, const uint32_t* weights, const uint32_t* site, const int32_t* run_off,
+                         const int32_t* run_group, int n_runs, const SiteProfileParams& p, unsigned long long* sum,
+                         unsigned long long* cnt) {
+    if (n_runs <= 0 || cv.n <= 0) return;
+    const size_t lds = (size_t)p.n_bins * 12;
+    if (p.weighted)
+        hipLaunchKernelGGL(site_profile_kernel<true>, dim3((unsigned)n_runs), dim3(kSiteThreads), lds, s, cv, weights, site, run_off,
+                           run_group, p, sum, cnt);
+    else
+        hipLaunchKernelGGL(site_profile_kernel<false>, dim3((unsigned)n_runs), dim3(kSiteThreads), lds, s, cv, weights, site, run_off,
+                           run_group, p, sum, cnt);
+}
+
+}  // namespace ftk

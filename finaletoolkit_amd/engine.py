@@ -806,6 +806,34 @@ class Engine:
                                                       C.byref(f), L.ptr(sums), L.ptr(n_weighted)))
         return sums, n_weighted
 
+    # -- site-aggregated midpoint profiles (csrc/ftk_siteprofile.hip) --------------------
+    def site_profile(self, name: str, centres: Sequence, flip=None, groups=None, n_groups: int = 1, half_width: int = 1000,
+                     bin_size: int = 1, quality_threshold=30, min_length=None, max_length=None, weighted: bool = False):
+        """``(sums, counts)`` int64 of shape ``(n_groups, 2 * half_width // bin_size)`` (``ftk_site_profile``): the
+        midpoint profile of resident contig ``name`` around the sites ``centres``, aggregated per group.  A fragment with
+        ``mapq >= quality_threshold`` and a length in ``[min_length, max_length]`` whose midpoint ``(start + end) >> 1``
+        lies ``d`` in ``[-half_width, half_width)`` from site ``i`` adds 1 to ``counts[groups[i], k]`` and its weight,
+        in units of 2^-16, to ``sums[groups[i], k]``, ``k = (d + half_width) // bin_size`` - counted from the other end
+        where ``flip[i]`` is set (a site on the - strand).  ``weighted=False``: every fragment weighs ``_lib.WEIGHT_ONE``
+        and the contig needs no weight column.  ``flip=None``: no site is flipped; ``groups=None``: all in group 0.  Sites
+        come in any order and are independent: one listed twice counts twice."""
+        c = np.ascontiguousarray(centres, dtype=np.int32)
+        fl = None if flip is None else np.ascontiguousarray(np.asarray(flip) != 0, dtype=np.uint8)
+        gr = None if groups is None else np.ascontiguousarray(groups, dtype=np.int32)
+        for other, what in ((fl, "flip"), (gr, "groups")):
+            if other is not None and other.shape != c.shape:
+                raise ValueError(f"{what} should have one entry per site")
+        n_bins = 2 * int(half_width) // max(int(bin_size), 1)
+        shape = (max(int(n_groups), 0), min(max(n_bins, 0), 4096))
+        sums, counts = np.zeros(shape, np.int64), np.zeros(shape, np.int64)
+        keep = np.empty(1, np.int64)  # (a pointer for outputs without an element: the call fails or writes nothing)
+        self._check(self.lib.ftk_site_profile(
+            self.ctx, self.contig_id(name), L.ptr(c) if len(c) else None, L.ptr(fl) if fl is not None and len(c) else None,
+            L.ptr(gr) if gr is not None and len(c) else None, len(c), int(n_groups), int(half_width), int(bin_size),
+            int(quality_threshold), -1 if min_length is None else int(min_length), -1 if max_length is None else int(max_length),
+            int(bool(weighted)), L.ptr(sums if sums.size else keep), L.ptr(counts if counts.size else keep)))
+        return sums, counts
+
     # -- WPS post-processing --------------------------------------------------------
     def wps_adjust(self, scores, offsets, median_window_size=1000, mean=False, edge_sub=None, savgol_window_size=21,
                    savgol_poly_deg=2, savgol=True, out=None):

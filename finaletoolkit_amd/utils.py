@@ -17,7 +17,7 @@ from .exceptions import InvalidInputError
 from .source import get_engine, open_source
 
 __all__ = ["chrom_sizes_to_list", "chrom_sizes_to_dict", "get_intervals", "overlaps", "frags_in_region", "frag_generator",
-           "frag_array", "frag_export", "frag_filter", "frag_gc_coverage", "gc_weights", "read_gc_bias_table", "read_region_mask", "agg_bw", "gen_kmers", "reverse_complement", "validate_compatible_contigs", "valid_interval",
+           "frag_array", "frag_export", "frag_filter", "frag_gc_coverage", "frag_site_profile", "read_sites", "gc_weights", "read_gc_bias_table", "read_region_mask", "agg_bw", "gen_kmers", "reverse_complement", "validate_compatible_contigs", "valid_interval",
            "_none_eq", "_none_geq", "_none_leq"]
 
 FragTuple = Tuple[str, int, int, int, bool]
@@ -690,6 +690,171 @@ def frag_gc_coverage(input_file, reference_file, interval_file, output_file=None
         writers.write_gc_coverage_rows(os.fspath(output_file), intervals, count, corrected)
     if verbose:
         sys.stderr.write(f"frag_gc_coverage: {len(intervals)} intervals in {time.time() - t0:.3f} s\n")
+    return res
+
+
+def read_sites(site_file) -> list[tuple[str, int, str, str]]:
+    """``(contig, centre, name, strand)`` per row of a ``.bed`` / ``.bed.gz`` file of sites: the lines ``get_intervals``
+    skips are skipped (``#`` / ``track`` / ``browser`` / blank lines, rows with < 3 columns); the centre is ``(start +
+    stop) // 2``, the name column 4 or ``'.'``, the strand ``'-'`` only when column 6 is ``-``, else ``'+'``."""
+    import gzip
+    import os
+    path = os.fspath(site_file)
+    sites = []
+    with (gzip.open(path, "rt") if path.endswith(".gz") else open(path, "r")) as bed:
+        for line in bed:
+            if line.startswith(("#", "track", "browser")) or not line.strip():
+                continue
+            parts = line.strip().split("\t")
+            if len(parts) < 3:
+                continue
+            sites.append((parts[0], (int(parts[1]) + int(parts[2])) // 2, parts[3] if len(parts) > 3 else ".",
+                          "-" if len(parts) > 5 and parts[5] == "-" else "+"))
+    return sites
+
+
+class SiteProfile(NamedTuple):
+    """Result of ``frag_site_profile``: one row of ``2 * half_width // bin_size`` bins per group of sites."""
+    groups: tuple             # names in order of first appearance (``by_name``), else ``("all",)``
+    n_sites: np.ndarray       # int64 per group: the sites used (those on contigs that were not skipped)
+    offsets: np.ndarray       # int64 per bin: its first offset from the site's centre, ``-half_width + k * bin_size``
+    count: np.ndarray         # int64 (n_groups, n_bins): fragment midpoints
+    corrected: np.ndarray     # float64 (n_groups, n_bins): the sum of their weights (``count`` without a reference)
+    skipped_contigs: tuple    # contigs with sites that the input, or the reference, does not hold
+
+
+SITE_PROFILE_MAX_BINS = 4096  # the bins one profile may have (``ftk_site_profile``)
+
+
+def _check_site_profile_args(output_file, reference_file, bias, half_width, bin_size, min_length, max_length, min_bias, stride):
+    if output_file is not None and not str(output_file).endswith((".tsv", ".tsv.gz")):
+        raise ValueError("output_file should have .tsv or .tsv.gz as suffix")
+    half_width, bin_size = int(half_width), int(bin_size)
+    if not 1 <= half_width <= 1 << 20:
+        raise ValueError(f"invalid half_width ({half_width}): between 1 and 2**20")
+    if bin_size < 1 or (2 * half_width) % bin_size:
+        raise ValueError(f"invalid bin_size ({bin_size}): it should divide 2 * half_width = {2 * half_width}")
+    if 2 * half_width // bin_size > SITE_PROFILE_MAX_BINS:
+        raise ValueError(f"{2 * half_width // bin_size} bins: at most {SITE_PROFILE_MAX_BINS} (a larger bin_size, or a smaller half_width)")
+    if reference_file is None:
+        if bias is not None:
+            raise ValueError("bias needs reference_file: without a reference the profile is not corrected")
+        if min_length is not None and max_length is not None and int(min_length) > int(max_length):
+            raise ValueError(f"invalid lengths: min_length ({min_length}) <= max_length ({max_length}) is required")
+    else:
+        _check_gc_coverage_args(None, bias, min_length, max_length, "midpoint", min_bias, stride)
+
+
+def frag_site_profile(input_file, site_file, output_file=None, reference_file=None, bias=None, half_width: int = 1000,
+                      bin_size: int = 1, min_length: int = 100, max_length: int = 220, quality_threshold: int = 30,
+                      by_name: bool = False, normalize: bool = False, min_bias: float = 0.05, stride: int = 1, workers=None,
+                      verbose=False) -> SiteProfile:
+    """Fragment-midpoint profile around the sites of ``site_file`` (``.bed`` / ``.bed.gz``, ``read_sites``), aggregated
+    over the sites and, with ``reference_file``, GC-corrected per fragment: the nucleosome profile Griffin computes around
+    transcription-factor binding sites, TSSs or open chromatin.
+
+    A fragment with ``mapq >= quality_threshold`` and a length in ``[min_length, max_length]`` whose midpoint ``(start +
+    end) >> 1`` lies ``d`` in ``[-half_width, half_width)`` from a site's centre counts in bin ``(d + half_width) //
+    bin_size`` of the site's group, counted from the other end for a site on the ``-`` strand, so that offsets run 5' to
+    3' of the site.  ``bin_size`` divides ``2 * half_width`` and gives at most 4096 bins.  Sites are independent: a
+    fragment near two sites counts for both.  ``by_name``: one group per name (column 4), in order of first appearance;
+    else one group ``"all"``.  Every fragment of a contig is eligible - a BAM and the fragment file exported from it give
+    the same profile.  The profile is accumulated as integers on the GPU, contig by contig as the input is decoded
+    (``Engine.site_profile``), and summed over the contigs on the host, so it is exact.
+
+    With ``reference_file`` (``.2bit`` / FASTA) every fragment weighs ``1 / bias[L - min_length, g]`` as in
+    ``frag_gc_coverage`` (``gc_weights``, ``min_bias``); ``bias`` is a ``GCBias``, the path of its TSV, or ``None`` - then
+    ``frag_gc_bias(input_file, reference_file, ...)`` runs first with the same lengths, MAPQ cut and ``stride``.  Without
+    a reference ``bias`` must be ``None`` and ``corrected`` equals ``count``.  ``normalize``: every group's ``corrected``
+    row is divided by its mean (a row whose mean is 0 stays 0).
+
+    Contigs with sites that the input does not hold, and - when correcting - contigs that the reference does not hold,
+    are skipped with one ``UserWarning`` each kind, listed in ``skipped_contigs`` and their sites left out of ``n_sites``.
+    ``output_file`` (``.tsv`` / ``.tsv.gz``): ``writers.write_site_profile_rows``."""
+    import os
+    import sys
+    import time
+    import warnings
+
+    from . import _lib as L
+    from . import writers
+    from .source import ContigFeed
+    _check_site_profile_args(output_file, reference_file, bias, half_width, bin_size, min_length, max_length, min_bias, stride)
+    H, b = int(half_width), int(bin_size)
+    n_bins = 2 * H // b
+    t0 = time.time()
+    sites = read_sites(site_file)  # read and checked before the input is walked for anything
+    if any(not 0 <= s[1] < COORD_BOUND for s in sites):
+        raise ValueError(f"{site_file}: a site's centre lies outside [0, 2**30)")
+    table = None
+    if reference_file is not None:
+        lo, hi = int(min_length), int(max_length)
+        if bias is None:
+            with warnings.catch_warnings():  # (contigs the reference lacks are reported once, below)
+                warnings.filterwarnings("ignore", message="frag_gc_bias: contigs not in the reference", category=UserWarning)
+                bias = frag_gc_bias(input_file, reference_file, None, None, lo, hi, quality_threshold, stride, None, workers, verbose)
+        elif not isinstance(bias, GCBias):
+            bias = read_gc_bias_table(bias, lo, hi)
+        table = gc_weights(bias, min_bias)
+    names: dict[str, int] = {}
+    if by_name:
+        for s in sites:
+            names.setdefault(s[2], len(names))
+    groups = tuple(names) if by_name else ("all",)
+    by_contig: dict[str, list[int]] = {}
+    for i, s in enumerate(sites):
+        by_contig.setdefault(s[0], []).append(i)
+    centre = np.array([s[1] for s in sites], dtype=np.int64)
+    flip = np.array([s[3] == "-" for s in sites], dtype=np.uint8)
+    group = np.array([names[s[2]] if by_name else 0 for s in sites], dtype=np.int32)
+    shape = (len(groups), n_bins)
+    count, units, n_sites = np.zeros(shape, np.int64), np.zeros(shape, np.int64), np.zeros(len(groups), np.int64)
+    no_reference, left = [], dict(by_contig)
+    if sites:
+        from contextlib import nullcontext
+
+        from .reference import ReferenceGenome
+        eng = get_engine()
+        feed = ContigFeed(input_file, workers, names=list(by_contig))
+        try:
+            with (ReferenceGenome(reference_file) if table is not None else nullcontext()) as ref:
+                for src, c in feed:
+                    idx = left.pop(c, None)
+                    if idx is None:
+                        continue
+                    if ref is not None and c not in ref.chroms:
+                        no_reference.append(c)
+                        continue
+                    key = src.key(c)
+                    idx = np.asarray(idx, dtype=np.int64)
+                    if ref is not None:
+                        rid = ref.device_image(eng, c, with_layout=True)
+                        eng.set_gc_weights(key, rid, int(min_length), int(max_length), table, quality_threshold)
+                    sums, counts = eng.site_profile(key, centre[idx], flip[idx], group[idx], len(groups), H, b, quality_threshold,
+                                                    min_length, max_length, weighted=ref is not None)
+                    units += sums
+                    count += counts
+                    n_sites += np.bincount(group[idx], minlength=len(groups))
+                    if verbose:
+                        sys.stderr.write(f"frag_site_profile: {c}: {len(idx)} sites, {int(counts.sum())} midpoints\n")
+                feed.finish()
+        except BaseException:
+            feed.close()
+            raise
+    if left:
+        warnings.warn("frag_site_profile: contigs not in the input were skipped: " + ", ".join(left), UserWarning)
+    if no_reference:
+        warnings.warn("frag_site_profile: contigs not in the reference were skipped: " + ", ".join(no_reference), UserWarning)
+    corrected = units / float(L.WEIGHT_ONE)
+    if normalize:
+        mean = corrected.mean(axis=1, keepdims=True)
+        corrected = np.divide(corrected, mean, out=np.zeros_like(corrected), where=mean != 0)
+    res = SiteProfile(groups, n_sites, -H + b * np.arange(n_bins, dtype=np.int64), count, corrected,
+                      tuple(left) + tuple(no_reference))
+    if output_file is not None:
+        writers.write_site_profile_rows(os.fspath(output_file), res)
+    if verbose:
+        sys.stderr.write(f"frag_site_profile: {len(sites)} sites in {time.time() - t0:.3f} s\n")
     return res
 
 

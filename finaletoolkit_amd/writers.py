@@ -294,3 +294,17 @@ def write_gc_coverage_rows(output_file: str, intervals, count, corrected) -> Non
     text = "".join([f"{c}\t{a}\t{b}\t{n}\t{int(k)}\t{'nan' if x != x else format(float(x), '.6f')}\n"
                     for (c, a, b, n), k, x in zip(intervals, count, corrected)])
     _emit(output_file, text, (".bed",), (".bed.gz",), message)
+
+
+def write_site_profile_rows(output_file: str, profile) -> None:
+    """``group n_sites offset count corrected`` per (group, bin) of a ``utils.SiteProfile`` behind the header line
+    ``#group n_sites offset count corrected``, in group order then bin order, ``corrected`` with six decimals; ``.tsv``
+    as text, ``.tsv.gz`` as gzip."""
+    message = "output_file should have .tsv or .tsv.gz as suffix"
+    if not output_file.endswith((".tsv", ".tsv.gz")):
+        raise ValueError(message)
+    rows = ["#group\tn_sites\toffset\tcount\tcorrected\n"]
+    for g, name in enumerate(profile.groups):
+        rows += [f"{name}\t{int(profile.n_sites[g])}\t{int(o)}\t{int(k)}\t{format(float(x), '.6f')}\n"
+                 for o, k, x in zip(profile.offsets, profile.count[g], profile.corrected[g])]
+    _emit(output_file, "".join(rows), (".tsv",), (".tsv.gz",), message)

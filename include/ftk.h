@@ -572,6 +572,29 @@ int ftk_frags_set_gc_weights(ftk_ctx* ctx, int contig_id, int ref_id, int32_t le
 int ftk_weighted_window_sums(ftk_ctx* ctx, int contig_id, const int32_t* w_start, const int32_t* w_end, int64_t n_win,
                              const ftk_filter* f, int64_t* sum_out, int64_t* n_weighted_out /* may be NULL */);
 
+/* ---- site-aggregated midpoint profiles (csrc/ftk_siteprofile.hip) ---------------------------------
+ * The profile of a resident contig's fragment midpoints around n_sites sites, aggregated per group of sites: site i has a
+ * centre centre[i] in [0, 2^30), a flip flag flip[i] (non-zero for a site on the - strand; NULL: none is flipped) and a
+ * group group[i] in [0, n_groups) (NULL: all in group 0).  n_bins = 2 * half_width / bin_size, which bin_size must
+ * divide; 1 <= half_width <= 2^20, n_bins <= 4096, n_groups * n_bins <= 2^28, 0 <= n_sites < 2^31.
+ *   A fragment passes with mapq >= mapq_min and min_len <= end - start <= max_len (closed; FTK_LEN_OPEN = no bound).
+ *   Its midpoint is m = (start + end) >> 1.  It contributes to site i when d = m - centre[i] lies in
+ *   [-half_width, half_width), in bin k = (d + half_width) / bin_size - bin n_bins - 1 - k of a flipped site:
+ *   count[group[i]][k] += 1 and sum[group[i]][k] += w, w being the fragment's weight (above) with use_weights, else
+ *   FTK_WEIGHT_ONE.
+ * Sites are independent: a fragment near two sites counts for both, a site listed twice counts twice; sites come in
+ * any order.  Every fragment of the contig is eligible - the read1 columns of a BAM contig play no part.  Bins that lie
+ * outside the contig stay 0.  The sites are HOST arrays; sum_out and count_out (may be NULL) are host or device arrays of
+ * n_groups * n_bins int64, row-major, overwritten (all 0 for n_sites == 0 or an empty contig).  The sums are integers, so
+ * every result is exact and independent of the order of arrival.
+ * FTK_ERR_INVALID for arguments outside the ranges above, a NULL centre (n_sites > 0) or sum_out, n_sites < 0, and for
+ * use_weights on a contig without a weights column; FTK_ERR_NO_CONTIG for an unknown contig.  A failing call writes to
+ * none of its outputs. */
+int ftk_site_profile(ftk_ctx* ctx, int contig_id, const int32_t* centre, const uint8_t* flip /* NULL: none */,
+                     const int32_t* group /* NULL: all 0 */, int64_t n_sites, int32_t n_groups, int32_t half_width,
+                     int32_t bin_size, int32_t mapq_min, int32_t min_len, int32_t max_len, int use_weights,
+                     int64_t* sum_out, int64_t* count_out /* may be NULL */);
+
 /* ---- BGZF inflate on the device -------------------------------------------------------------------
  * The streaming decoder's host threads spend most of a fragment file's decode in DEFLATE; BGZF blocks are
  * independent streams of at most 64 KB of data, decoded here one wavefront per block (csrc/ftk_inflate.hip).

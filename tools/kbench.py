@@ -3,7 +3,8 @@
 HIP events, interleaved repetitions.  usage: tools/kbench.py [contig_len] [reps]
 KBENCH=depth: the depth track (per base and run-length encoded) beside the cleavage profile of the same contig.
 KBENCH=gcbias: the observed and the expected length x GC table (lengths 100-220) against a synthetic 2bit image.
-KBENCH=gcweights: the GC weight column (lengths 100-220) and its sums per window beside ftk_window_counts on the same windows."""
+KBENCH=gcweights: the GC weight column (lengths 100-220) and its sums per window beside ftk_window_counts on the same windows.
+KBENCH=siteprofile: the midpoint profile of 10 000 sites (H = 990, b = 15) beside ftk_weighted_window_sums over the same sites x bins windows."""
 import os
 import sys
 
@@ -234,6 +235,58 @@ if "gcweights" in which:
         timeit(lambda: eng.window_counts("c", one_lo, one_hi, 30, out=cov[:1]), "window_counts one window", 9 * n)
     sums(ws, we)
     print("gcweights checksum", int(d_sum.sum().item()), int(d_cnt.sum().item()), "counts", int(eng.window_counts("c", ws, we, 30).sum()))
+if "siteprofile" in which:
+    # Site profile: 10 000 random sites, H = 990, b = 15 (132 bins), one group, unweighted and weighted, outputs on the
+    # device - the whole call (sites sorted and cut into runs on the host, three small uploads, the kernel, one wait).
+    # Beside it the only route there was before: ftk_weighted_window_sums over the same n_sites x n_bins windows, whose
+    # per-window sums, added up over the sites, are the same profile (the checksum line).  Byte floors: 9 B (start, end,
+    # mapq) per candidate - the fragments the position index hands each site, counted here from the sorted starts -
+    # and 13 B with the weight; the windows route reads 13 B per candidate of every one of its windows.  The sites reach
+    # a few tens of MB of the columns, so repeated calls find them in the Infinity Cache: the COLD lines evict first.
+    import ctypes as C
+    from finaletoolkit_amd import _lib as L
+    rng = np.random.default_rng(11)
+    H, B, NS = 990, 15, 10_000
+    nb = 2 * H // B
+    centres = rng.integers(H, size - H, NS).astype(np.int32)
+    eng.set_weights("c", rng.integers(1, 1 << 20, n, dtype=np.int64).astype(np.uint32))
+    lmax = eng.info("c")[1]
+    hs = s.cpu().numpy().astype(np.int64)
+    c64 = centres.astype(np.int64)
+    cand = int((np.searchsorted(hs, ((c64 + H >> 9) + 1) << 9, side="left")
+                - np.searchsorted(hs, (np.maximum(c64 - H - lmax, 0) >> 9) << 9, side="left")).sum())
+    w_lo = (c64[:, None] - H + B * np.arange(nb)[None, :]).reshape(-1)
+    w_cand = int((np.searchsorted(hs, ((w_lo + B >> 9) + 1) << 9, side="left")
+                  - np.searchsorted(hs, (np.maximum(w_lo - lmax, 0) >> 9) << 9, side="left")).sum())
+    w_lo32, w_hi32 = w_lo.astype(np.int32), (w_lo + B).astype(np.int32)
+    d_psum = torch.zeros(nb, dtype=torch.int64, device=dev)
+    d_pcnt = torch.zeros(nb, dtype=torch.int64, device=dev)
+    d_wsum = torch.zeros(NS * nb, dtype=torch.int64, device=dev)
+    d_wcnt = torch.zeros(NS * nb, dtype=torch.int64, device=dev)
+    flt = L.make_filter(30, None, None, "midpoint")
+
+    def profile(weighted):
+        eng._check(eng.lib.ftk_site_profile(eng.ctx, eng.contig_id("c"), L.ptr(centres), None, None, NS, 1, H, B, 30, -1, -1,
+                                            int(weighted), L.ptr(d_psum), L.ptr(d_pcnt)))
+
+    def windows():
+        eng._check(eng.lib.ftk_weighted_window_sums(eng.ctx, eng.contig_id("c"), L.ptr(w_lo32), L.ptr(w_hi32), NS * nb, C.byref(flt),
+                                                    L.ptr(d_wsum), L.ptr(d_wcnt)))
+    print(f"siteprofile: {n} fragments, {NS} sites x {nb} bins, {cand} candidates ({cand / NS:.0f} per site); the windows route: "
+          f"{NS * nb} windows, {w_cand} candidates", flush=True)
+    for _ in range(2):  # twice: the spread between the two passes is the noise
+        timeit(lambda: profile(False), "site profile, unweighted", 9 * cand)
+        timeit(lambda: profile(True), "site profile, weighted", 13 * cand)
+        timeit(lambda: windows(), "weighted sums, sites x bins", 13 * w_cand)
+        timeit(lambda: profile(False), "site profile, unweighted COLD", 9 * cand, cold="read")
+        timeit(lambda: profile(True), "site profile, weighted COLD", 13 * cand, cold="read")
+        timeit(lambda: windows(), "weighted sums, s x b COLD", 13 * w_cand, cold="read")
+    profile(True)
+    windows()
+    torch.cuda.synchronize()
+    route = d_wsum.view(NS, nb).sum(0)
+    print("siteprofile checksum", int(d_psum.sum().item()), int(route.sum().item()), "bins equal", bool(torch.equal(d_psum, route)),
+          "midpoints", int(d_pcnt.sum().item()))
 if "gc" in which:
     rng = np.random.default_rng(6)
     packed = rng.integers(0, 256, (size + 3) // 4, dtype=np.uint8)
