@@ -189,6 +189,20 @@ class Engine:
             self._next_id += 1
         return self._ids[name]
 
+    def _load(self, name: str, call):
+        """Run ``call(cid)``, the C calls of one load into ``name``'s id.  A refused load leaves no contig under the
+        name: the library drops the id's old columns before it validates the new ones (upload_common), so the name
+        goes too, whether it was new or a reload.  Its id is spent; a later load of the name gets a fresh one."""
+        cid = self._new_id(name)
+        try:
+            call(cid)
+        except Exception:
+            self._ids.pop(name, None)
+            self._bam.pop(name, None)
+            self.lib.ftk_frags_release(self.ctx, cid)  # (refused before the drop, or after the columns went in)
+            raise
+        return cid
+
     def contig_id(self, name: str) -> int:
         if name not in self._ids:
             raise KeyError(name)
@@ -213,30 +227,29 @@ class Engine:
         n = len(start)
         if not (len(end) == n and len(mapq) == n and (strand is None or len(strand) == n)):
             raise ValueError("fragment columns differ in length")
-        cid = self._new_id(name)
-        self._check(self.lib.ftk_frags_from_host(self.ctx, cid, L.ptr(start), L.ptr(end), L.ptr(mapq),
-                                                 L.ptr(strand), n))
-        self._bam[name] = False
-        if r1_start is not None:
-            r1s = np.ascontiguousarray(r1_start, dtype=np.int32)
-            r1e = np.ascontiguousarray(r1_end, dtype=np.int32)
-            self._check(self.lib.ftk_frags_set_read1(self.ctx, cid, L.ptr(r1s), L.ptr(r1e), n))
-            self._bam[name] = True
+        r1s = None if r1_start is None else np.ascontiguousarray(r1_start, dtype=np.int32)
+        r1e = None if r1_start is None else np.ascontiguousarray(r1_end, dtype=np.int32)
+
+        def call(cid):
+            self._check(self.lib.ftk_frags_from_host(self.ctx, cid, L.ptr(start), L.ptr(end), L.ptr(mapq),
+                                                     L.ptr(strand), n))
+            if r1s is not None:
+                self._check(self.lib.ftk_frags_set_read1(self.ctx, cid, L.ptr(r1s), L.ptr(r1e), n))
+        cid = self._load(name, call)
+        self._bam[name] = r1s is not None
         return cid
 
     def load_contig_from_table(self, name: str, table, index: int, is_bam: bool):
         """Upload contig ``index`` of a decoded ``ftk_fragtable`` (page-locked columns -> HBM)."""
-        cid = self._new_id(name)
-        self._check(self.lib.ftk_frags_from_table(self.ctx, cid, table, int(index)))
+        cid = self._load(name, lambda cid: self._check(self.lib.ftk_frags_from_table(self.ctx, cid, table, int(index))))
         # an empty BAM contig carries no read1 columns: plain fetch mode is equivalent
         self._bam[name] = bool(is_bam) and self.lib.ftk_fragtable_contig_rows(table, int(index)) > 0
         return cid
 
     def load_contig_device(self, name: str, d_start, d_end, d_mapq, d_strand, n: int):
         """Adopt columns already in HBM (torch tensors or raw device addresses)."""
-        cid = self._new_id(name)
-        self._check(self.lib.ftk_frags_from_device(self.ctx, cid, L.ptr(d_start), L.ptr(d_end), L.ptr(d_mapq),
-                                                   L.ptr(d_strand), int(n)))
+        cid = self._load(name, lambda cid: self._check(self.lib.ftk_frags_from_device(
+            self.ctx, cid, L.ptr(d_start), L.ptr(d_end), L.ptr(d_mapq), L.ptr(d_strand), int(n))))
         self._bam[name] = False
         return cid
 
