@@ -65,6 +65,7 @@ EXPORTS = [
     "ftk_frag_gc", "ftk_frag_gc_table", "ftk_ref_gc_table",
     "ftk_frags_set_weights", "ftk_frags_weights", "ftk_frags_set_gc_weights", "ftk_weighted_window_sums",
     "ftk_site_profile",
+    "ftk_site_vplot",
 ]
 
 
@@ -339,6 +340,7 @@ def load() -> C.CDLL:
     lib.ftk_frags_set_gc_weights.argtypes = [vp, C.c_int, C.c_int, i32, i32, i32, vp, vp]
     lib.ftk_weighted_window_sums.argtypes = [vp, C.c_int, vp, vp, i64, C.POINTER(Filter), vp, vp]
     lib.ftk_site_profile.argtypes = [vp, C.c_int, vp, vp, vp, i64, i32, i32, i32, i32, i32, i32, C.c_int, vp, vp]
+    lib.ftk_site_vplot.argtypes = [vp, C.c_int, vp, vp, vp, i64, i32, i32, i32, i32, i32, i32, i32, C.c_int, vp, vp]
     lib.ftk_comm_unique_id.argtypes = [C.c_char_p]
     lib.ftk_comm_create.argtypes = [vp, C.c_int, C.c_int, C.c_char_p, C.POINTER(vp)]
     lib.ftk_comm_size.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]

@@ -1271,3 +1271,4 @@ static int wps_params(ftk_ctx* ctx, const ContigData& c, int64_t chrom_size, int
 #include "ftk_api_gcbias.inc"
 #include "ftk_api_weights.inc"
 #include "ftk_api_siteprofile.inc"
+#include "ftk_api_vplot.inc"

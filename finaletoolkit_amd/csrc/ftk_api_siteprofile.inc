@@ -1,13 +1,15 @@
 // Part of ftk_api.hip's translation unit (#included there behind the weights part) - the site-aggregated midpoint
 // profile of a resident contig (`ftk_site_profile`) over the kernel of ftk_siteprofile.hip: the call checks its
 // arguments, sorts the sites by (group, centre), cuts them into runs of one group each and launches one workgroup per run.
+// The checks of the site list and of the offset axis, and the plan of runs, are shared with ftk_site_vplot
+// (ftk_api_vplot.inc).
 #include "ftk_siteprofile.h"
 
-extern "C" {
+namespace {
 
-int ftk_site_profile(ftk_ctx* ctx, int contig_id, const int32_t* centre, const uint8_t* flip, const int32_t* group, int64_t n_sites,
-                     int32_t n_groups, int32_t half_width, int32_t bin_size, int32_t mapq_min, int32_t min_len, int32_t max_len,
-                     int use_weights, int64_t* sum_out, int64_t* count_out) {
+// The checks every site call starts with, in this order: the context, the site count, the pointers, the offset axis.
+int check_site_axis(ftk_ctx* ctx, int64_t n_sites, const int32_t* centre, const int64_t* sum_out, int32_t half_width,
+                    int32_t bin_size, int* n_bins) {
     if (!ctx) return fail(nullptr, FTK_ERR_INVALID, "ctx is NULL");
     if (n_sites < 0 || n_sites > INT32_MAX) return fail(ctx, FTK_ERR_INVALID, "n_sites out of range");
     if (n_sites > 0 && !centre) return fail(ctx, FTK_ERR_INVALID, "NULL centre pointer");
@@ -16,35 +18,40 @@ int ftk_site_profile(ftk_ctx* ctx, int contig_id, const int32_t* centre, const u
         return fail(ctx, FTK_ERR_INVALID, "half_width %d out of range [1, %d]", half_width, kSiteMaxHalfWidth);
     if (bin_size < 1 || (2 * half_width) % bin_size != 0)
         return fail(ctx, FTK_ERR_INVALID, "bin_size %d does not divide 2 * half_width = %d", bin_size, 2 * half_width);
-    const int n_bins = 2 * half_width / bin_size;
-    if (n_bins > kSiteMaxBins) return fail(ctx, FTK_ERR_INVALID, "%d bins: at most %d", n_bins, kSiteMaxBins);
-    if (n_groups < 1 || (int64_t)n_groups * n_bins > (1 << 28))
-        return fail(ctx, FTK_ERR_INVALID, "n_groups %d out of range (n_groups * n_bins <= 2^28)", n_groups);
-    if (is_device_ptr(centre) || is_device_ptr(flip) || is_device_ptr(group))
-        return fail(ctx, FTK_ERR_INVALID, "the sites must be host arrays");
-    ContigData* c;
-    int rc = get_contig(ctx, contig_id, &c);
-    if (rc) return rc;
-    if (use_weights && !c->weights) return no_weights(ctx, contig_id);
-    // the sites as sortable words: group, then centre, then the flip flag (which takes no part in the order that matters)
-    std::vector<uint64_t> keys((size_t)n_sites);
-    for (int64_t i = 0; i < n_sites; ++i) {
-        const int32_t g = group ? group[i] : 0;
-        if (centre[i] < 0 || centre[i] >= kPadCoord)
-            return fail(ctx, FTK_ERR_INVALID, "site %lld: centre %d outside [0, 2^30)", (long long)i, centre[i]);
-        if (g < 0 || g >= n_groups)
-            return fail(ctx, FTK_ERR_INVALID, "site %lld: group %d outside [0, %d)", (long long)i, g, n_groups);
-        keys[(size_t)i] = (uint64_t)g << 32 | (uint64_t)centre[i] << 1 | (uint64_t)(flip && flip[i]);
-    }
-    std::sort(keys.begin(), keys.end());
-    const ftk_filter f{mapq_min, min_len, max_len, FTK_POLICY_MIDPOINT, FTK_FETCH_TABIX};
-    const SiteProfileParams p{half_width, bin_size, n_bins, mapq_min, min_len < 0 ? INT32_MIN : min_len,
-                              max_len < 0 ? INT32_MAX : max_len, eff_lmax(&f, *c), use_weights != 0};
-    // runs: at most per_run sites, never across a group's end
-    std::vector<uint32_t> words((size_t)n_sites);
+    *n_bins = 2 * half_width / bin_size;
+    if (*n_bins > kSiteMaxBins) return fail(ctx, FTK_ERR_INVALID, "%d bins: at most %d", *n_bins, kSiteMaxBins);
+    return FTK_OK;
+}
+
+// The sites of one call as the kernels take them: 32-bit words sorted by (group, centre), cut into runs that stay inside
+// one group; and their temporaries in the call's scratch.
+struct SitePlan {
+    std::vector<uint64_t> keys;   // group, then centre, then the flip flag (which takes no part in the order that matters)
+    std::vector<uint32_t> words;  // the centre with the flip flag on top (kSiteFlipBit), in key order
     std::vector<int32_t> run_off, run_group;
-    if (n_sites > 0 && c->n > 0) {
-        const long long per_run = site_run_sites(ctx->n_cu, n_sites, c->n, c->max_end, p);
+    uint32_t* d_words = nullptr;
+    int32_t *d_off = nullptr, *d_group = nullptr;
+    size_t n_runs() const { return run_group.size(); }
+
+    // checks every site and sorts them
+    int sort(ftk_ctx* ctx, const int32_t* centre, const uint8_t* flip, const int32_t* group, int64_t n_sites, int32_t n_groups) {
+        keys.resize((size_t)n_sites);
+        for (int64_t i = 0; i < n_sites; ++i) {
+            const int32_t g = group ? group[i] : 0;
+            if (centre[i] < 0 || centre[i] >= kPadCoord)
+                return fail(ctx, FTK_ERR_INVALID, "site %lld: centre %d outside [0, 2^30)", (long long)i, centre[i]);
+            if (g < 0 || g >= n_groups)
+                return fail(ctx, FTK_ERR_INVALID, "site %lld: group %d outside [0, %d)", (long long)i, g, n_groups);
+            keys[(size_t)i] = (uint64_t)g << 32 | (uint64_t)centre[i] << 1 | (uint64_t)(flip && flip[i]);
+        }
+        std::sort(keys.begin(), keys.end());
+        return FTK_OK;
+    }
+    // runs: at most per_run sites, never across a group's end (per_run <= 0: no runs - an empty contig)
+    void cut(long long per_run) {
+        const int64_t n_sites = (int64_t)keys.size();
+        words.resize(keys.size());
+        if (n_sites == 0 || per_run <= 0) return;
         for (int64_t i = 0; i < n_sites; ++i) {
             const int32_t g = (int32_t)(keys[(size_t)i] >> 32);
             if (run_group.empty() || g != run_group.back() || i - run_off.back() >= per_run) {
@@ -56,34 +63,65 @@ int ftk_site_profile(ftk_ctx* ctx, int contig_id, const int32_t* centre, const u
         }
         run_off.push_back((int32_t)n_sites);
     }
-    const size_t n_runs = run_group.size(), cells = (size_t)n_groups * (size_t)n_bins;
+    // (behind the call's outputs; the plan must not move between this and Scratch::reserve)
+    void declare(Scratch& s) {
+        if (!n_runs()) return;
+        s.tmp(&d_words, words.size());
+        s.tmp(&d_off, n_runs() + 1);
+        s.tmp(&d_group, n_runs());
+    }
+    // the uploads read the vectors above (pageable): the caller waits for the stream on every way out
+    int upload(ftk_ctx* ctx) {
+        HIPCHK(ctx, hipMemcpyAsync(d_words, words.data(), words.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+        HIPCHK(ctx, hipMemcpyAsync(d_off, run_off.data(), (n_runs() + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
+        HIPCHK(ctx, hipMemcpyAsync(d_group, run_group.data(), n_runs() * 4, hipMemcpyHostToDevice, ctx->stream));
+        return FTK_OK;
+    }
+};
+
+}  // namespace
+
+extern "C" {
+
+int ftk_site_profile(ftk_ctx* ctx, int contig_id, const int32_t* centre, const uint8_t* flip, const int32_t* group, int64_t n_sites,
+                     int32_t n_groups, int32_t half_width, int32_t bin_size, int32_t mapq_min, int32_t min_len, int32_t max_len,
+                     int use_weights, int64_t* sum_out, int64_t* count_out) {
+    int n_bins = 0;
+    int rc = check_site_axis(ctx, n_sites, centre, sum_out, half_width, bin_size, &n_bins);
+    if (rc) return rc;
+    if (n_groups < 1 || (int64_t)n_groups * n_bins > (1 << 28))
+        return fail(ctx, FTK_ERR_INVALID, "n_groups %d out of range (n_groups * n_bins <= 2^28)", n_groups);
+    if (is_device_ptr(centre) || is_device_ptr(flip) || is_device_ptr(group))
+        return fail(ctx, FTK_ERR_INVALID, "the sites must be host arrays");
+    ContigData* c;
+    if ((rc = get_contig(ctx, contig_id, &c))) return rc;
+    if (use_weights && !c->weights) return no_weights(ctx, contig_id);
+    SitePlan plan;
+    if ((rc = plan.sort(ctx, centre, flip, group, n_sites, n_groups))) return rc;
+    const ftk_filter f{mapq_min, min_len, max_len, FTK_POLICY_MIDPOINT, FTK_FETCH_TABIX};
+    const SiteProfileParams p{half_width, bin_size, n_bins, mapq_min, min_len < 0 ? INT32_MIN : min_len,
+                              max_len < 0 ? INT32_MAX : max_len, eff_lmax(&f, *c), use_weights != 0};
+    plan.cut(n_sites > 0 && c->n > 0 ? site_run_sites(ctx->n_cu, n_sites, c->n, c->max_end, p) : 0);
+    const size_t n_runs = plan.n_runs(), cells = (size_t)n_groups * (size_t)n_bins;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     int64_t *d_sum = nullptr, *d_cnt = nullptr;
-    uint32_t* d_words = nullptr;
-    int32_t *d_off = nullptr, *d_group = nullptr;
     Scratch s(ctx);
     s.out(&d_sum, sum_out, cells);
     if (count_out) s.out(&d_cnt, count_out, cells);
-    if (n_runs) {
-        s.tmp(&d_words, (size_t)n_sites);
-        s.tmp(&d_off, n_runs + 1);
-        s.tmp(&d_group, n_runs);
-    }
+    plan.declare(s);
     if ((rc = s.reserve())) return rc;
     HIPCHK(ctx, hipMemsetAsync(d_sum, 0, cells * 8, ctx->stream));
     if (d_cnt) HIPCHK(ctx, hipMemsetAsync(d_cnt, 0, cells * 8, ctx->stream));
-    // From here on the stream may be reading the vectors above (pageable staging of this call): every way out, an error's
-    // included, waits for the stream first.
+    // From here on the stream may be reading the plan's vectors (pageable staging of this call): every way out, an
+    // error's included, waits for the stream first.
     auto enqueue = [&]() -> int {
         if (!n_runs) return FTK_OK;
-        HIPCHK(ctx, hipMemcpyAsync(d_words, words.data(), (size_t)n_sites * 4, hipMemcpyHostToDevice, ctx->stream));
-        HIPCHK(ctx, hipMemcpyAsync(d_off, run_off.data(), (n_runs + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
-        HIPCHK(ctx, hipMemcpyAsync(d_group, run_group.data(), n_runs * 4, hipMemcpyHostToDevice, ctx->stream));
+        if (int e = plan.upload(ctx)) return e;
         // at most kSiteMaxRunsPerLaunch workgroups per launch: a grid of any workgroup size stays below 2^32 threads
         for (size_t r0 = 0; r0 < n_runs; r0 += kSiteMaxRunsPerLaunch) {
             const int part = (int)std::min(n_runs - r0, (size_t)kSiteMaxRunsPerLaunch);
-            launch_site_profile(ctx->stream, c->v, c->weights, d_words, d_off + r0, d_group + r0, part, p, (unsigned long long*)d_sum,
-                                (unsigned long long*)d_cnt);
+            launch_site_profile(ctx->stream, c->v, c->weights, plan.d_words, plan.d_off + r0, plan.d_group + r0, part, p,
+                                (unsigned long long*)d_sum, (unsigned long long*)d_cnt);
             HIPCHK(ctx, hipGetLastError());
         }
         return FTK_OK;

@@ -36,6 +36,10 @@ struct SiteProfileParams {
 // about kSiteRunCandidates candidates at the contig's mean density, no more than leaves kSiteRunsPerCu runs per compute unit, and
 // few enough that a bin's 32-bit LDS count cannot wrap (a site adds at most n_frag to a bin).
 long long site_run_sites(int n_cu, long long n_sites, long long n_frag, int max_end, const SiteProfileParams& p);
+// The same rule with the caller's own numbers: `run_candidates` candidates per run, and runs of `groups_per_run`
+// workgroups each (kSiteRunsPerCu workgroups per compute unit are kept, not runs).
+long long site_run_sites_of(int n_cu, long long n_sites, long long n_frag, int max_end, int half_width, int lmax,
+                            long long run_candidates, long long groups_per_run);
 
 // Run r = sites [run_off[r], run_off[r + 1]) of `site` (sorted by group, then centre), all of group run_group[r]:
 // sum[run_group[r] * n_bins + k] and cnt[...] (may be NULL) += the run's profile; both zeroed by the caller.  `weights`

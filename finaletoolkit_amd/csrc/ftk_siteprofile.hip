@@ -95,13 +95,19 @@ __global__ __launch_bounds__(kSiteThreads) void site_profile_kernel(ContigView c
 
 }  // namespace
 
-long long site_run_sites(int n_cu, long long n_sites, long long n_frag, int max_end, const SiteProfileParams& p) {
-    const double reach = 2.0 * p.half_width + p.lmax + 2.0 * (1 << kBinShift);  // what the index hands one site
+long long site_run_sites_of(int n_cu, long long n_sites, long long n_frag, int max_end, int half_width, int lmax,
+                            long long run_candidates, long long groups_per_run) {
+    const double reach = 2.0 * half_width + lmax + 2.0 * (1 << kBinShift);  // what the index hands one site
     const double est = std::max(1.0, std::min((double)n_frag, (double)n_frag / std::max(max_end, 1) * reach));
-    long long per_run = (long long)((double)kSiteRunCandidates / est) + 1;
-    per_run = std::min(per_run, (n_sites + kSiteRunsPerCu * n_cu - 1) / (kSiteRunsPerCu * n_cu));
+    long long per_run = (long long)((double)run_candidates / est) + 1;
+    const long long runs = std::max((kSiteRunsPerCu * n_cu + groups_per_run - 1) / groups_per_run, 1LL);
+    per_run = std::min(per_run, (n_sites + runs - 1) / runs);
     per_run = std::min(per_run, (long long)(0xffffffffLL / std::max(n_frag, 1LL)));
     return std::max(per_run, 1LL);
+}
+
+long long site_run_sites(int n_cu, long long n_sites, long long n_frag, int max_end, const SiteProfileParams& p) {
+    return site_run_sites_of(n_cu, n_sites, n_frag, max_end, p.half_width, p.lmax, kSiteRunCandidates, 1);
 }
 
 void launch_site_profile(hipStream_t s, const ContigView& cv, const uint32_t* weights, const uint32_t* site, const int32_t* run_off,

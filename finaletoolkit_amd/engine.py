@@ -847,6 +847,37 @@ class Engine:
             int(bool(weighted)), L.ptr(sums if sums.size else keep), L.ptr(counts if counts.size else keep)))
         return sums, counts
 
+    # -- fragment length x offset maps around sites (csrc/ftk_vplot.hip) ----------------
+    def site_vplot(self, name: str, centres: Sequence, flip=None, groups=None, n_groups: int = 1, half_width: int = 500,
+                   bin_size: int = 5, len_lo: int = 50, len_hi: int = 349, len_bin: int = 5, mapq_min=30, weighted: bool = False):
+        """``(sums, counts)`` int64 of shape ``(n_groups, n_rows, n_bins)`` (``ftk_site_vplot``), ``n_rows = (len_hi -
+        len_lo + 1) // len_bin`` and ``n_bins = 2 * half_width // bin_size``: the V-plot of resident contig ``name``
+        around the sites ``centres``, aggregated per group.  A fragment with ``mapq >= mapq_min`` and a length ``L`` in
+        ``[len_lo, len_hi]`` whose midpoint ``(start + end) >> 1`` lies ``d`` in ``[-half_width, half_width)`` from site
+        ``i`` adds 1 to ``counts[groups[i], r, k]`` and its weight, in units of 2^-16, to ``sums[groups[i], r, k]``, ``r
+        = (L - len_lo) // len_bin`` and ``k = (d + half_width) // bin_size`` - ``k`` counted from the other end where
+        ``flip[i]`` is set; the length axis is never reversed.  ``weighted``, ``flip``, ``groups`` and the sites' order:
+        as in ``site_profile``."""
+        c = np.ascontiguousarray(centres, dtype=np.int32)
+        fl = None if flip is None else np.ascontiguousarray(np.asarray(flip) != 0, dtype=np.uint8)
+        gr = None if groups is None else np.ascontiguousarray(groups, dtype=np.int32)
+        for other, what in ((fl, "flip"), (gr, "groups")):
+            if other is not None and other.shape != c.shape:
+                raise ValueError(f"{what} should have one entry per site")
+        n_bins = 2 * int(half_width) // max(int(bin_size), 1)
+        n_rows = (int(len_hi) - int(len_lo) + 1) // max(int(len_bin), 1)
+        shape = [max(int(n_groups), 0), min(max(n_rows, 0), 4096), min(max(n_bins, 0), 4096)]
+        if shape[0] * shape[1] * shape[2] > 1 << 28:  # (the call fails and writes nothing)
+            shape[0] = 0
+        sums, counts = np.zeros(shape, np.int64), np.zeros(shape, np.int64)
+        keep = np.empty(1, np.int64)  # (a pointer for outputs without an element: the call fails or writes nothing)
+        self._check(self.lib.ftk_site_vplot(
+            self.ctx, self.contig_id(name), L.ptr(c) if len(c) else None, L.ptr(fl) if fl is not None and len(c) else None,
+            L.ptr(gr) if gr is not None and len(c) else None, len(c), int(n_groups), int(half_width), int(bin_size),
+            int(len_lo), int(len_hi), int(len_bin), int(mapq_min), int(bool(weighted)), L.ptr(sums if sums.size else keep),
+            L.ptr(counts if counts.size else keep)))
+        return sums, counts
+
     # -- WPS post-processing --------------------------------------------------------
     def wps_adjust(self, scores, offsets, median_window_size=1000, mean=False, edge_sub=None, savgol_window_size=21,
                    savgol_poly_deg=2, savgol=True, out=None):

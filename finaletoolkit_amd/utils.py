@@ -17,7 +17,7 @@ from .exceptions import InvalidInputError
 from .source import get_engine, open_source
 
 __all__ = ["chrom_sizes_to_list", "chrom_sizes_to_dict", "get_intervals", "overlaps", "frags_in_region", "frag_generator",
-           "frag_array", "frag_export", "frag_filter", "frag_gc_coverage", "frag_site_profile", "read_sites", "gc_weights", "read_gc_bias_table", "read_region_mask", "agg_bw", "gen_kmers", "reverse_complement", "validate_compatible_contigs", "valid_interval",
+           "frag_array", "frag_export", "frag_filter", "frag_gc_coverage", "frag_site_profile", "frag_vplot", "VPlot", "read_sites", "gc_weights", "read_gc_bias_table", "read_region_mask", "agg_bw", "gen_kmers", "reverse_complement", "validate_compatible_contigs", "valid_interval",
            "_none_eq", "_none_geq", "_none_leq"]
 
 FragTuple = Tuple[str, int, int, int, bool]
@@ -774,18 +774,50 @@ def frag_site_profile(input_file, site_file, output_file=None, reference_file=No
     import os
     import sys
     import time
-    import warnings
 
     from . import _lib as L
     from . import writers
-    from .source import ContigFeed
     _check_site_profile_args(output_file, reference_file, bias, half_width, bin_size, min_length, max_length, min_bias, stride)
     H, b = int(half_width), int(bin_size)
     n_bins = 2 * H // b
     t0 = time.time()
+
+    def one_contig(eng, key, centre, flip, group, n_groups, weighted):
+        return eng.site_profile(key, centre, flip, group, n_groups, H, b, quality_threshold, min_length, max_length, weighted=weighted)
+    groups, n_sites, count, units, skipped, n_read = _sites_over_contigs(
+        "frag_site_profile", one_contig, (n_bins,), input_file, site_file, reference_file, bias, min_length, max_length,
+        quality_threshold, by_name, min_bias, stride, workers, verbose)
+    corrected = units / float(L.WEIGHT_ONE)
+    if normalize:
+        mean = corrected.mean(axis=1, keepdims=True)
+        corrected = np.divide(corrected, mean, out=np.zeros_like(corrected), where=mean != 0)
+    res = SiteProfile(groups, n_sites, -H + b * np.arange(n_bins, dtype=np.int64), count, corrected, skipped)
+    if output_file is not None:
+        writers.write_site_profile_rows(os.fspath(output_file), res)
+    if verbose:
+        sys.stderr.write(f"frag_site_profile: {n_read} sites in {time.time() - t0:.3f} s\n")
+    return res
+
+
+def _sites_over_contigs(what, one_contig, cell_shape, input_file, site_file, reference_file, bias, min_length, max_length,
+                        quality_threshold, by_name, min_bias, stride, workers, verbose, max_cells=None):
+    """The driver ``frag_site_profile`` and ``frag_vplot`` share: the sites read and grouped, the bias table made ready,
+    one ``ContigFeed`` pass with ``set_gc_weights`` per contig when there is a reference, ``one_contig(eng, key, centre,
+    flip, group, n_groups, weighted) -> (sums, counts)`` of shape ``(n_groups,) + cell_shape`` per contig summed on the
+    host, and the two warnings (named after ``what``).  ``max_cells``: the cells all groups together may have, checked
+    once the site file has given the groups.  Returns ``(groups, n_sites, count, units, skipped_contigs,
+    sites read)``."""
+    import sys
+    import warnings
+
+    from .source import ContigFeed
     sites = read_sites(site_file)  # read and checked before the input is walked for anything
     if any(not 0 <= s[1] < COORD_BOUND for s in sites):
         raise ValueError(f"{site_file}: a site's centre lies outside [0, 2**30)")
+    if max_cells is not None:
+        n_groups = max(len({s[2] for s in sites}), 1) if by_name else 1
+        if n_groups * int(np.prod(cell_shape)) > max_cells:
+            raise ValueError(f"{n_groups} groups of {' x '.join(str(n) for n in cell_shape)} cells: at most {max_cells} cells in all")
     table = None
     if reference_file is not None:
         lo, hi = int(min_length), int(max_length)
@@ -807,7 +839,7 @@ def frag_site_profile(input_file, site_file, output_file=None, reference_file=No
     centre = np.array([s[1] for s in sites], dtype=np.int64)
     flip = np.array([s[3] == "-" for s in sites], dtype=np.uint8)
     group = np.array([names[s[2]] if by_name else 0 for s in sites], dtype=np.int32)
-    shape = (len(groups), n_bins)
+    shape = (len(groups),) + tuple(cell_shape)
     count, units, n_sites = np.zeros(shape, np.int64), np.zeros(shape, np.int64), np.zeros(len(groups), np.int64)
     no_reference, left = [], dict(by_contig)
     if sites:
@@ -830,31 +862,96 @@ def frag_site_profile(input_file, site_file, output_file=None, reference_file=No
                     if ref is not None:
                         rid = ref.device_image(eng, c, with_layout=True)
                         eng.set_gc_weights(key, rid, int(min_length), int(max_length), table, quality_threshold)
-                    sums, counts = eng.site_profile(key, centre[idx], flip[idx], group[idx], len(groups), H, b, quality_threshold,
-                                                    min_length, max_length, weighted=ref is not None)
+                    sums, counts = one_contig(eng, key, centre[idx], flip[idx], group[idx], len(groups), ref is not None)
                     units += sums
                     count += counts
                     n_sites += np.bincount(group[idx], minlength=len(groups))
                     if verbose:
-                        sys.stderr.write(f"frag_site_profile: {c}: {len(idx)} sites, {int(counts.sum())} midpoints\n")
+                        sys.stderr.write(f"{what}: {c}: {len(idx)} sites, {int(counts.sum())} midpoints\n")
                 feed.finish()
         except BaseException:
             feed.close()
             raise
     if left:
-        warnings.warn("frag_site_profile: contigs not in the input were skipped: " + ", ".join(left), UserWarning)
+        warnings.warn(f"{what}: contigs not in the input were skipped: " + ", ".join(left), UserWarning)
     if no_reference:
-        warnings.warn("frag_site_profile: contigs not in the reference were skipped: " + ", ".join(no_reference), UserWarning)
+        warnings.warn(f"{what}: contigs not in the reference were skipped: " + ", ".join(no_reference), UserWarning)
+    return groups, n_sites, count, units, tuple(left) + tuple(no_reference), len(sites)
+
+
+class VPlot(NamedTuple):
+    """Result of ``frag_vplot``: per group of sites, ``n_rows`` length rows of ``2 * half_width // bin_size`` offset bins."""
+    groups: tuple             # names in order of first appearance (``by_name``), else ``("all",)``
+    n_sites: np.ndarray       # int64 per group: the sites used (those on contigs that were not skipped)
+    offsets: np.ndarray       # int64 per bin: its first offset from the site's centre, ``-half_width + k * bin_size``
+    lengths: np.ndarray       # int64 per row: its first length, ``min_length + r * length_bin``
+    count: np.ndarray         # int64 (n_groups, n_rows, n_bins): fragment midpoints
+    corrected: np.ndarray     # float64 (n_groups, n_rows, n_bins): the sum of their weights (``count`` without a reference)
+    skipped_contigs: tuple    # contigs with sites that the input, or the reference, does not hold
+
+
+VPLOT_MAX_ROWS = 4096     # the length rows one matrix may have (``ftk_site_vplot``)
+VPLOT_MAX_CELLS = 1 << 28  # groups x rows x bins of one call
+
+
+def _check_vplot_args(output_file, reference_file, bias, half_width, bin_size, min_length, max_length, length_bin, min_bias, stride):
+    if min_length is None or max_length is None:
+        raise ValueError("invalid lengths: min_length and max_length bound the length axis and cannot be None")
+    _check_site_profile_args(output_file, reference_file, bias, half_width, bin_size, min_length, max_length, min_bias, stride)
+    lo, hi, lb = int(min_length), int(max_length), int(length_bin)
+    if not 0 <= lo <= hi < 1 << 16:
+        raise ValueError(f"invalid lengths: 0 <= min_length ({lo}) <= max_length ({hi}) < 2**16 is required")
+    if lb < 1 or (hi - lo + 1) % lb:
+        raise ValueError(f"invalid length_bin ({lb}): it should divide max_length - min_length + 1 = {hi - lo + 1}")
+    if (hi - lo + 1) // lb > VPLOT_MAX_ROWS:
+        raise ValueError(f"{(hi - lo + 1) // lb} length rows: at most {VPLOT_MAX_ROWS} (a larger length_bin, or a narrower range)")
+
+
+def frag_vplot(input_file, site_file, output_file=None, reference_file=None, bias=None, half_width: int = 500, bin_size: int = 5,
+               min_length: int = 50, max_length: int = 349, length_bin: int = 5, quality_threshold: int = 30,
+               by_name: bool = False, normalize: bool = False, min_bias: float = 0.05, stride: int = 1, workers=None,
+               verbose=False) -> VPlot:
+    """V-plot around the sites of ``site_file`` (``.bed`` / ``.bed.gz``, ``read_sites``): fragment length against the
+    midpoint's offset from the site, aggregated over the sites and, with ``reference_file``, GC-corrected per fragment.
+    It shows whether the signal at a binding site comes from nucleosome-sized fragments flanking it or from short
+    sub-nucleosomal ones sitting on the factor itself - what ``frag_site_profile``, with its one axis, cannot.
+
+    A fragment with ``mapq >= quality_threshold`` and a length ``L`` in ``[min_length, max_length]`` whose midpoint
+    ``(start + end) >> 1`` lies ``d`` in ``[-half_width, half_width)`` from a site's centre counts in row ``(L -
+    min_length) // length_bin`` and column ``(d + half_width) // bin_size`` of the site's group - the column counted from
+    the other end for a site on the ``-`` strand; the length axis is never reversed.  ``bin_size`` divides ``2 *
+    half_width`` and gives at most 4096 bins; ``length_bin`` divides ``max_length - min_length + 1`` and gives at most
+    4096 rows; groups x rows x bins is at most 2**28.  Sites, groups (``by_name``), skipped contigs, the bias (``bias``,
+    ``min_bias``, ``stride``) and exactness are as in ``frag_site_profile``: one pass over the input, one
+    ``Engine.site_vplot`` call per contig, summed on the host.  ``normalize``: every group's ``corrected`` matrix is
+    divided by its mean (a matrix whose mean is 0 stays 0).  ``output_file`` (``.tsv`` / ``.tsv.gz``):
+    ``writers.write_vplot_rows``."""
+    import os
+    import sys
+    import time
+
+    from . import _lib as L
+    from . import writers
+    _check_vplot_args(output_file, reference_file, bias, half_width, bin_size, min_length, max_length, length_bin, min_bias, stride)
+    H, b, lo, hi, lb = int(half_width), int(bin_size), int(min_length), int(max_length), int(length_bin)
+    n_bins, n_rows = 2 * H // b, (hi - lo + 1) // lb
+    t0 = time.time()
+
+    def one_contig(eng, key, centre, flip, group, n_groups, weighted):
+        return eng.site_vplot(key, centre, flip, group, n_groups, H, b, lo, hi, lb, quality_threshold, weighted=weighted)
+    groups, n_sites, count, units, skipped, n_read = _sites_over_contigs(
+        "frag_vplot", one_contig, (n_rows, n_bins), input_file, site_file, reference_file, bias, lo, hi, quality_threshold,
+        by_name, min_bias, stride, workers, verbose, VPLOT_MAX_CELLS)
     corrected = units / float(L.WEIGHT_ONE)
     if normalize:
-        mean = corrected.mean(axis=1, keepdims=True)
+        mean = corrected.mean(axis=(1, 2), keepdims=True)
         corrected = np.divide(corrected, mean, out=np.zeros_like(corrected), where=mean != 0)
-    res = SiteProfile(groups, n_sites, -H + b * np.arange(n_bins, dtype=np.int64), count, corrected,
-                      tuple(left) + tuple(no_reference))
+    res = VPlot(groups, n_sites, -H + b * np.arange(n_bins, dtype=np.int64), lo + lb * np.arange(n_rows, dtype=np.int64), count,
+                corrected, skipped)
     if output_file is not None:
-        writers.write_site_profile_rows(os.fspath(output_file), res)
+        writers.write_vplot_rows(os.fspath(output_file), res)
     if verbose:
-        sys.stderr.write(f"frag_site_profile: {len(sites)} sites in {time.time() - t0:.3f} s\n")
+        sys.stderr.write(f"frag_vplot: {n_read} sites in {time.time() - t0:.3f} s\n")
     return res
 
 

@@ -308,3 +308,19 @@ def write_site_profile_rows(output_file: str, profile) -> None:
         rows += [f"{name}\t{int(profile.n_sites[g])}\t{int(o)}\t{int(k)}\t{format(float(x), '.6f')}\n"
                  for o, k, x in zip(profile.offsets, profile.count[g], profile.corrected[g])]
     _emit(output_file, "".join(rows), (".tsv",), (".tsv.gz",), message)
+
+
+def write_vplot_rows(output_file: str, vplot) -> None:
+    """``group n_sites length offset count corrected`` per cell of a ``utils.VPlot`` behind the header line ``#group
+    n_sites length offset count corrected``, in group order, then row order, then bin order, ``corrected`` with six
+    decimals; ``.tsv`` as text, ``.tsv.gz`` as gzip."""
+    message = "output_file should have .tsv or .tsv.gz as suffix"
+    if not output_file.endswith((".tsv", ".tsv.gz")):
+        raise ValueError(message)
+    rows = ["#group\tn_sites\tlength\toffset\tcount\tcorrected\n"]
+    for g, name in enumerate(vplot.groups):
+        head = f"{name}\t{int(vplot.n_sites[g])}\t"
+        for r, length in enumerate(vplot.lengths):
+            rows += [f"{head}{int(length)}\t{int(o)}\t{int(k)}\t{format(float(x), '.6f')}\n"
+                     for o, k, x in zip(vplot.offsets, vplot.count[g, r], vplot.corrected[g, r])]
+    _emit(output_file, "".join(rows), (".tsv",), (".tsv.gz",), message)

@@ -595,6 +595,30 @@ int ftk_site_profile(ftk_ctx* ctx, int contig_id, const int32_t* centre, const u
                      int32_t bin_size, int32_t mapq_min, int32_t min_len, int32_t max_len, int use_weights,
                      int64_t* sum_out, int64_t* count_out /* may be NULL */);
 
+/* ---- fragment length x midpoint offset maps around sites: the V-plot (csrc/ftk_vplot.hip) ----------
+ * ftk_site_profile with a second axis.  Sites are as there: centre centre[i] in [0, 2^30), flip flag flip[i], group
+ * group[i] in [0, n_groups).
+ *   Offset axis: half_width = H lies in [1, 2^20]; bin_size = b divides 2 H; n_bins = 2 H / b <= 4096.
+ *   Length axis: closed bounds 0 <= len_lo <= len_hi < 2^16; len_bin = lb >= 1 divides len_hi - len_lo + 1; n_rows =
+ *   (len_hi - len_lo + 1) / lb <= 4096; n_groups * n_rows * n_bins <= 2^28.
+ *   A fragment passes with mapq >= mapq_min and len_lo <= L = end - start <= len_hi.  Its midpoint is m = (start + end)
+ *   >> 1.  It contributes to site i when d = m - centre[i] lies in [-H, H): to row r = (L - len_lo) / lb and column k =
+ *   (d + H) / b - column n_bins - 1 - k when flip[i] is set; the flip reverses the offset axis only, never the length
+ *   axis.  count[group[i]][r][k] += 1 and sum[group[i]][r][k] += w, w being the weight column's entry with use_weights,
+ *   else FTK_WEIGHT_ONE.
+ * Everything else is as in ftk_site_profile: sites are independent, repeats count twice, a fragment near two sites
+ * counts for both; cells with nothing in them stay 0; there is no read1 fetch rule, so a BAM and the fragment file
+ * exported from it give the same matrix; the sums are integers and exact whatever the order of arrival.  The sites are
+ * HOST arrays; sum_out and count_out (may be NULL) are host or device arrays of n_groups * n_rows * n_bins int64,
+ * row-major [group][row][bin], overwritten (all 0 for n_sites == 0 or an empty contig).
+ * FTK_ERR_INVALID for arguments outside the ranges above, a NULL centre (n_sites > 0) or sum_out, n_sites < 0, and for
+ * use_weights on a contig without a weights column; FTK_ERR_NO_CONTIG for an unknown contig.  A failing call writes to
+ * none of its outputs. */
+int ftk_site_vplot(ftk_ctx* ctx, int contig_id, const int32_t* centre, const uint8_t* flip /* NULL: none */,
+                   const int32_t* group /* NULL: all 0 */, int64_t n_sites, int32_t n_groups, int32_t half_width,
+                   int32_t bin_size, int32_t len_lo, int32_t len_hi, int32_t len_bin, int32_t mapq_min, int use_weights,
+                   int64_t* sum_out, int64_t* count_out /* may be NULL */);
+
 /* ---- BGZF inflate on the device -------------------------------------------------------------------
  * The streaming decoder's host threads spend most of a fragment file's decode in DEFLATE; BGZF blocks are
  * independent streams of at most 64 KB of data, decoded here one wavefront per block (csrc/ftk_inflate.hip).

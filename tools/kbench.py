@@ -4,7 +4,8 @@ HIP events, interleaved repetitions.  usage: tools/kbench.py [contig_len] [reps]
 KBENCH=depth: the depth track (per base and run-length encoded) beside the cleavage profile of the same contig.
 KBENCH=gcbias: the observed and the expected length x GC table (lengths 100-220) against a synthetic 2bit image.
 KBENCH=gcweights: the GC weight column (lengths 100-220) and its sums per window beside ftk_window_counts on the same windows.
-KBENCH=siteprofile: the midpoint profile of 10 000 sites (H = 990, b = 15) beside ftk_weighted_window_sums over the same sites x bins windows."""
+KBENCH=siteprofile: the midpoint profile of 10 000 sites (H = 990, b = 15) beside ftk_weighted_window_sums over the same sites x bins windows.
+KBENCH=vplot: the length x offset map of the same sites (lengths 100-399 in 60 rows of 5) beside 60 calls of ftk_site_profile, one per row."""
 import os
 import sys
 
@@ -287,6 +288,61 @@ if "siteprofile" in which:
     route = d_wsum.view(NS, nb).sum(0)
     print("siteprofile checksum", int(d_psum.sum().item()), int(route.sum().item()), "bins equal", bool(torch.equal(d_psum, route)),
           "midpoints", int(d_pcnt.sum().item()))
+if "vplot" in which:
+    # V-plot: the siteprofile mode's contig and sites (KBENCH_VPLOT_SITES of them, 10 000 by default; KBENCH_VPLOT_ROWS=0
+    # leaves the rows route out, for experiments with many sites), H = 990, b = 15
+    # (132 bins), lengths 100-399 in 5-bp rows (60 rows), one group, unweighted and weighted, outputs on the device - the
+    # whole call.  Beside it the only route there was before: one ftk_site_profile call per row with that row's min_len /
+    # max_len, 60 calls, each sorting and uploading the sites again and reading every candidate again.  Byte floors: 9 B
+    # (13 B weighted) per candidate of ONE pass over the sites - the fragments the position index hands each site with
+    # the call's longest passing length; the matrix reads them once per tile of rows, the rows route once per row.
+    import ctypes as C
+    from finaletoolkit_amd import _lib as L
+    rng = np.random.default_rng(11)
+    H, B, NS = 990, 15, int(os.environ.get("KBENCH_VPLOT_SITES", "10000"))
+    LO, HI, LB = 100, 399, 5
+    nb, nr = 2 * H // B, (HI - LO + 1) // LB
+    centres = rng.integers(H, size - H, NS).astype(np.int32)
+    eng.set_weights("c", rng.integers(1, 1 << 20, n, dtype=np.int64).astype(np.uint32))
+    lmax = min(eng.info("c")[1], HI)
+    hs = s.cpu().numpy().astype(np.int64)
+    c64 = centres.astype(np.int64)
+    cand = int((np.searchsorted(hs, ((c64 + H >> 9) + 1) << 9, side="left")
+                - np.searchsorted(hs, (np.maximum(c64 - H - lmax, 0) >> 9) << 9, side="left")).sum())
+    d_vsum = torch.zeros(nr * nb, dtype=torch.int64, device=dev)
+    d_vcnt = torch.zeros(nr * nb, dtype=torch.int64, device=dev)
+    d_rsum = torch.zeros(nr * nb, dtype=torch.int64, device=dev)
+    d_rcnt = torch.zeros(nr * nb, dtype=torch.int64, device=dev)
+    cid = eng.contig_id("c")
+    ROWS = os.environ.get("KBENCH_VPLOT_ROWS", "1") != "0"
+
+    def vplot(weighted):
+        eng._check(eng.lib.ftk_site_vplot(eng.ctx, cid, L.ptr(centres), None, None, NS, 1, H, B, LO, HI, LB, 30, int(weighted),
+                                          L.ptr(d_vsum), L.ptr(d_vcnt)))
+
+    def rows(weighted):
+        for r in range(nr):
+            eng._check(eng.lib.ftk_site_profile(eng.ctx, cid, L.ptr(centres), None, None, NS, 1, H, B, 30, LO + r * LB, LO + (r + 1) * LB - 1,
+                                                int(weighted), d_rsum.data_ptr() + r * nb * 8, d_rcnt.data_ptr() + r * nb * 8))
+    print(f"vplot: {n} fragments, {NS} sites x {nr} rows x {nb} bins, {cand} candidates per pass ({cand / NS:.0f} per site); "
+          f"the rows route: {nr} calls of ftk_site_profile", flush=True)
+    for _ in range(2):  # twice: the spread between the two passes is the noise
+        timeit(lambda: vplot(False), "vplot, unweighted", 9 * cand)
+        timeit(lambda: vplot(True), "vplot, weighted", 13 * cand)
+        timeit(lambda: vplot(False), "vplot, unweighted COLD", 9 * cand, cold="read")
+        timeit(lambda: vplot(True), "vplot, weighted COLD", 13 * cand, cold="read")
+        if ROWS:
+            timeit(lambda: rows(False), "60 profiles, unweighted", 9 * cand)
+            timeit(lambda: rows(True), "60 profiles, weighted", 13 * cand)
+            timeit(lambda: rows(False), "60 profiles, unw. COLD", 9 * cand, cold="read")
+            timeit(lambda: rows(True), "60 profiles, weighted COLD", 13 * cand, cold="read")
+    for weighted in (False, True) if ROWS else ():
+        vplot(weighted)
+        rows(weighted)
+        torch.cuda.synchronize()
+        print("vplot checksum", "weighted" if weighted else "unweighted", int(d_vsum.sum().item()), int(d_rsum.sum().item()),
+              "stacked profiles equal the matrix", bool(torch.equal(d_vsum, d_rsum) and torch.equal(d_vcnt, d_rcnt)),
+              "midpoints", int(d_vcnt.sum().item()))
 if "gc" in which:
     rng = np.random.default_rng(6)
     packed = rng.integers(0, 256, (size + 3) // 4, dtype=np.uint8)
