@@ -32,6 +32,7 @@ OPEN_HI = 2 ** 31 - 1
 LEN_OPEN = -1
 GC_MAX_LEN = 1000  # FTK_GC_MAX_LEN
 WEIGHT_ONE = 65536  # FTK_WEIGHT_ONE
+SPECTRUM_TILE = 16 << 10  # kSpectrumLdsSamples: a run of up to this many samples is folded out of LDS, a longer one from memory
 POLICY = {"midpoint": 0, "any": 1}
 POLICY_FETCH = 2  # no intersect test: the index query alone (AlignmentWrapper.fetch)
 FETCH_TABIX = 0
@@ -66,6 +67,7 @@ EXPORTS = [
     "ftk_frags_set_weights", "ftk_frags_weights", "ftk_frags_set_gc_weights", "ftk_weighted_window_sums",
     "ftk_site_profile",
     "ftk_site_vplot",
+    "ftk_track_spectrum", "ftk_wps_spectrum",
 ]
 
 
@@ -341,6 +343,8 @@ def load() -> C.CDLL:
     lib.ftk_weighted_window_sums.argtypes = [vp, C.c_int, vp, vp, i64, C.POINTER(Filter), vp, vp]
     lib.ftk_site_profile.argtypes = [vp, C.c_int, vp, vp, vp, i64, i32, i32, i32, i32, i32, i32, C.c_int, vp, vp]
     lib.ftk_site_vplot.argtypes = [vp, C.c_int, vp, vp, vp, i64, i32, i32, i32, i32, i32, i32, i32, C.c_int, vp, vp]
+    lib.ftk_track_spectrum.argtypes = [vp, vp, vp, i64, vp, i32, C.c_double, C.c_int, vp, vp]
+    lib.ftk_wps_spectrum.argtypes = [vp, C.c_int, vp, vp, i64, i64, i32, i32, i32, i32, vp, i32, C.c_double, C.c_int, i64, vp, vp]
     lib.ftk_comm_unique_id.argtypes = [C.c_char_p]
     lib.ftk_comm_create.argtypes = [vp, C.c_int, C.c_int, C.c_char_p, C.POINTER(vp)]
     lib.ftk_comm_size.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]

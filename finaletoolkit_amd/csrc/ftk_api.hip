@@ -1272,3 +1272,4 @@ static int wps_params(ftk_ctx* ctx, const ContigData& c, int64_t chrom_size, int
 #include "ftk_api_weights.inc"
 #include "ftk_api_siteprofile.inc"
 #include "ftk_api_vplot.inc"
+#include "ftk_api_spectrum.inc"

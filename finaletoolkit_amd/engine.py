@@ -878,6 +878,53 @@ class Engine:
             L.ptr(counts if counts.size else keep)))
         return sums, counts
 
+    # -- periodograms of score runs (csrc/ftk_spectrum.hip) --------------------------------
+    @staticmethod
+    def _spectrum_outputs(n_iv, periods, out, ssw_out):
+        """The periods as int32 and the two outputs of a spectrum call: fresh host arrays, or the caller's float64
+        ``out`` (``n_iv * n_per * 2`` elements: re, im) and ``ssw_out`` (``n_iv``) - host arrays or device tensors."""
+        per = np.ascontiguousarray(periods, dtype=np.int32).reshape(-1)
+        res = np.zeros((n_iv, len(per)), np.complex128) if out is None else out
+        ssw = np.zeros(n_iv, np.float64) if ssw_out is None else ssw_out
+        return per, res, ssw
+
+    def track_spectrum(self, scores, offsets, periods, taper=0.1, detrend=True, out=None, ssw_out=None):
+        """``(spectrum complex128 [n_iv, n_per], ssw float64 [n_iv])`` of the int64 score runs
+        ``scores[offsets[i]:offsets[i+1]]`` at the integer ``periods`` (``ftk_track_spectrum``; the rule is in
+        ``include/ftk.h``): each run less its mean (``detrend``) under a split cosine bell of fraction ``taper``, summed
+        against ``exp(-2j pi (n mod p) / p)`` in float64; ``ssw`` is the bell's sum of squares, so ``abs(spectrum) ** 2 /
+        ssw`` is the power.  ``scores``: a host array, a device tensor or a device address.  A ``(run, period)`` value
+        does not depend on what else the call asks for."""
+        offs = np.ascontiguousarray(offsets, dtype=np.int64)
+        n_iv = max(len(offs) - 1, 0)
+        if not (isinstance(scores, (int, np.integer)) or hasattr(scores, "data_ptr")):
+            scores = np.ascontiguousarray(scores, dtype=np.int64)
+        per, res, ssw = self._spectrum_outputs(n_iv, periods, out, ssw_out)
+        keep = np.empty(1, np.int64)  # (a pointer for arrays without an element: the call fails or reads nothing)
+        self._check(self.lib.ftk_track_spectrum(
+            self.ctx, L.ptr(int(scores) if isinstance(scores, np.integer) else scores), L.ptr(offs if len(offs) else keep), n_iv,
+            L.ptr(per if len(per) else keep.view(np.int32)), len(per), float(taper), int(bool(detrend)), L.ptr(res), L.ptr(ssw)))
+        return res, ssw
+
+    def wps_spectrum(self, name: str, starts, stops, chrom_size: int, periods, window_size=120, min_length=120,
+                     max_length=180, quality_threshold=30, taper=0.1, detrend=True, batch_bases=None, out=None, ssw_out=None):
+        """``track_spectrum`` of the WPS of the intervals ``[starts[i], stops[i])`` of resident contig ``name``
+        (``ftk_wps_spectrum``): the scores of ``wps_intervals`` with the same arguments, written to device scratch and
+        transformed there, ``batch_bases`` bases of intervals at a time (``None``: the library's choice) - no per-base
+        value reaches the host.  The same bits as ``track_spectrum(*wps_intervals(...), periods, ...)``."""
+        s = np.ascontiguousarray(starts, dtype=np.int64)
+        e = np.ascontiguousarray(stops, dtype=np.int64)
+        if s.shape != e.shape:
+            raise ValueError("starts and stops differ in length")
+        per, res, ssw = self._spectrum_outputs(len(s), periods, out, ssw_out)
+        keep = np.empty(1, np.int64)
+        self._check(self.lib.ftk_wps_spectrum(
+            self.ctx, self.contig_id(name), L.ptr(s if len(s) else keep), L.ptr(e if len(s) else keep), len(s), int(chrom_size),
+            int(window_size), int(min_length), int(max_length), int(quality_threshold),
+            L.ptr(per if len(per) else keep.view(np.int32)), len(per), float(taper), int(bool(detrend)),
+            0 if batch_bases is None else int(batch_bases), L.ptr(res), L.ptr(ssw)))
+        return res, ssw
+
     # -- WPS post-processing --------------------------------------------------------
     def wps_adjust(self, scores, offsets, median_window_size=1000, mean=False, edge_sub=None, savgol_window_size=21,
                    savgol_poly_deg=2, savgol=True, out=None):

@@ -17,7 +17,7 @@ from .exceptions import InvalidInputError
 from .source import get_engine, open_source
 
 __all__ = ["chrom_sizes_to_list", "chrom_sizes_to_dict", "get_intervals", "overlaps", "frags_in_region", "frag_generator",
-           "frag_array", "frag_export", "frag_filter", "frag_gc_coverage", "frag_site_profile", "frag_vplot", "VPlot", "read_sites", "gc_weights", "read_gc_bias_table", "read_region_mask", "agg_bw", "gen_kmers", "reverse_complement", "validate_compatible_contigs", "valid_interval",
+           "frag_array", "frag_export", "frag_filter", "frag_gc_coverage", "frag_site_profile", "frag_vplot", "VPlot", "frag_wps_spectrum", "WpsSpectrum", "read_sites", "gc_weights", "read_gc_bias_table", "read_region_mask", "agg_bw", "gen_kmers", "reverse_complement", "validate_compatible_contigs", "valid_interval",
            "_none_eq", "_none_geq", "_none_leq"]
 
 FragTuple = Tuple[str, int, int, int, bool]
@@ -952,6 +952,123 @@ def frag_vplot(input_file, site_file, output_file=None, reference_file=None, bia
         writers.write_vplot_rows(os.fspath(output_file), res)
     if verbose:
         sys.stderr.write(f"frag_vplot: {n_read} sites in {time.time() - t0:.3f} s\n")
+    return res
+
+
+class WpsSpectrum(NamedTuple):
+    """Result of ``frag_wps_spectrum``, one row per interval of the interval file, in its order."""
+    intervals: list           # (contig, start, stop, name)
+    periods: np.ndarray       # int64: min_period .. max_period
+    power: np.ndarray         # float64 (n_intervals, n_periods): (re^2 + im^2) / ssw; NaN for an empty interval
+    band_mean: np.ndarray     # float64 per interval: the mean of ``power`` over the periods inside ``band``
+    n_bases: np.ndarray       # int64 per interval: the bases transformed, ``max(stop - start, 0)``
+
+
+SPECTRUM_MAX_PERIODS = 1024          # periods of one call (``ftk_wps_spectrum``)
+SPECTRUM_PERIOD_RANGE = (2, 4096)
+SPECTRUM_MAX_BASES = 1 << 22         # bases of one interval
+
+
+def _is_alignment_file(input_file) -> bool:
+    import os
+    return isinstance(input_file, (str, os.PathLike)) and str(input_file).endswith((".sam", ".bam", ".cram"))
+
+
+def _check_wps_spectrum_args(input_file, chrom_sizes, output_file, min_period, max_period, band, taper):
+    if output_file is not None and not str(output_file).endswith((".tsv", ".tsv.gz")):
+        raise ValueError("output_file should have .tsv or .tsv.gz as suffix")
+    lo, hi = int(min_period), int(max_period)
+    if lo > hi:
+        raise ValueError(f"invalid periods: min_period ({lo}) is above max_period ({hi})")
+    if lo < SPECTRUM_PERIOD_RANGE[0] or hi > SPECTRUM_PERIOD_RANGE[1]:
+        raise ValueError(f"invalid periods: [{lo}, {hi}] leaves the range {SPECTRUM_PERIOD_RANGE[0]} .. {SPECTRUM_PERIOD_RANGE[1]}")
+    if hi - lo + 1 > SPECTRUM_MAX_PERIODS:
+        raise ValueError(f"invalid periods: {hi - lo + 1} of them, at most {SPECTRUM_MAX_PERIODS}")
+    try:
+        b0, b1 = (int(b) for b in band)
+    except (TypeError, ValueError):
+        raise ValueError(f"invalid band ({band!r}): a pair of periods") from None
+    if not lo <= b0 <= b1 <= hi:
+        raise ValueError(f"invalid band ({b0}, {b1}): it should lie inside the periods [{lo}, {hi}]")
+    if not 0.0 <= float(taper) <= 0.5:
+        raise ValueError(f"invalid taper ({taper}): a fraction in [0, 0.5]")
+    if chrom_sizes is None and not _is_alignment_file(input_file):
+        raise ValueError("chrom_sizes must be specified for BED/Fragment files")
+
+
+def frag_wps_spectrum(input_file, interval_file, chrom_sizes=None, output_file=None, min_period: int = 120, max_period: int = 280,
+                      band=(193, 199), window_size: int = 120, min_length: int = 120, max_length: int = 180,
+                      quality_threshold: int = 30, taper: float = 0.1, workers=None, verbose=False) -> WpsSpectrum:
+    """Periodicity of the windowed protection score over every interval of ``interval_file`` (BED; gene bodies, as a rule):
+    the periodogram of the interval's WPS at every integer period from ``min_period`` to ``max_period`` bases, and its
+    mean over ``band`` - the 193-199 bp intensity that follows nucleosome spacing and, through it, expression and
+    tissue of origin.
+
+    Per interval, the WPS of ``frag.wps`` with the same ``window_size``, lengths and ``quality_threshold`` has its mean
+    removed, is tapered by a split cosine bell over a fraction ``taper`` of the interval at either end, and is summed
+    against ``exp(-2j pi (n mod p) / p)`` for every period ``p``, all in float64 (the rule: ``include/ftk.h``,
+    "spectrum").  ``power = |X_p|^2 / sum(bell^2)``; an empty interval has ``power = nan``.  The scores are written and
+    transformed on the GPU, contig by contig as the input is decoded (``Engine.wps_spectrum``): no per-base value comes
+    back to the host.  Strand is ignored - power is unchanged by reversing a run.
+
+    Chromosome sizes (the WPS ignores fragments that leave the contig): the BAM header, else the ``chrom_sizes`` file,
+    else ``ValueError``.  An interval on a contig the input lacks raises ``ValueError``, as in ``frag.coverage``; an
+    interval of more than 2**22 bases raises too.  ``output_file`` (``.tsv`` / ``.tsv.gz``):
+    ``writers.write_wps_spectrum_rows``."""
+    import os
+    import sys
+    import time
+
+    from . import writers
+    from .source import ContigFeed
+    _check_wps_spectrum_args(input_file, chrom_sizes, output_file, min_period, max_period, band, taper)
+    t0 = time.time()
+    periods = np.arange(int(min_period), int(max_period) + 1, dtype=np.int64)
+    sizes = None if _is_alignment_file(input_file) else chrom_sizes_to_dict(chrom_sizes)
+    intervals = get_intervals(interval_file)
+    by_contig: dict[str, list[int]] = {}
+    for i, iv in enumerate(intervals):
+        by_contig.setdefault(iv[0], []).append(i)
+    starts = np.array([iv[1] for iv in intervals], dtype=np.int64)
+    stops = np.array([iv[2] for iv in intervals], dtype=np.int64)
+    n_bases = np.maximum(stops - starts, 0)
+    if len(n_bases) and int(n_bases.max()) > SPECTRUM_MAX_BASES:
+        raise ValueError(f"interval {intervals[int(n_bases.argmax())][:3]} holds more than {SPECTRUM_MAX_BASES} bases")
+    if sizes is not None:
+        for c in by_contig:
+            if c not in sizes:
+                raise ValueError(f"{c} is not in chrom_sizes")
+    spectrum = np.zeros((len(intervals), len(periods)), np.complex128)
+    ssw = np.zeros(len(intervals), np.float64)
+    left = dict(by_contig)
+    eng = get_engine()
+    feed = ContigFeed(input_file, workers, names=list(by_contig))
+    try:
+        for src, c in feed:
+            idx = left.pop(c, None)
+            if idx is None:
+                continue
+            size = int(src.lengths[c]) if sizes is None else int(sizes[c])
+            spectrum[idx], ssw[idx] = eng.wps_spectrum(src.key(c), starts[idx], stops[idx], size, periods, window_size, min_length,
+                                                       max_length, quality_threshold, taper, True)
+            if verbose:
+                sys.stderr.write(f"frag_wps_spectrum: {c}: {len(idx)} intervals, {int(n_bases[idx].sum())} bases\n")
+        src = feed.finish()
+    except BaseException:
+        feed.close()
+        raise
+    for c in left:  # contigs the file does not hold: the ValueError of frag.coverage
+        src.require(c)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        power = (spectrum.real ** 2 + spectrum.imag ** 2) / ssw[:, None]
+    power[(ssw == 0) | (n_bases == 0)] = np.nan
+    in_band = (periods >= int(band[0])) & (periods <= int(band[1]))
+    band_mean = power[:, in_band].mean(axis=1) if len(intervals) else np.zeros(0)
+    res = WpsSpectrum(intervals, periods, power, band_mean, n_bases)
+    if output_file is not None:
+        writers.write_wps_spectrum_rows(os.fspath(output_file), res)
+    if verbose:
+        sys.stderr.write(f"frag_wps_spectrum: {len(intervals)} intervals in {time.time() - t0:.3f} s\n")
     return res
 
 

@@ -324,3 +324,19 @@ def write_vplot_rows(output_file: str, vplot) -> None:
             rows += [f"{head}{int(length)}\t{int(o)}\t{int(k)}\t{format(float(x), '.6f')}\n"
                      for o, k, x in zip(vplot.offsets, vplot.count[g, r], vplot.corrected[g, r])]
     _emit(output_file, "".join(rows), (".tsv",), (".tsv.gz",), message)
+
+
+def write_wps_spectrum_rows(output_file: str, spectrum) -> None:
+    """One row per interval of a ``utils.WpsSpectrum``, in its order, behind the header line ``contig start stop name
+    n_bases band_mean p<min> ... p<max>``: the interval, its bases, the band's mean power and the power at every period,
+    floats with six significant digits or ``nan``; ``.tsv`` as text, ``.tsv.gz`` as gzip."""
+    message = "output_file should have .tsv or .tsv.gz as suffix"
+    if not output_file.endswith((".tsv", ".tsv.gz")):
+        raise ValueError(message)
+
+    def num(x):
+        return "nan" if x != x else format(float(x), ".6g")
+    rows = ["\t".join(["contig", "start", "stop", "name", "n_bases", "band_mean"] + [f"p{int(p)}" for p in spectrum.periods]) + "\n"]
+    for (c, a, b, name), n, mean, row in zip(spectrum.intervals, spectrum.n_bases, spectrum.band_mean, spectrum.power):
+        rows.append("\t".join([str(c), str(a), str(b), str(name), str(int(n)), num(mean)] + [num(x) for x in row]) + "\n")
+    _emit(output_file, "".join(rows), (".tsv",), (".tsv.gz",), message)

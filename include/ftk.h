@@ -783,6 +783,43 @@ int ftk_bigwig_fixedstep_sections(uint32_t chrom_id, const int64_t* iv_start, co
                                   int n_threads, char** out, int64_t* out_len, int64_t* n_sections_out,
                                   int64_t** section_table_out, double** section_stats_out);
 
+/* ---- spectrum: the periodogram of integer score runs at integer periods ----------------------------
+ * What the WPS is read for downstream of the per-base track: its periodicity over a gene body (the intensity at
+ * 120-280 bp, the 193-199 bp band above all).  Computed on the device, so that no per-base value crosses to the host.
+ *
+ * THE RULE.  A run is N integer scores v[0..N) of one region, n = base - region start.  For an integer period p in bases:
+ *     m    = detrend ? (sum v) / N : 0             (the sum exact in int64, one float64 division)
+ *     w[n] = split cosine bell of fraction a:      M = floor(a * N);
+ *            w[n] = w[N-1-n] = 0.5 * (1 - cos(pi * (2n + 1) / (2M)))  for n < M, 1 elsewhere   (a = 0: all 1)
+ *     x[n] = (v[n] - m) * w[n]
+ *     j    = n mod p                               (the angle is ALWAYS formed from n mod p, never from n)
+ *     re_p =  sum_n x[n] * cos(2 pi j / p)
+ *     im_p = -sum_n x[n] * sin(2 pi j / p)
+ *     ssw  =  sum_n w[n]^2
+ * All of it in float64: x, the twiddles and the accumulators.  The twiddles of a period come from a p-entry table.
+ * N == 0 gives zeros (ssw included).  Each (run, period) sum is formed in an order that depends on N and p alone - not on
+ * the other runs or periods of the call, their order, the launch or any atomic - so a result is the same bits in every
+ * call that asks for it (csrc/ftk_spectrum.hip says how).
+ *
+ * ftk_track_spectrum: run i is scores[offsets[i], offsets[i+1]) (scores: host or device; offsets: host, n_iv + 1 entries,
+ * non-negative and non-decreasing); out[(i * n_per + k) * 2 + {0, 1}] = (re, im) of run i at periods[k] (host or device),
+ * ssw_out[i] (host or device, may be NULL) its ssw.
+ * ftk_wps_spectrum: the runs are the WPS of the intervals [iv_start[i], iv_stop[i]) of a resident contig - the scores of
+ * the interval form of the WPS call with the same arguments, written to device scratch and transformed there.  The
+ * intervals are taken in consecutive batches of at most batch_bases bases (0: the library's choice, 2^25; an interval
+ * longer than that is a batch of its own); every batch reuses the scratch, 16 bytes per base.  Interval validity is that of
+ * the interval form; a degenerate interval (stop <= start) is an empty run.
+ * FTK_ERR_INVALID: a NULL argument (ssw_out excepted), device pointers for offsets / periods / the interval arrays,
+ * decreasing offsets, a run longer than 2^22, a score with |v| >= 2^31 (found on the device: the outputs are written, the
+ * call fails), n_per outside 0..1024, a period outside 2..4096, taper outside [0, 0.5], a negative batch_bases.  n_iv == 0
+ * or n_per == 0 is valid and writes nothing. */
+int ftk_track_spectrum(ftk_ctx* ctx, const int64_t* scores, const int64_t* offsets, int64_t n_iv, const int32_t* periods,
+                       int32_t n_per, double taper, int detrend, double* out, double* ssw_out);
+int ftk_wps_spectrum(ftk_ctx* ctx, int contig_id, const int64_t* iv_start, const int64_t* iv_stop, int64_t n_iv,
+                     int64_t chrom_size, int32_t window_size, int32_t min_len, int32_t max_len, int32_t mapq_min,
+                     const int32_t* periods, int32_t n_per, double taper, int detrend, int64_t batch_bases, double* out,
+                     double* ssw_out);
+
 /* ---- multi-GPU (SURVEY 8-e, 8-b's export list) -------------------------------------------------
  * One process and one ftk_ctx per GPU.  Contigs / genome runs are dealt to the ranks by the host and every window,
  * bin and base depends on its own contig's fragments only, so the data path has no collective.  What remains are the

@@ -5,7 +5,9 @@ KBENCH=depth: the depth track (per base and run-length encoded) beside the cleav
 KBENCH=gcbias: the observed and the expected length x GC table (lengths 100-220) against a synthetic 2bit image.
 KBENCH=gcweights: the GC weight column (lengths 100-220) and its sums per window beside ftk_window_counts on the same windows.
 KBENCH=siteprofile: the midpoint profile of 10 000 sites (H = 990, b = 15) beside ftk_weighted_window_sums over the same sites x bins windows.
-KBENCH=vplot: the length x offset map of the same sites (lengths 100-399 in 60 rows of 5) beside 60 calls of ftk_site_profile, one per row."""
+KBENCH=vplot: the length x offset map of the same sites (lengths 100-399 in 60 rows of 5) beside 60 calls of ftk_site_profile, one per row.
+KBENCH=spectrum: the WPS periodogram of 2 000 regions x 10 000 bases at periods 120-280 - the transform alone, the fused call, and
+the route there was before (ftk_wps_intervals to host memory + a numpy matrix product on the host threads)."""
 import os
 import sys
 
@@ -343,6 +345,77 @@ if "vplot" in which:
         print("vplot checksum", "weighted" if weighted else "unweighted", int(d_vsum.sum().item()), int(d_rsum.sum().item()),
               "stacked profiles equal the matrix", bool(torch.equal(d_vsum, d_rsum) and torch.equal(d_vcnt, d_rcnt)),
               "midpoints", int(d_vcnt.sum().item()))
+if "spectrum" in which:
+    # WPS periodogram: KBENCH_SPECTRUM_REGIONS regions (2 000) of 10 000 bases spread over the contig, periods 120-280.
+    # Three times, wall clock around the whole call (the host route has no device events to offer): (a) the transform
+    # alone - scores already on the device, (re, im) left there; (b) the fused call, results in host memory; (c) today's
+    # route - ftk_wps_intervals to host memory, then mean, bell and x @ [cos | sin] in numpy on the host's BLAS threads.
+    # Roofs of the DIRECT form for the same (sample, period) pairs: 2 float64 FMAs per pair at 39.3e12 FMA/s (78.6 TFLOP/s),
+    # one 16-byte twiddle per pair out of LDS at 150 TB/s.  The kernel folds instead (one add and 8 bytes per pair).
+    import time
+    from finaletoolkit_amd import _lib as L
+    rng = np.random.default_rng(193)
+    NR, NB = int(os.environ.get("KBENCH_SPECTRUM_REGIONS", "2000")), 10_000
+    periods = np.arange(120, 281, dtype=np.int32)
+    r_start = np.sort(rng.integers(0, size - NB, NR)).astype(np.int64)
+    r_stop = r_start + NB
+    pairs = NR * NB * len(periods)
+    scores, offs = eng.wps_intervals("c", r_start, r_stop, size)
+    d_scores = torch.from_numpy(np.asarray(scores)).to(dev)
+    d_spec = torch.zeros((NR, len(periods), 2), dtype=torch.float64, device=dev)
+    d_ssw = torch.zeros(NR, dtype=torch.float64, device=dev)
+    torch.cuda.synchronize()
+
+    def transform():
+        eng.track_spectrum(d_scores, offs, periods, out=d_spec, ssw_out=d_ssw)
+
+    def fused():
+        return eng.wps_spectrum("c", r_start, r_stop, size, periods)
+
+    nn = np.arange(NB)
+    bell = np.ones(NB)
+    M = int(np.floor(0.1 * NB))
+    bell[:M] = 0.5 * (1.0 - np.cos(np.pi * (2.0 * nn[:M] + 1.0) / (2.0 * M)))
+    bell[NB - M:] = bell[:M][::-1]
+    ang = 2 * np.pi * (nn[:, None] % periods[None, :]) / periods[None, :]
+    twiddle = np.concatenate([np.cos(ang), -np.sin(ang)], axis=1)  # built once, outside the timed part
+
+    def host_route():
+        sc, _ = eng.wps_intervals("c", r_start, r_stop, size)
+        x = np.asarray(sc).reshape(NR, NB).astype(np.float64)
+        x -= x.mean(axis=1, keepdims=True)
+        x *= bell
+        both = x @ twiddle
+        return both[:, :len(periods)] + 1j * both[:, len(periods):]
+
+    def wall(fn, name):
+        fn()
+        torch.cuda.synchronize()
+        ts = []
+        for _ in range(max(reps // 4, 3)):
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            ts.append(time.perf_counter() - t0)
+        ts = np.array(ts)
+        print(f"{name:34s} median {np.median(ts) * 1e3:9.3f} ms  min {ts.min() * 1e3:9.3f} ms", flush=True)
+        return float(np.median(ts))
+
+    print(f"spectrum: {n} fragments, {NR} regions x {NB} bases x {len(periods)} periods = {pairs:.3g} (sample, period) pairs", flush=True)
+    for _ in range(2):  # twice: the spread between the two passes is the noise
+        t_tr = wall(transform, "spectrum, transform alone")
+        t_fu = wall(fused, "spectrum, fused call")
+        t_ho = wall(host_route, "wps_intervals + numpy on the host")
+        timeit(transform, "transform alone (device events)", 8 * NR * NB * (2 + len(periods) / 4))
+        print(f"  fused call vs the host route: {t_ho / t_fu:.1f} x;  transform: {pairs / t_tr / 1e12:.2f}e12 pairs/s = "
+              f"{2 * pairs / 39.3e12 / t_tr:.1%} of the direct form's FMA roof, {16 * pairs / 150e12 / t_tr:.1%} of its LDS-lookup roof", flush=True)
+    got, _ = fused()
+    want = host_route()
+    torch.cuda.synchronize()
+    scale = float(np.abs(want).max())
+    print("spectrum checksum: fused vs host route, largest difference over the largest value",
+          float(np.abs(got - want).max()) / scale, "fused == transform bits",
+          bool(np.array_equal(got.view(np.float64).reshape(NR, len(periods), 2), d_spec.cpu().numpy())))
 if "gc" in which:
     rng = np.random.default_rng(6)
     packed = rng.integers(0, 256, (size + 3) // 4, dtype=np.uint8)
