@@ -67,6 +67,7 @@ EXPORTS = [
     "ftk_frags_set_weights", "ftk_frags_weights", "ftk_frags_set_gc_weights", "ftk_weighted_window_sums",
     "ftk_site_profile",
     "ftk_site_vplot",
+    "ftk_site_ends",
     "ftk_track_spectrum", "ftk_wps_spectrum",
 ]
 
@@ -343,6 +344,7 @@ def load() -> C.CDLL:
     lib.ftk_weighted_window_sums.argtypes = [vp, C.c_int, vp, vp, i64, C.POINTER(Filter), vp, vp]
     lib.ftk_site_profile.argtypes = [vp, C.c_int, vp, vp, vp, i64, i32, i32, i32, i32, i32, i32, C.c_int, vp, vp]
     lib.ftk_site_vplot.argtypes = [vp, C.c_int, vp, vp, vp, i64, i32, i32, i32, i32, i32, i32, i32, C.c_int, vp, vp]
+    lib.ftk_site_ends.argtypes = [vp, C.c_int, vp, vp, vp, i64, i32, i32, i32, i32, i32, i32, C.c_int, i32, i32, vp, vp, vp, vp]
     lib.ftk_track_spectrum.argtypes = [vp, vp, vp, i64, vp, i32, C.c_double, C.c_int, vp, vp]
     lib.ftk_wps_spectrum.argtypes = [vp, C.c_int, vp, vp, i64, i64, i32, i32, i32, i32, vp, i32, C.c_double, C.c_int, i64, vp, vp]
     lib.ftk_comm_unique_id.argtypes = [C.c_char_p]

@@ -1272,4 +1272,5 @@ static int wps_params(ftk_ctx* ctx, const ContigData& c, int64_t chrom_size, int
 #include "ftk_api_weights.inc"
 #include "ftk_api_siteprofile.inc"
 #include "ftk_api_vplot.inc"
+#include "ftk_api_siteends.inc"
 #include "ftk_api_spectrum.inc"

@@ -2,7 +2,7 @@
 // profile of a resident contig (`ftk_site_profile`) over the kernel of ftk_siteprofile.hip: the call checks its
 // arguments, sorts the sites by (group, centre), cuts them into runs of one group each and launches one workgroup per run.
 // The checks of the site list and of the offset axis, and the plan of runs, are shared with ftk_site_vplot
-// (ftk_api_vplot.inc).
+// (ftk_api_vplot.inc) and ftk_site_ends (ftk_api_siteends.inc).
 #include "ftk_siteprofile.h"
 
 namespace {
@@ -29,12 +29,14 @@ struct SitePlan {
     std::vector<uint64_t> keys;   // group, then centre, then the flip flag (which takes no part in the order that matters)
     std::vector<uint32_t> words;  // the centre with the flip flag on top (kSiteFlipBit), in key order
     std::vector<int32_t> run_off, run_group;
+    std::vector<int32_t> order;   // optional (sort's keep_order): the caller's index of every sorted site; else empty
     uint32_t* d_words = nullptr;
-    int32_t *d_off = nullptr, *d_group = nullptr;
+    int32_t *d_off = nullptr, *d_group = nullptr, *d_order = nullptr;
     size_t n_runs() const { return run_group.size(); }
 
-    // checks every site and sorts them
-    int sort(ftk_ctx* ctx, const int32_t* centre, const uint8_t* flip, const int32_t* group, int64_t n_sites, int32_t n_groups) {
+    // checks every site and sorts them; keep_order: `order` is filled too (equal keys in the caller's order)
+    int sort(ftk_ctx* ctx, const int32_t* centre, const uint8_t* flip, const int32_t* group, int64_t n_sites, int32_t n_groups,
+             bool keep_order = false) {
         keys.resize((size_t)n_sites);
         for (int64_t i = 0; i < n_sites; ++i) {
             const int32_t g = group ? group[i] : 0;
@@ -43,6 +45,14 @@ struct SitePlan {
             if (g < 0 || g >= n_groups)
                 return fail(ctx, FTK_ERR_INVALID, "site %lld: group %d outside [0, %d)", (long long)i, g, n_groups);
             keys[(size_t)i] = (uint64_t)g << 32 | (uint64_t)centre[i] << 1 | (uint64_t)(flip && flip[i]);
+        }
+        if (keep_order) {
+            const std::vector<uint64_t> given = keys;
+            order.resize((size_t)n_sites);
+            for (int64_t i = 0; i < n_sites; ++i) order[(size_t)i] = (int32_t)i;
+            std::stable_sort(order.begin(), order.end(), [&](int32_t a, int32_t b) { return given[(size_t)a] < given[(size_t)b]; });
+            for (int64_t i = 0; i < n_sites; ++i) keys[(size_t)i] = given[(size_t)order[(size_t)i]];
+            return FTK_OK;
         }
         std::sort(keys.begin(), keys.end());
         return FTK_OK;
@@ -69,12 +79,14 @@ struct SitePlan {
         s.tmp(&d_words, words.size());
         s.tmp(&d_off, n_runs() + 1);
         s.tmp(&d_group, n_runs());
+        if (!order.empty()) s.tmp(&d_order, order.size());
     }
     // the uploads read the vectors above (pageable): the caller waits for the stream on every way out
     int upload(ftk_ctx* ctx) {
         HIPCHK(ctx, hipMemcpyAsync(d_words, words.data(), words.size() * 4, hipMemcpyHostToDevice, ctx->stream));
         HIPCHK(ctx, hipMemcpyAsync(d_off, run_off.data(), (n_runs() + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
         HIPCHK(ctx, hipMemcpyAsync(d_group, run_group.data(), n_runs() * 4, hipMemcpyHostToDevice, ctx->stream));
+        if (d_order) HIPCHK(ctx, hipMemcpyAsync(d_order, order.data(), order.size() * 4, hipMemcpyHostToDevice, ctx->stream));
         return FTK_OK;
     }
 };

@@ -136,7 +136,8 @@ struct ftk_ctx {
     size_t scratch_bytes = 0;
     void* d_stats = nullptr;  // load-time validation summary (upload_common)
     int vplot_lds = 0;        // LDS budget of a V-plot workgroup on this device (vplot_lds_budget); 0: not asked yet
-    int spectrum_lds = 0;     // samples a periodogram run may hold in LDS on this device (spectrum_lds_samples); 0: not asked yet
+    int siteends_lds = 0;     // the most LDS a site-ends workgroup may take on this device (siteends_lds_most); 0: not asked yet
+    int spectrum_lds = 0;    // samples a periodogram run may hold in LDS on this device (spectrum_lds_samples); 0: not asked yet
     // asynchronous host results (ftk_wps_async): two device buffers, each copied back on the copy stream behind
     // its kernel; a buffer is reused once its copy has finished
     hipStream_t copy_stream = nullptr;

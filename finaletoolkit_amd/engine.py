@@ -878,6 +878,45 @@ class Engine:
             L.ptr(counts if counts.size else keep)))
         return sums, counts
 
+    # -- fragment-end profiles and OCF window sums around sites (csrc/ftk_siteends.hip) --
+    def site_ends(self, name: str, centres: Sequence, flip=None, groups=None, n_groups: int = 1, half_width: int = 1000,
+                  bin_size: int = 1, quality_threshold=30, min_length=None, max_length=None, weighted: bool = False, peak=None,
+                  flank: int = 10):
+        """``(sums, counts)`` int64 of shape ``(n_groups, 2, n_bins)`` (``ftk_site_ends``), ``n_bins = 2 * half_width //
+        bin_size``: where the fragments of resident contig ``name`` END around the sites ``centres``, aggregated per group.
+        A fragment ``[start, end)`` with ``mapq >= quality_threshold`` and a length in ``[min_length, max_length]`` has its
+        U end on base ``start`` and its D end on base ``end - 1``; an end ``d`` in ``[-half_width, half_width)`` from site
+        ``i`` adds 1 to ``counts[groups[i], t, k]`` and the fragment's weight, in units of 2^-16, to ``sums[groups[i], t,
+        k]``, ``t`` = 0 (U) or 1 (D) and ``k = (d + half_width) // bin_size`` - where ``flip[i]`` is set, ``k`` is counted
+        from the other end and the tracks change places.  With ``peak`` given, ``(sums, counts, site_sums, site_counts)``:
+        the last two int64 of shape ``(n_sites, 4)`` in the order of ``centres`` - ``left_up, left_down, right_up,
+        right_down``, the U and D ends with ``d`` in ``[-peak - flank, -peak + flank]`` and in ``[peak - flank, peak +
+        flank]``, in genome orientation (``flip`` is not applied; ``0 <= flank < peak``, ``peak + flank < half_width``).
+        ``OCF = (left_down - left_up) + (right_up - right_down)``.  ``weighted``, ``flip``, ``groups`` and the sites'
+        order: as in ``site_profile``."""
+        c = np.ascontiguousarray(centres, dtype=np.int32)
+        fl = None if flip is None else np.ascontiguousarray(np.asarray(flip) != 0, dtype=np.uint8)
+        gr = None if groups is None else np.ascontiguousarray(groups, dtype=np.int32)
+        for other, what in ((fl, "flip"), (gr, "groups")):
+            if other is not None and other.shape != c.shape:
+                raise ValueError(f"{what} should have one entry per site")
+        n_bins = 2 * int(half_width) // max(int(bin_size), 1)
+        shape = [max(int(n_groups), 0), 2, min(max(n_bins, 0), 4096)]
+        if shape[0] * shape[1] * shape[2] > 1 << 28:  # (the call fails and writes nothing)
+            shape[0] = 0
+        sums, counts = np.zeros(shape, np.int64), np.zeros(shape, np.int64)
+        per_site = peak is not None
+        site_sums, site_counts = np.zeros((len(c), 4), np.int64), np.zeros((len(c), 4), np.int64)
+        keep = np.empty(1, np.int64)  # (a pointer for outputs without an element: the call fails or writes nothing)
+        self._check(self.lib.ftk_site_ends(
+            self.ctx, self.contig_id(name), L.ptr(c) if len(c) else None, L.ptr(fl) if fl is not None and len(c) else None,
+            L.ptr(gr) if gr is not None and len(c) else None, len(c), int(n_groups), int(half_width), int(bin_size),
+            int(quality_threshold), -1 if min_length is None else int(min_length), -1 if max_length is None else int(max_length),
+            int(bool(weighted)), int(peak) if per_site else 0, int(flank) if per_site else 0, L.ptr(sums if sums.size else keep),
+            L.ptr(counts if counts.size else keep), (L.ptr(site_sums if len(c) else keep)) if per_site else None,
+            (L.ptr(site_counts if len(c) else keep)) if per_site else None))
+        return (sums, counts, site_sums, site_counts) if per_site else (sums, counts)
+
     # -- periodograms of score runs (csrc/ftk_spectrum.hip) --------------------------------
     @staticmethod
     def _spectrum_outputs(n_iv, periods, out, ssw_out):

@@ -17,7 +17,7 @@ from .exceptions import InvalidInputError
 from .source import get_engine, open_source
 
 __all__ = ["chrom_sizes_to_list", "chrom_sizes_to_dict", "get_intervals", "overlaps", "frags_in_region", "frag_generator",
-           "frag_array", "frag_export", "frag_filter", "frag_gc_coverage", "frag_site_profile", "frag_vplot", "VPlot", "frag_wps_spectrum", "WpsSpectrum", "read_sites", "gc_weights", "read_gc_bias_table", "read_region_mask", "agg_bw", "gen_kmers", "reverse_complement", "validate_compatible_contigs", "valid_interval",
+           "frag_array", "frag_export", "frag_filter", "frag_gc_coverage", "frag_site_profile", "frag_vplot", "VPlot", "frag_ocf", "OCF", "frag_wps_spectrum", "WpsSpectrum", "read_sites", "gc_weights", "read_gc_bias_table", "read_region_mask", "agg_bw", "gen_kmers", "reverse_complement", "validate_compatible_contigs", "valid_interval",
            "_none_eq", "_none_geq", "_none_leq"]
 
 FragTuple = Tuple[str, int, int, int, bool]
@@ -800,13 +800,16 @@ def frag_site_profile(input_file, site_file, output_file=None, reference_file=No
 
 
 def _sites_over_contigs(what, one_contig, cell_shape, input_file, site_file, reference_file, bias, min_length, max_length,
-                        quality_threshold, by_name, min_bias, stride, workers, verbose, max_cells=None):
-    """The driver ``frag_site_profile`` and ``frag_vplot`` share: the sites read and grouped, the bias table made ready,
-    one ``ContigFeed`` pass with ``set_gc_weights`` per contig when there is a reference, ``one_contig(eng, key, centre,
-    flip, group, n_groups, weighted) -> (sums, counts)`` of shape ``(n_groups,) + cell_shape`` per contig summed on the
-    host, and the two warnings (named after ``what``).  ``max_cells``: the cells all groups together may have, checked
-    once the site file has given the groups.  Returns ``(groups, n_sites, count, units, skipped_contigs,
-    sites read)``."""
+                        quality_threshold, by_name, min_bias, stride, workers, verbose, max_cells=None, per_site=None):
+    """The driver ``frag_site_profile``, ``frag_vplot`` and ``frag_ocf`` share: the sites read and grouped, the bias table
+    made ready, one ``ContigFeed`` pass with ``set_gc_weights`` per contig when there is a reference, ``one_contig(eng,
+    key, centre, flip, group, n_groups, weighted) -> (sums, counts)`` of shape ``(n_groups,) + cell_shape`` per contig
+    summed on the host, and the two warnings (named after ``what``).  ``max_cells``: the cells all groups together may
+    have, checked once the site file has given the groups.  ``per_site``: a callable; ``one_contig`` may then return
+    further per-site arrays behind ``(sums, counts)``, in the order of the sites it was given, and ``per_site(idx, *those)``
+    is called once per visited contig with the indices of the contig's sites among the sites read - the sites of skipped
+    contigs never get a call.  Returns ``(groups, n_sites, count, units, skipped_contigs, sites
+    read)``."""
     import sys
     import warnings
 
@@ -862,12 +865,14 @@ def _sites_over_contigs(what, one_contig, cell_shape, input_file, site_file, ref
                     if ref is not None:
                         rid = ref.device_image(eng, c, with_layout=True)
                         eng.set_gc_weights(key, rid, int(min_length), int(max_length), table, quality_threshold)
-                    sums, counts = one_contig(eng, key, centre[idx], flip[idx], group[idx], len(groups), ref is not None)
+                    sums, counts, *rest = one_contig(eng, key, centre[idx], flip[idx], group[idx], len(groups), ref is not None)
+                    if per_site is not None:
+                        per_site(idx, *rest)
                     units += sums
                     count += counts
                     n_sites += np.bincount(group[idx], minlength=len(groups))
                     if verbose:
-                        sys.stderr.write(f"{what}: {c}: {len(idx)} sites, {int(counts.sum())} midpoints\n")
+                        sys.stderr.write(f"{what}: {c}: {len(idx)} sites, {int(counts.sum())} {'midpoints' if per_site is None else 'ends'}\n")
                 feed.finish()
         except BaseException:
             feed.close()
@@ -952,6 +957,124 @@ def frag_vplot(input_file, site_file, output_file=None, reference_file=None, bia
         writers.write_vplot_rows(os.fspath(output_file), res)
     if verbose:
         sys.stderr.write(f"frag_vplot: {n_read} sites in {time.time() - t0:.3f} s\n")
+    return res
+
+
+class OCF(NamedTuple):
+    """Result of ``frag_ocf``: per group of sites the U / D end profiles and the OCF score, and every site's score."""
+    groups: tuple               # names in order of first appearance (``by_name``), else ``("all",)``
+    n_sites: np.ndarray         # int64 per group: the sites used (those on contigs that were not skipped)
+    offsets: np.ndarray         # int64 per bin: its first offset from the site's centre, ``-half_width + k * bin_size``
+    up_count: np.ndarray        # int64 (n_groups, n_bins): U ends (fragment starts), 5' to 3' of the sites
+    down_count: np.ndarray      # int64 (n_groups, n_bins): D ends (last bases of the fragments)
+    up_corrected: np.ndarray    # float64 (n_groups, n_bins): the sum of their weights (``up_count`` without a reference)
+    down_corrected: np.ndarray  # float64 (n_groups, n_bins)
+    windows_count: np.ndarray   # int64 (n_groups, 4): left_up, left_down, right_up, right_down summed over the group's sites
+    ocf_count: np.ndarray       # int64 per group: (left_down - left_up) + (right_up - right_down) of ``windows_count``
+    ocf: np.ndarray             # float64 per group: the same from the weighted sums (``ocf_count`` without a reference)
+    site_ocf: np.ndarray        # float64 per site, in the site file's order; NaN for the sites of skipped contigs
+    skipped_contigs: tuple      # contigs with sites that the input, or the reference, does not hold
+
+
+OCF_MAX_CELLS = 1 << 28  # groups x 2 tracks x bins of one call
+
+
+def _check_ocf_args(output_file, profile_file, site_output_file, reference_file, bias, half_width, bin_size, peak, flank, min_length,
+                    max_length, min_bias, stride):
+    _check_site_profile_args(output_file, reference_file, bias, half_width, bin_size, min_length, max_length, min_bias, stride)
+    for path, what in ((profile_file, "profile_file"), (site_output_file, "site_output_file")):
+        if path is not None and not str(path).endswith((".tsv", ".tsv.gz")):
+            raise ValueError(f"{what} should have .tsv or .tsv.gz as suffix")
+    if peak is None or flank is None:
+        raise ValueError("invalid windows: peak and flank cannot be None")
+    H, p, w = int(half_width), int(peak), int(flank)
+    if p < 1:
+        raise ValueError(f"invalid peak ({p}): at least 1")
+    if not 0 <= w < p:
+        raise ValueError(f"invalid flank ({w}): 0 <= flank < peak = {p} is required")
+    if p + w >= H:
+        raise ValueError(f"invalid windows: peak + flank = {p + w} should be below half_width = {H}")
+
+
+def frag_ocf(input_file, site_file, output_file=None, profile_file=None, site_output_file=None, reference_file=None, bias=None,
+             half_width: int = 1000, bin_size: int = 1, peak: int = 60, flank: int = 10, min_length: int = 50, max_length: int = 350,
+             quality_threshold: int = 30, by_name: bool = False, normalize: bool = False, min_bias: float = 0.05, stride: int = 1,
+             workers=None, verbose=False) -> OCF:
+    """Orientation-aware cfDNA fragmentation (OCF, Sun et al., Genome Research 2019) around the sites of ``site_file``
+    (``.bed`` / ``.bed.gz``, ``read_sites``): where fragments END relative to tissue-specific open-chromatin centres.
+    Upstream (U) and downstream (D) fragment ends pile up on opposite sides of an open site; their signed difference in
+    two small windows at ``-peak`` and ``+peak`` is the tissue-of-origin score.
+
+    A fragment ``[start, end)`` with ``mapq >= quality_threshold`` and a length in ``[min_length, max_length]`` has its U
+    end on base ``start`` and its D end on base ``end - 1``.  Profile: an end ``d`` in ``[-half_width, half_width)`` from a
+    site's centre counts in bin ``(d + half_width) // bin_size`` of ``up_count`` or ``down_count`` of the site's group.
+    The profile is STRAND-AWARE, as in ``frag_site_profile``: for a site on the ``-`` strand the bins are counted from the
+    other end and U and D change places, so that offsets run 5' to 3' of the site and "up" is upstream of it.  Score: per
+    site, ``left_up`` / ``left_down`` are the U / D ends with ``d`` in ``[-peak - flank, -peak + flank]`` and ``right_up``
+    / ``right_down`` those in ``[peak - flank, peak + flank]``, and ``OCF = (left_down - left_up) + (right_up -
+    right_down)``.  Mirroring a site swaps left with right and U with D, which leaves the score as it is - it is
+    strand-free, and so is a group's ``ocf``, the sum of its sites' scores.  ``0 <= flank < peak``, ``peak + flank <
+    half_width``.  Everything is accumulated as integers on the GPU, contig by contig as the input is decoded
+    (``Engine.site_ends``), and summed on the host, so it is exact.
+
+    Sites, groups (``by_name``), skipped contigs (two ``UserWarning`` kinds), and the GC correction (``reference_file``,
+    ``bias`` as a ``GCBias``, the path of its TSV or ``None``, ``min_bias``, ``stride``) are exactly as in
+    ``frag_site_profile``; without a reference the corrected arrays equal the counts.  ``normalize``: both corrected
+    tracks and ``ocf`` of a group are divided by the mean of the group's corrected profile over both tracks (a mean of 0
+    leaves zeros).  ``site_ocf`` holds every site's score from the weighted sums, NaN for the sites of skipped contigs.
+
+    Files (``.tsv`` / ``.tsv.gz``): ``output_file`` one row per group (``writers.write_ocf_rows``), ``profile_file`` the
+    end profiles (``writers.write_end_profile_rows``), ``site_output_file`` one row per site
+    (``writers.write_site_ocf_rows``)."""
+    import os
+    import sys
+    import time
+
+    from . import _lib as L
+    from . import writers
+    _check_ocf_args(output_file, profile_file, site_output_file, reference_file, bias, half_width, bin_size, peak, flank, min_length,
+                    max_length, min_bias, stride)
+    H, b, p, w = int(half_width), int(bin_size), int(peak), int(flank)
+    n_bins = 2 * H // b
+    t0 = time.time()
+    sites = read_sites(site_file)  # (read again by the driver: the per-site arrays and the site file's rows need them here)
+    site_units, site_count = np.zeros((len(sites), 4), np.int64), np.zeros((len(sites), 4), np.int64)
+    seen = np.zeros(len(sites), bool)
+
+    def one_contig(eng, key, centre, flip, group, n_groups, weighted):
+        return eng.site_ends(key, centre, flip, group, n_groups, H, b, quality_threshold, min_length, max_length, weighted=weighted,
+                             peak=p, flank=w)
+
+    def per_site(idx, site_sums, site_counts):
+        site_units[idx], site_count[idx], seen[idx] = site_sums, site_counts, True
+    groups, n_sites, count, units, skipped, n_read = _sites_over_contigs(
+        "frag_ocf", one_contig, (2, n_bins), input_file, site_file, reference_file, bias, min_length, max_length, quality_threshold,
+        by_name, min_bias, stride, workers, verbose, OCF_MAX_CELLS, per_site)
+    sign = np.array([-1, 1, 1, -1], np.int64)  # left_up, left_down, right_up, right_down
+    site_score = (site_units * sign).sum(axis=1)
+    site_ocf = site_score / float(L.WEIGHT_ONE)
+    site_ocf[~seen] = np.nan
+    names = {name: g for g, name in enumerate(groups)}
+    group_of = np.array([names[s[2]] if by_name else 0 for s in sites], dtype=np.int64)
+    windows_count, ocf_units = np.zeros((len(groups), 4), np.int64), np.zeros(len(groups), np.int64)
+    np.add.at(windows_count, group_of[seen], site_count[seen])
+    np.add.at(ocf_units, group_of[seen], site_score[seen])
+    corrected = units / float(L.WEIGHT_ONE)
+    ocf = ocf_units / float(L.WEIGHT_ONE)
+    if normalize:
+        mean = corrected.mean(axis=(1, 2), keepdims=True)
+        corrected = np.divide(corrected, mean, out=np.zeros_like(corrected), where=mean != 0)
+        ocf = np.divide(ocf, mean[:, 0, 0], out=np.zeros_like(ocf), where=mean[:, 0, 0] != 0)
+    res = OCF(groups, n_sites, -H + b * np.arange(n_bins, dtype=np.int64), count[:, 0], count[:, 1], corrected[:, 0], corrected[:, 1],
+              windows_count, (windows_count * sign).sum(axis=1), ocf, site_ocf, skipped)
+    if output_file is not None:
+        writers.write_ocf_rows(os.fspath(output_file), res)
+    if profile_file is not None:
+        writers.write_end_profile_rows(os.fspath(profile_file), res)
+    if site_output_file is not None:
+        writers.write_site_ocf_rows(os.fspath(site_output_file), sites, site_count, site_ocf)
+    if verbose:
+        sys.stderr.write(f"frag_ocf: {n_read} sites in {time.time() - t0:.3f} s\n")
     return res
 
 

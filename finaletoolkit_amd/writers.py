@@ -326,6 +326,48 @@ def write_vplot_rows(output_file: str, vplot) -> None:
     _emit(output_file, "".join(rows), (".tsv",), (".tsv.gz",), message)
 
 
+def write_ocf_rows(output_file: str, ocf) -> None:
+    """``group n_sites left_up left_down right_up right_down ocf_count ocf`` per group of a ``utils.OCF`` behind the header
+    line ``#group n_sites left_up left_down right_up right_down ocf_count ocf``: the four window counts summed over the
+    group's sites, the score from the counts and the (corrected) score with six decimals; ``.tsv`` as text, ``.tsv.gz`` as
+    gzip."""
+    message = "output_file should have .tsv or .tsv.gz as suffix"
+    if not output_file.endswith((".tsv", ".tsv.gz")):
+        raise ValueError(message)
+    rows = ["#group\tn_sites\tleft_up\tleft_down\tright_up\tright_down\tocf_count\tocf\n"]
+    rows += [f"{name}\t{int(ocf.n_sites[g])}\t" + "\t".join(str(int(x)) for x in ocf.windows_count[g])
+             + f"\t{int(ocf.ocf_count[g])}\t{format(float(ocf.ocf[g]), '.6f')}\n" for g, name in enumerate(ocf.groups)]
+    _emit(output_file, "".join(rows), (".tsv",), (".tsv.gz",), message)
+
+
+def write_end_profile_rows(output_file: str, ocf) -> None:
+    """``group n_sites offset up_count down_count up_corrected down_corrected`` per (group, bin) of a ``utils.OCF`` behind
+    the header line of those names with a ``#`` in front, in group order then bin order, the corrected columns with six
+    decimals; ``.tsv`` as text, ``.tsv.gz`` as gzip."""
+    message = "profile_file should have .tsv or .tsv.gz as suffix"
+    if not output_file.endswith((".tsv", ".tsv.gz")):
+        raise ValueError(message)
+    rows = ["#group\tn_sites\toffset\tup_count\tdown_count\tup_corrected\tdown_corrected\n"]
+    for g, name in enumerate(ocf.groups):
+        rows += [f"{name}\t{int(ocf.n_sites[g])}\t{int(o)}\t{int(u)}\t{int(d)}\t{format(float(x), '.6f')}\t{format(float(y), '.6f')}\n"
+                 for o, u, d, x, y in zip(ocf.offsets, ocf.up_count[g], ocf.down_count[g], ocf.up_corrected[g], ocf.down_corrected[g])]
+    _emit(output_file, "".join(rows), (".tsv",), (".tsv.gz",), message)
+
+
+def write_site_ocf_rows(output_file: str, sites, site_windows_count, site_ocf) -> None:
+    """``contig centre name strand left_up left_down right_up right_down ocf`` per site of ``sites`` (``utils.read_sites``)
+    behind the header line of those names with a ``#`` in front, in the site file's order: the four window COUNTS of the
+    site (``site_windows_count``, int64 ``(n_sites, 4)``) and its score ``site_ocf`` with six decimals.  Sites whose score
+    is NaN - those on skipped contigs - are left out.  ``.tsv`` as text, ``.tsv.gz`` as gzip."""
+    message = "site_output_file should have .tsv or .tsv.gz as suffix"
+    if not output_file.endswith((".tsv", ".tsv.gz")):
+        raise ValueError(message)
+    rows = ["#contig\tcentre\tname\tstrand\tleft_up\tleft_down\tright_up\tright_down\tocf\n"]
+    rows += [f"{c}\t{int(centre)}\t{name}\t{strand}\t" + "\t".join(str(int(x)) for x in w) + f"\t{format(float(s), '.6f')}\n"
+             for (c, centre, name, strand), w, s in zip(sites, site_windows_count, site_ocf) if s == s]
+    _emit(output_file, "".join(rows), (".tsv",), (".tsv.gz",), message)
+
+
 def write_wps_spectrum_rows(output_file: str, spectrum) -> None:
     """One row per interval of a ``utils.WpsSpectrum``, in its order, behind the header line ``contig start stop name
     n_bases band_mean p<min> ... p<max>``: the interval, its bases, the band's mean power and the power at every period,

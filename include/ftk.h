@@ -619,6 +619,43 @@ int ftk_site_vplot(ftk_ctx* ctx, int contig_id, const int32_t* centre, const uin
                    int32_t bin_size, int32_t len_lo, int32_t len_hi, int32_t len_bin, int32_t mapq_min, int use_weights,
                    int64_t* sum_out, int64_t* count_out /* may be NULL */);
 
+/* ---- fragment-end profiles and OCF window sums around sites (csrc/ftk_siteends.hip) -----------------
+ * Where fragments END relative to a site: what orientation-aware cfDNA fragmentation (OCF, Sun et al., Genome Research
+ * 2019) is computed from.  Sites, groups and the offset axis are as in ftk_site_profile: centre centre[i] in [0, 2^30),
+ * flip flag flip[i], group group[i] in [0, n_groups); half_width = H in [1, 2^20]; bin_size = b divides 2 H; n_bins =
+ * 2 H / b <= 4096; n_groups * 2 * n_bins <= 2^28; 0 <= n_sites < 2^31.
+ *   A fragment [start, end) passes with mapq >= mapq_min and min_len <= end - start <= max_len (closed; FTK_LEN_OPEN =
+ *   no bound).  A passing fragment has two ends: its U end on base `start` and its D end on base `end - 1`; a fragment
+ *   of length 1 has both on one base and counts in both tracks.  (A fragment that holds no base, end <= start, has no
+ *   ends.)
+ *   Group profile.  For site i, each end at position x with d = x - centre[i] in [-H, H) falls in bin k = (d + H) / b:
+ *   count[group[i]][track][k] += 1 and sum[group[i]][track][k] += w, w being the fragment's weight with use_weights,
+ *   else FTK_WEIGHT_ONE; track is 0 for a U end and 1 for a D end.  A flipped site uses bin n_bins - 1 - k AND THE OTHER
+ *   TRACK: what is upstream on the genome is downstream of a site on the - strand.  The two ends of a fragment are
+ *   independent events: either, both or neither may fall in the window.
+ *   Per-site window sums (site_sum_out != NULL).  With peak = p and flank = w, 0 <= w < p and p + w < H, every site i
+ *   gets four sums in GENOME orientation - the flip flag is not applied:
+ *     left_up, left_down    the U ends and the D ends with d in [-p - w, -p + w]
+ *     right_up, right_down  the U ends and the D ends with d in [ p - w,  p + w]      (both ranges closed)
+ *   site_sum_out[i][0..3] = their weights summed in that order, site_count_out[i][0..3] (may be NULL) = how many they
+ *   are, rows in the CALLER'S order of the sites.  The score is OCF_i = (left_down - left_up) + (right_up - right_down).
+ *   Mirroring a site - d -> -d with U and D swapped, which is what the - strand does to it - maps left_down <-> right_up
+ *   and left_up <-> right_down, and so OCF_i onto itself: the score does not depend on the strand, which is why no
+ *   flip is applied.  With site_sum_out == NULL, peak, flank and site_count_out are ignored.
+ * Sites are independent: a fragment near two sites counts for both, a site listed twice counts twice (and has two rows);
+ * sites come in any order.  The read1 columns of a BAM contig play no part.  The sites are HOST arrays; sum_out and
+ * count_out (may be NULL) are host or device arrays of n_groups * 2 * n_bins int64, row-major [group][track][bin];
+ * site_sum_out and site_count_out host or device arrays of n_sites * 4 int64; all overwritten (all 0 for n_sites == 0 or
+ * an empty contig).  The sums are integers, so every result is exact and independent of the order of arrival.
+ * FTK_ERR_INVALID for arguments outside the ranges above, a NULL centre (n_sites > 0) or sum_out, n_sites < 0, sites that
+ * are device arrays, and for use_weights on a contig without a weights column (the message names ftk_frags_set_weights
+ * and ftk_frags_set_gc_weights); FTK_ERR_NO_CONTIG for an unknown contig.  A failing call writes to none of its outputs. */
+int ftk_site_ends(ftk_ctx* ctx, int contig_id, const int32_t* centre, const uint8_t* flip /* NULL: none */,
+                  const int32_t* group /* NULL: all 0 */, int64_t n_sites, int32_t n_groups, int32_t half_width,
+                  int32_t bin_size, int32_t mapq_min, int32_t min_len, int32_t max_len, int use_weights, int32_t peak,
+                  int32_t flank, int64_t* sum_out, int64_t* count_out /* may be NULL */, int64_t* site_sum_out /* may be NULL */,
+                  int64_t* site_count_out /* may be NULL */);
+
 /* ---- BGZF inflate on the device -------------------------------------------------------------------
  * The streaming decoder's host threads spend most of a fragment file's decode in DEFLATE; BGZF blocks are
  * independent streams of at most 64 KB of data, decoded here one wavefront per block (csrc/ftk_inflate.hip).

@@ -6,6 +6,8 @@ KBENCH=gcbias: the observed and the expected length x GC table (lengths 100-220)
 KBENCH=gcweights: the GC weight column (lengths 100-220) and its sums per window beside ftk_window_counts on the same windows.
 KBENCH=siteprofile: the midpoint profile of 10 000 sites (H = 990, b = 15) beside ftk_weighted_window_sums over the same sites x bins windows.
 KBENCH=vplot: the length x offset map of the same sites (lengths 100-399 in 60 rows of 5) beside 60 calls of ftk_site_profile, one per row.
+KBENCH=siteends: the U / D end profiles and per-site OCF window sums of the same sites beside ftk_site_profile, both LDS arrangements
+of the widest weighted profile, and the route there was before (the columns to host memory + the rule in numpy).
 KBENCH=spectrum: the WPS periodogram of 2 000 regions x 10 000 bases at periods 120-280 - the transform alone, the fused call, and
 the route there was before (ftk_wps_intervals to host memory + a numpy matrix product on the host threads)."""
 import os
@@ -345,6 +347,96 @@ if "vplot" in which:
         print("vplot checksum", "weighted" if weighted else "unweighted", int(d_vsum.sum().item()), int(d_rsum.sum().item()),
               "stacked profiles equal the matrix", bool(torch.equal(d_vsum, d_rsum) and torch.equal(d_vcnt, d_rcnt)),
               "midpoints", int(d_vcnt.sum().item()))
+if "siteends" in which:
+    # Site ends: the siteprofile mode's contig and sites (10 000 random sites, H = 990, b = 15, one group), the whole
+    # call with outputs on the device: unweighted and weighted, with and without the per-site window sums (peak 60, flank
+    # 10), beside ftk_site_profile over the same sites - the same candidates, half the LDS atomics.  Then the widest
+    # weighted profile (H = 2048, b = 1: 4096 bins x 2 tracks x 12 B = 96 KiB of LDS) in both arrangements: one
+    # workgroup per run (FTK_SITE_ENDS_SPLIT=0), and one per (run, track) (=1), which reads the candidates twice.  Last, by
+    # the wall clock, the only route there was before: the three columns to host memory and the rule in numpy, site by
+    # site (KBENCH_SITEENDS_HOST=0 leaves it out).  Byte floors as in the siteprofile mode: 9 B (13 B weighted) per
+    # candidate.
+    import time
+    from finaletoolkit_amd import _lib as L
+    rng = np.random.default_rng(11)
+    H, B, NS, PEAK, FLANK = 990, 15, 10_000, 60, 10
+    nb = 2 * H // B
+    centres = rng.integers(H, size - H, NS).astype(np.int32)
+    flips = rng.integers(0, 2, NS).astype(np.uint8)
+    eng.set_weights("c", rng.integers(1, 1 << 20, n, dtype=np.int64).astype(np.uint32))
+    lmax = eng.info("c")[1]
+    hs = s.cpu().numpy().astype(np.int64)
+    c64 = centres.astype(np.int64)
+
+    def candidates(h):
+        return int((np.searchsorted(hs, ((c64 + h >> 9) + 1) << 9, side="left")
+                    - np.searchsorted(hs, (np.maximum(c64 - h - lmax, 0) >> 9) << 9, side="left")).sum())
+    cand = candidates(H)
+    d_esum = torch.zeros(2 * 4096, dtype=torch.int64, device=dev)
+    d_ecnt = torch.zeros(2 * 4096, dtype=torch.int64, device=dev)
+    d_ssum = torch.zeros(NS * 4, dtype=torch.int64, device=dev)
+    d_scnt = torch.zeros(NS * 4, dtype=torch.int64, device=dev)
+    d_psum = torch.zeros(nb, dtype=torch.int64, device=dev)
+    d_pcnt = torch.zeros(nb, dtype=torch.int64, device=dev)
+    cid = eng.contig_id("c")
+
+    def ends(weighted, per_site, h=H, b=B):
+        eng._check(eng.lib.ftk_site_ends(eng.ctx, cid, L.ptr(centres), L.ptr(flips), None, NS, 1, h, b, 30, -1, -1, int(weighted), PEAK,
+                                         FLANK, L.ptr(d_esum), L.ptr(d_ecnt), L.ptr(d_ssum) if per_site else None,
+                                         L.ptr(d_scnt) if per_site else None))
+
+    def profile(weighted):
+        eng._check(eng.lib.ftk_site_profile(eng.ctx, cid, L.ptr(centres), L.ptr(flips), None, NS, 1, H, B, 30, -1, -1, int(weighted),
+                                            L.ptr(d_psum), L.ptr(d_pcnt)))
+    print(f"siteends: {n} fragments, {NS} sites x 2 tracks x {nb} bins, {cand} candidates ({cand / NS:.0f} per site)", flush=True)
+    for _ in range(2):  # twice: the spread between the two passes is the noise
+        for weighted, nbytes in ((False, 9), (True, 13)):
+            tag = "weighted" if weighted else "unweighted"
+            timeit(lambda: ends(weighted, False), f"site ends, {tag}", nbytes * cand)
+            timeit(lambda: ends(weighted, True), f"site ends + sites, {tag}", nbytes * cand)
+            timeit(lambda: profile(weighted), f"site profile, {tag}", nbytes * cand)
+        for weighted, nbytes in ((False, 9), (True, 13)):
+            tag = "weigh." if weighted else "unw."
+            timeit(lambda: ends(weighted, False), f"site ends, {tag} COLD", nbytes * cand, cold="read")
+            timeit(lambda: ends(weighted, True), f"site ends + sites, {tag} COLD", nbytes * cand, cold="read")
+            timeit(lambda: profile(weighted), f"site profile, {tag} COLD", nbytes * cand, cold="read")
+    wide = candidates(2048)
+    print(f"siteends: 4096 bins, weighted, {wide} candidates per pass", flush=True)
+    for _ in range(2):
+        for split in ("0", "1"):
+            os.environ["FTK_SITE_ENDS_SPLIT"] = split
+            tag = "2 x 48 KiB" if split == "1" else "1 x 96 KiB"
+            timeit(lambda: ends(True, True, 2048, 1), f"4096 bins {tag}", 13 * wide)
+            timeit(lambda: ends(True, True, 2048, 1), f"4096 bins {tag} COLD", 13 * wide, cold="read")
+    del os.environ["FTK_SITE_ENDS_SPLIT"]
+    for weighted in (False, True):
+        ends(weighted, True)
+        torch.cuda.synchronize()
+        ocf = (d_ssum.view(NS, 4) * torch.tensor([-1, 1, 1, -1], device=dev)).sum()
+        print("siteends checksum", "weighted" if weighted else "unweighted", int(d_esum[:2 * nb].sum().item()), "ends",
+              int(d_ecnt[:2 * nb].sum().item()),
+              "window ends", int(d_scnt.sum().item()), "ocf units", int(ocf.item()))
+    if os.environ.get("KBENCH_SITEENDS_HOST", "1") != "0":
+        ts = []
+        for _ in range(3):
+            t0 = time.perf_counter()
+            fs, fe, fq = (x.cpu().numpy() for x in (s, e, q))  # the columns to host memory
+            fs, fe = fs[:n].astype(np.int64), fe[:n].astype(np.int64)
+            keep = (fq[:n] >= 30) & (fe > fs)
+            counts, windows = np.zeros(2 * nb, np.int64), np.zeros((NS, 4), np.int64)
+            for kind, x in enumerate((np.sort(fs[keep]), np.sort(fe[keep] - 1))):
+                lo_i, hi_i = np.searchsorted(x, c64 - H), np.searchsorted(x, c64 + H)
+                for c, f, lo, hi in zip(c64.tolist(), flips.tolist(), lo_i.tolist(), hi_i.tolist()):
+                    k = (x[lo:hi] - c + H) // B
+                    counts += np.bincount((1 - kind) * nb + nb - 1 - k if f else kind * nb + k, minlength=2 * nb)
+                for side, mid in enumerate((c64 - PEAK, c64 + PEAK)):
+                    windows[:, 2 * side + kind] = np.searchsorted(x, mid + FLANK, "right") - np.searchsorted(x, mid - FLANK, "left")
+            ts.append(time.perf_counter() - t0)
+        ends(False, True)
+        torch.cuda.synchronize()
+        print(f"host route (columns to host + numpy), unweighted: median {np.median(ts) * 1e3:.1f} ms  min {min(ts) * 1e3:.1f} ms; "
+              f"equal to the call: {bool(np.array_equal(counts, d_ecnt[:2 * nb].cpu().numpy()))} "
+              f"{bool(np.array_equal(windows, d_scnt.view(NS, 4).cpu().numpy()))}", flush=True)
 if "spectrum" in which:
     # WPS periodogram: KBENCH_SPECTRUM_REGIONS regions (2 000) of 10 000 bases spread over the contig, periods 120-280.
     # Three times, wall clock around the whole call (the host route has no device events to offer): (a) the transform
