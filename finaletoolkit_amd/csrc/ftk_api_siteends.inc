@@ -46,44 +46,20 @@ int ftk_site_ends(ftk_ctx* ctx, int contig_id, const int32_t* centre, const uint
     }
     if (whole > ctx->siteends_lds) p.split = 1;
     plan.cut(n_sites > 0 && c->n > 0 ? siteends_run_sites(ctx->n_cu, n_sites, c->n, c->max_end, p) : 0);
-    const size_t n_runs = plan.n_runs(), cells = (size_t)n_groups * 2 * (size_t)n_bins, site_cells = (size_t)n_sites * 4;
+    const size_t cells = (size_t)n_groups * 2 * (size_t)n_bins, site_cells = (size_t)n_sites * 4;
     int64_t *d_sum = nullptr, *d_cnt = nullptr, *d_ssum = nullptr, *d_scnt = nullptr;
-    Scratch s(ctx);
-    s.out(&d_sum, sum_out, cells);
-    if (count_out) s.out(&d_cnt, count_out, cells);
-    if (per_site && site_cells) {
-        s.out(&d_ssum, site_sum_out, site_cells);
-        if (site_count_out) s.out(&d_scnt, site_count_out, site_cells);
-    }
-    plan.declare(s);
-    if ((rc = s.reserve())) return rc;
-    HIPCHK(ctx, hipMemsetAsync(d_sum, 0, cells * 8, ctx->stream));
-    if (d_cnt) HIPCHK(ctx, hipMemsetAsync(d_cnt, 0, cells * 8, ctx->stream));
-    // (the kernel writes every site's row; the zeros are what a call without runs - an empty contig - returns)
-    if (d_ssum) HIPCHK(ctx, hipMemsetAsync(d_ssum, 0, site_cells * 8, ctx->stream));
-    if (d_scnt) HIPCHK(ctx, hipMemsetAsync(d_scnt, 0, site_cells * 8, ctx->stream));
-    // From here on the stream may be reading the plan's vectors (pageable staging of this call): every way out, an
-    // error's included, waits for the stream first.
-    auto enqueue = [&]() -> int {
-        if (!n_runs) return FTK_OK;
-        if (int e = plan.upload(ctx)) return e;
-        // at most kSiteMaxRunsPerLaunch workgroups per launch, a split run being two
-        const size_t per_launch = (size_t)kSiteMaxRunsPerLaunch / (p.split ? 2 : 1);
-        for (size_t r0 = 0; r0 < n_runs; r0 += per_launch) {
-            const int part = (int)std::min(n_runs - r0, per_launch);
-            launch_site_ends(ctx->stream, c->v, c->weights, plan.d_words, plan.d_order, plan.d_off + r0, plan.d_group + r0, part, p,
-                             (unsigned long long*)d_sum, (unsigned long long*)d_cnt, (unsigned long long*)d_ssum,
-                             (unsigned long long*)d_scnt);
-            HIPCHK(ctx, hipGetLastError());
-        }
-        return FTK_OK;
-    };
-    if ((rc = enqueue())) {
-        (void)hipStreamSynchronize(ctx->stream);
-        return rc;
-    }
-    if ((rc = s.finish(true))) (void)hipStreamSynchronize(ctx->stream);
-    return rc;
+    // (the kernel writes every site's row; the zeros of the per-site outputs are what a call without runs - an empty
+    // contig - returns.  A split run is two workgroups.)
+    return run_site_call(ctx, plan,
+                         {{&d_sum, sum_out, cells},
+                          {&d_cnt, count_out, cells},
+                          {&d_ssum, site_sum_out, site_cells},
+                          {&d_scnt, per_site ? site_count_out : nullptr, site_cells}},
+                         p.split ? 2 : 1, [&](size_t r0, int part) {
+                             launch_site_ends(ctx->stream, c->v, c->weights, plan.d_words, plan.d_order, plan.d_off + r0,
+                                              plan.d_group + r0, part, p, (unsigned long long*)d_sum, (unsigned long long*)d_cnt,
+                                              (unsigned long long*)d_ssum, (unsigned long long*)d_scnt);
+                         });
 }
 
 }  // extern "C"

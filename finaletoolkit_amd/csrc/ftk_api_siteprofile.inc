@@ -1,7 +1,7 @@
 // Part of ftk_api.hip's translation unit (#included there behind the weights part) - the site-aggregated midpoint
 // profile of a resident contig (`ftk_site_profile`) over the kernel of ftk_siteprofile.hip: the call checks its
 // arguments, sorts the sites by (group, centre), cuts them into runs of one group each and launches one workgroup per run.
-// The checks of the site list and of the offset axis, and the plan of runs, are shared with ftk_site_vplot
+// The checks of the site list and of the offset axis, the plan of runs and the call's tail are shared with ftk_site_vplot
 // (ftk_api_vplot.inc) and ftk_site_ends (ftk_api_siteends.inc).
 #include "ftk_siteprofile.h"
 
@@ -91,6 +91,48 @@ struct SitePlan {
     }
 };
 
+// One output of a site call: `cells` 64-bit cells at `user` (host or device; NULL or no cells: not asked for), reached
+// on the device through *dev.
+struct SiteOut {
+    int64_t** dev;
+    int64_t* user;
+    size_t cells;
+};
+
+// The tail every site call ends with: the outputs and the plan get their place in the scratch, the outputs are zeroed,
+// the plan goes up, and launch(r0, part) is called for runs [r0, r0 + part) - at most kSiteMaxRunsPerLaunch workgroups
+// per launch, a run being groups_per_run of them, so that a grid of any workgroup size stays below 2^32 threads.
+template <class Launch>
+int run_site_call(ftk_ctx* ctx, SitePlan& plan, std::initializer_list<SiteOut> outs, size_t groups_per_run, Launch&& launch) {
+    Scratch s(ctx);
+    for (const SiteOut& o : outs)
+        if (o.user && o.cells) s.out(o.dev, o.user, o.cells);
+    plan.declare(s);
+    int rc;
+    if ((rc = s.reserve())) return rc;
+    for (const SiteOut& o : outs)
+        if (*o.dev) HIPCHK(ctx, hipMemsetAsync(*o.dev, 0, o.cells * 8, ctx->stream));
+    // From here on the stream may be reading the plan's vectors (pageable staging of this call): every way out, an
+    // error's included, waits for the stream first.
+    auto enqueue = [&]() -> int {
+        const size_t n_runs = plan.n_runs();
+        if (!n_runs) return FTK_OK;
+        if (int e = plan.upload(ctx)) return e;
+        const size_t per_launch = std::max<size_t>((size_t)kSiteMaxRunsPerLaunch / groups_per_run, 1);
+        for (size_t r0 = 0; r0 < n_runs; r0 += per_launch) {
+            launch(r0, (int)std::min(n_runs - r0, per_launch));
+            HIPCHK(ctx, hipGetLastError());
+        }
+        return FTK_OK;
+    };
+    if ((rc = enqueue())) {
+        (void)hipStreamSynchronize(ctx->stream);
+        return rc;
+    }
+    if ((rc = s.finish(true))) (void)hipStreamSynchronize(ctx->stream);
+    return rc;
+}
+
 }  // namespace
 
 extern "C" {
@@ -114,36 +156,13 @@ int ftk_site_profile(ftk_ctx* ctx, int contig_id, const int32_t* centre, const u
     const SiteProfileParams p{half_width, bin_size, n_bins, mapq_min, min_len < 0 ? INT32_MIN : min_len,
                               max_len < 0 ? INT32_MAX : max_len, eff_lmax(&f, *c), use_weights != 0};
     plan.cut(n_sites > 0 && c->n > 0 ? site_run_sites(ctx->n_cu, n_sites, c->n, c->max_end, p) : 0);
-    const size_t n_runs = plan.n_runs(), cells = (size_t)n_groups * (size_t)n_bins;
+    const size_t cells = (size_t)n_groups * (size_t)n_bins;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     int64_t *d_sum = nullptr, *d_cnt = nullptr;
-    Scratch s(ctx);
-    s.out(&d_sum, sum_out, cells);
-    if (count_out) s.out(&d_cnt, count_out, cells);
-    plan.declare(s);
-    if ((rc = s.reserve())) return rc;
-    HIPCHK(ctx, hipMemsetAsync(d_sum, 0, cells * 8, ctx->stream));
-    if (d_cnt) HIPCHK(ctx, hipMemsetAsync(d_cnt, 0, cells * 8, ctx->stream));
-    // From here on the stream may be reading the plan's vectors (pageable staging of this call): every way out, an
-    // error's included, waits for the stream first.
-    auto enqueue = [&]() -> int {
-        if (!n_runs) return FTK_OK;
-        if (int e = plan.upload(ctx)) return e;
-        // at most kSiteMaxRunsPerLaunch workgroups per launch: a grid of any workgroup size stays below 2^32 threads
-        for (size_t r0 = 0; r0 < n_runs; r0 += kSiteMaxRunsPerLaunch) {
-            const int part = (int)std::min(n_runs - r0, (size_t)kSiteMaxRunsPerLaunch);
-            launch_site_profile(ctx->stream, c->v, c->weights, plan.d_words, plan.d_off + r0, plan.d_group + r0, part, p,
-                                (unsigned long long*)d_sum, (unsigned long long*)d_cnt);
-            HIPCHK(ctx, hipGetLastError());
-        }
-        return FTK_OK;
-    };
-    if ((rc = enqueue())) {
-        (void)hipStreamSynchronize(ctx->stream);
-        return rc;
-    }
-    if ((rc = s.finish(true))) (void)hipStreamSynchronize(ctx->stream);
-    return rc;
+    return run_site_call(ctx, plan, {{&d_sum, sum_out, cells}, {&d_cnt, count_out, cells}}, 1, [&](size_t r0, int part) {
+        launch_site_profile(ctx->stream, c->v, c->weights, plan.d_words, plan.d_off + r0, plan.d_group + r0, part, p,
+                            (unsigned long long*)d_sum, (unsigned long long*)d_cnt);
+    });
 }
 
 }  // extern "C"

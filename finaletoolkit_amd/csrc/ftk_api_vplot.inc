@@ -32,36 +32,14 @@ int ftk_site_vplot(ftk_ctx* ctx, int contig_id, const int32_t* centre, const uin
     VplotParams p{half_width, bin_size, n_bins, len_lo, len_hi, len_bin, n_rows, 0, mapq_min, std::max(c->max_len, 0), use_weights != 0};
     p.tile_rows = vplot_tile_rows(ctx->vplot_lds, n_rows, n_bins, use_weights != 0);
     plan.cut(n_sites > 0 && c->n > 0 ? vplot_run_sites(ctx->n_cu, n_sites, c->n, c->max_end, p) : 0);
-    const size_t n_runs = plan.n_runs(), cells = (size_t)n_groups * (size_t)n_rows * (size_t)n_bins;
+    const size_t cells = (size_t)n_groups * (size_t)n_rows * (size_t)n_bins;
     int64_t *d_sum = nullptr, *d_cnt = nullptr;
-    Scratch s(ctx);
-    s.out(&d_sum, sum_out, cells);
-    if (count_out) s.out(&d_cnt, count_out, cells);
-    plan.declare(s);
-    if ((rc = s.reserve())) return rc;
-    HIPCHK(ctx, hipMemsetAsync(d_sum, 0, cells * 8, ctx->stream));
-    if (d_cnt) HIPCHK(ctx, hipMemsetAsync(d_cnt, 0, cells * 8, ctx->stream));
-    // From here on the stream may be reading the plan's vectors (pageable staging of this call): every way out, an
-    // error's included, waits for the stream first.
-    auto enqueue = [&]() -> int {
-        if (!n_runs) return FTK_OK;
-        if (int e = plan.upload(ctx)) return e;
-        // at most kSiteMaxRunsPerLaunch workgroups per launch, a run being one workgroup per tile
-        const size_t per_launch = std::max<size_t>((size_t)kSiteMaxRunsPerLaunch / (size_t)vplot_tiles(p), 1);
-        for (size_t r0 = 0; r0 < n_runs; r0 += per_launch) {
-            const int part = (int)std::min(n_runs - r0, per_launch);
-            launch_site_vplot(ctx->stream, c->v, c->weights, plan.d_words, plan.d_off + r0, plan.d_group + r0, part, p,
-                              (unsigned long long*)d_sum, (unsigned long long*)d_cnt);
-            HIPCHK(ctx, hipGetLastError());
-        }
-        return FTK_OK;
-    };
-    if ((rc = enqueue())) {
-        (void)hipStreamSynchronize(ctx->stream);
-        return rc;
-    }
-    if ((rc = s.finish(true))) (void)hipStreamSynchronize(ctx->stream);
-    return rc;
+    // (a run is one workgroup per tile)
+    return run_site_call(ctx, plan, {{&d_sum, sum_out, cells}, {&d_cnt, count_out, cells}}, (size_t)vplot_tiles(p),
+                         [&](size_t r0, int part) {
+                             launch_site_vplot(ctx->stream, c->v, c->weights, plan.d_words, plan.d_off + r0, plan.d_group + r0, part, p,
+                                               (unsigned long long*)d_sum, (unsigned long long*)d_cnt);
+                         });
 }
 
 }  // extern "C"

@@ -1,4 +1,4 @@
-// Device-only primitives that more than one kernel file uses (included by .hip files only): the wave scan and the
+// Device-only primitives that more than one kernel file uses (included by .hip files only): the wave scan and sums, the
 // position-index bound of the per-base tiles, and the reads of a reference image through
 // its RefView (the G + C count of a span included).  A new kernel file takes these from here.
 #pragma once
@@ -17,6 +17,18 @@ __device__ __forceinline__ int wave_incl_scan_dpp(int x) {
     x += __builtin_amdgcn_update_dpp(0, x, 0x142, 0xa, 0xf, false);
     x += __builtin_amdgcn_update_dpp(0, x, 0x143, 0xc, 0xf, false);
     return x;
+}
+
+// the sum over the 64 lanes of a wave, in every lane
+__device__ __forceinline__ unsigned int wave_sum_u32(unsigned int v) {
+#pragma unroll
+    for (int d = 32; d; d >>= 1) v += __shfl_xor(v, d, 64);
+    return v;
+}
+__device__ __forceinline__ unsigned long long wave_sum_u64x(unsigned long long v) {
+#pragma unroll
+    for (int d = 32; d; d >>= 1) v += __shfl_xor(v, d, 64);
+    return v;
 }
 
 // first fragment of the position-index bin of q (which = 0) or of the bin behind it (which = 1): the conservative

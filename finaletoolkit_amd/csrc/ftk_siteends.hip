@@ -15,19 +15,16 @@
 //                   LDS: per track n_bins 32-bit counts and, with weights, n_bins 64-bit sums in front of them (4 or
 //                   12 bytes per bin; both tracks of 4096 weighted bins take 96 KiB: above a threshold the launch is
 //                   split, and for whole launches above 64 KiB the kernel's dynamic-LDS limit is raised,
-//                   ftk_siteends.h).  A wave takes one site at a time;
-//                   the lanes stride over the candidates, kEndsUnroll loads in flight per lane and column, with coalesced
-//                   reads of start, end and mapq (9 bytes per candidate; 13 with the weight, read only when weights are
-//                   used).  The predicate is branch-free; each end's quotient is estimated in float (d + H < 2^21 is
-//                   exact there) and corrected by one step either way, so it is the integer quotient.  An end in the
-//                   window adds to its bin with LDS atomics; without weights the sum is the count times FTK_WEIGHT_ONE
-//                   and only the count is kept.  With SITES the four window counts (and, weighted, four 64-bit sums) of
-//                   the wave's site stay in registers per lane over the candidate loop, are summed across the wave once
-//                   per site, and lane 0 writes them with plain stores to the row of the site's place in the caller's
-//                   list (order[]): no atomics, so they are deterministic.  A split workgroup handles one end of every
-//                   site (the one that lands in its track: U for track 0 of an unflipped site, D of a flipped one) and
-//                   writes that end's two columns.  At the end of the run the non-zero bins go to the zeroed outputs of
-//                   the run's group with one 64-bit global atomic each.
+//                   ftk_siteends.h).  The scan is the shared one of ftk_sitescan.h: a wave takes one site at a time and
+//                   its lanes stride over the site's candidates.  The predicate is branch-free and each end's bin is
+//                   the integer quotient (quot).  An end in the window adds to its bin with LDS atomics.  With SITES
+//                   the four window counts (and, weighted, four 64-bit sums) of the wave's site stay in registers per
+//                   lane over the candidate loop (locals that the scan's lambda captures by reference), are summed
+//                   across the wave once per site, and lane 0 writes them with plain stores to the row of the site's
+//                   place in the caller's list (order[]): no atomics, so they are deterministic.  A split workgroup
+//                   handles one end of every site (the one that lands in its track: U for track 0 of an unflipped site,
+//                   D of a flipped one) and writes that end's two columns.  At the end of the run the non-zero bins go
+//                   to the zeroed outputs of the run's group.
 //
 // The 32-bit LDS counts cannot wrap under site_run_sites_of's bound per_run <= (2^32 - 1) / n_frag: a fragment has one U
 // end and one D end, a site sends all its U ends to one track and all its D ends to the other, so although a site may
@@ -36,32 +33,12 @@
 // most per_run * n_frag <= 2^32 - 1 to a bin.  The per-lane site counts see a candidate once: below n_frag < 2^31.
 #include <algorithm>
 
-#include "ftk_device.h"
+#include "ftk_sitescan.h"
 #include "ftk_siteends.h"
 
 namespace ftk {
 
 namespace {
-
-constexpr int kEndsUnroll = 4;
-
-__device__ __forceinline__ unsigned int wave_sum_u32(unsigned int v) {
-#pragma unroll
-    for (int d = 32; d; d >>= 1) v += __shfl_xor(v, d, 64);
-    return v;
-}
-__device__ __forceinline__ unsigned long long wave_sum_u64x(unsigned long long v) {
-#pragma unroll
-    for (int d = 32; d; d >>= 1) v += __shfl_xor(v, d, 64);
-    return v;
-}
-
-// integer quotient x / b of 0 <= x < 2^21 from the float estimate (within one of it)
-__device__ __forceinline__ int quot(int x, int b, float rinv) {
-    int k = (int)((float)x * rinv);
-    const int r = x - k * b;
-    return k + (r >= b) - (r < 0);
-}
 
 template <bool WEIGHTED, bool SITES>
 __global__ __launch_bounds__(kSiteThreads) void site_ends_kernel(ContigView cv, const uint32_t* __restrict__ weights,
@@ -76,13 +53,9 @@ __global__ __launch_bounds__(kSiteThreads) void site_ends_kernel(ContigView cv, 
     extern __shared__ unsigned long long ends_s[];  // WEIGHTED: cells sums, then as many counts; else the counts alone
     const int cells = (p.split ? 1 : 2) * p.n_bins;  // what the launch gave the block: track 0's bins, then track 1's
     unsigned int* cnt_s = reinterpret_cast<unsigned int*>(WEIGHTED ? ends_s + cells : ends_s);
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int only = p.split ? (int)blockIdx.y : -1;  // the one track this workgroup holds (gridDim.y == 2), or both
-    for (int k = tid; k < cells; k += kSiteThreads) {
-        if (WEIGHTED) ends_s[k] = 0;
-        cnt_s[k] = 0;
-    }
-    __syncthreads();
+    site_cells_clear<WEIGHTED>(ends_s, cnt_s, cells);
     const int s0 = run_off[blockIdx.x], s1 = run_off[blockIdx.x + 1];
     const int H = p.half_width, b = p.bin_size;
     const float rinv = 1.0f / (float)b;
@@ -98,56 +71,39 @@ __global__ __launch_bounds__(kSiteThreads) void site_ends_kernel(ContigView cv, 
         const int off_u = only < 0 ? tr_u * p.n_bins : 0, off_d = only < 0 ? tr_d * p.n_bins : 0;
         unsigned int wc[4] = {0u, 0u, 0u, 0u};             // left_up, left_down, right_up, right_down of this lane
         unsigned long long ws[4] = {0ull, 0ull, 0ull, 0ull};
-        const int lo = index_bound(cv, (long long)c - H - p.lmax, 0);
-        int hi = index_bound(cv, (long long)c + H, 1);
-        if (hi < lo) hi = lo;
-        for (int base = lo; base < hi; base += 64 * kEndsUnroll) {
-            int fs[kEndsUnroll], fe[kEndsUnroll], q[kEndsUnroll];
-            uint32_t wt[kEndsUnroll];
-            bool valid[kEndsUnroll];
-#pragma unroll
-            for (int u = 0; u < kEndsUnroll; ++u) {
-                const int j = base + u * 64 + lane;  // (hi <= n < 2^31 - 1024: no overflow)
-                valid[u] = j < hi;
-                const int i = valid[u] ? j : base;  // (lo <= base < hi <= n: a fragment of the contig)
-                fs[u] = cv.start[i];
-                fe[u] = cv.end[i];
-                q[u] = cv.mapq[i];
-                wt[u] = WEIGHTED ? weights[i] : 0u;
+        site_scan<WEIGHTED>(cv, weights, c, H, p.lmax, lane, [&](bool valid, int fs, int fe, int q, uint32_t wt) {
+            const int len = fe - fs;
+            const bool pass = valid & (q >= p.mapq_min) & (len >= p.min_len) & (len <= p.max_len) & (len >= 1);
+            const int du = fs - c, dd = fe - 1 - c;  // coordinates < 2^30: no overflow
+            const bool ok_u = pass & (du >= -H) & (du < H) & do_u;
+            const bool ok_d = pass & (dd >= -H) & (dd < H) & do_d;
+            int ku = quot(ok_u ? du + H : 0, b, rinv);  // 0 <= x < 2 H <= 2^21
+            int kd = quot(ok_d ? dd + H : 0, b, rinv);
+            if (flip) {
+                ku = p.n_bins - 1 - ku;
+                kd = p.n_bins - 1 - kd;
             }
+            ku += off_u;  // 0 <= ku, kd < n_bins where the end counts: its cell of the workgroup's tracks
+            kd += off_d;
+            if (ok_u) {
+                atomicAdd(&cnt_s[ku], 1u);
+                if (WEIGHTED) atomicAdd(&ends_s[ku], (unsigned long long)wt);
+            }
+            if (ok_d) {
+                atomicAdd(&cnt_s[kd], 1u);
+                if (WEIGHTED) atomicAdd(&ends_s[kd], (unsigned long long)wt);
+            }
+            if (SITES) {  // (peak + flank < H: an end inside a window is inside [-H, H))
+                const unsigned lu = (unsigned)(-du - near) <= span, ld = (unsigned)(-dd - near) <= span;
+                const unsigned ru = (unsigned)(du - near) <= span, rd = (unsigned)(dd - near) <= span;
+                const unsigned in[4] = {lu & (unsigned)ok_u, ld & (unsigned)ok_d, ru & (unsigned)ok_u, rd & (unsigned)ok_d};
 #pragma unroll
-            for (int u = 0; u < kEndsUnroll; ++u) {
-                const int len = fe[u] - fs[u];
-                const bool pass = valid[u] & (q[u] >= p.mapq_min) & (len >= p.min_len) & (len <= p.max_len) & (len >= 1);
-                const int du = fs[u] - c, dd = fe[u] - 1 - c;  // coordinates < 2^30: no overflow
-                const bool ok_u = pass & do_u & (du >= -H) & (du < H);
-                const bool ok_d = pass & do_d & (dd >= -H) & (dd < H);
-                int ku = quot(ok_u ? du + H : 0, b, rinv);  // 0 <= x < 2 H <= 2^21
-                int kd = quot(ok_d ? dd + H : 0, b, rinv);
-                if (flip) {
-                    ku = p.n_bins - 1 - ku;
-                    kd = p.n_bins - 1 - kd;
-                }
-                if (ok_u) {  // 0 <= ku < n_bins
-                    atomicAdd(&cnt_s[off_u + ku], 1u);
-                    if (WEIGHTED) atomicAdd(&ends_s[off_u + ku], (unsigned long long)wt[u]);
-                }
-                if (ok_d) {
-                    atomicAdd(&cnt_s[off_d + kd], 1u);
-                    if (WEIGHTED) atomicAdd(&ends_s[off_d + kd], (unsigned long long)wt[u]);
-                }
-                if (SITES) {  // (peak + flank < H: an end inside a window is inside [-H, H))
-                    const unsigned lu = (unsigned)(-du - near) <= span, ld = (unsigned)(-dd - near) <= span;
-                    const unsigned ru = (unsigned)(du - near) <= span, rd = (unsigned)(dd - near) <= span;
-                    const unsigned in[4] = {lu & (unsigned)ok_u, ld & (unsigned)ok_d, ru & (unsigned)ok_u, rd & (unsigned)ok_d};
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        wc[j] += in[j];
-                        if (WEIGHTED) ws[j] += in[j] ? (unsigned long long)wt[u] : 0ull;
-                    }
+                for (int j = 0; j < 4; ++j) {
+                    wc[j] += in[j];
+                    if (WEIGHTED) ws[j] += in[j] ? (unsigned long long)wt : 0ull;
                 }
             }
-        }
+        });
         if (SITES) {
             const size_t row = (size_t)order[si] * 4;  // the site's place in the caller's list
 #pragma unroll
@@ -161,35 +117,18 @@ __global__ __launch_bounds__(kSiteThreads) void site_ends_kernel(ContigView cv, 
             }
         }
     }
-    __syncthreads();
     // the group's two tracks lie behind one another: cell t * n_bins + k of a whole run, k of track `only` of a split one
     const size_t first = ((size_t)run_group[blockIdx.x] * 2 + (size_t)(only < 0 ? 0 : only)) * (size_t)p.n_bins;
-    for (int k = tid; k < cells; k += kSiteThreads) {
-        const unsigned long long n = cnt_s[k];
-        const unsigned long long w = WEIGHTED ? ends_s[k] : n * FTK_WEIGHT_ONE;
-        if (w) atomicAdd(&sum_out[first + k], w);
-        if (cnt_out && n) atomicAdd(&cnt_out[first + k], n);
-    }
+    site_cells_flush<WEIGHTED>(ends_s, cnt_s, cells, first, sum_out, cnt_out);
 }
 
 }  // namespace
 
-hipError_t siteends_lds_most(int device, int* most_out) {
-    int limit = 0;
-    hipError_t e = hipDeviceGetAttribute(&limit, hipDeviceAttributeMaxSharedMemoryPerBlock, device);
-    if (e != hipSuccess) return e;
-    if (limit < 12 * kSiteMaxBins) return hipErrorInvalidValue;  // one weighted track of the widest profile (no gfx9 device: 64 KiB is the least any has)
-    const int most = std::min(kSiteEndsLdsMost, limit);
-    if (most > (64 << 10)) {  // (the unweighted kernels take 32 KiB at most)
-        if ((e = hipFuncSetAttribute(reinterpret_cast<const void*>(&site_ends_kernel<true, false>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, most)) != hipSuccess)
-            return e;
-        if ((e = hipFuncSetAttribute(reinterpret_cast<const void*>(&site_ends_kernel<true, true>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, most)) != hipSuccess)
-            return e;
-    }
-    *most_out = most;
-    return hipSuccess;
+hipError_t siteends_lds_most(int device, int* most_out) {  // (the unweighted kernels take 32 KiB at most)
+    return site_lds_limit(device, kSiteEndsLdsMost,
+                          {reinterpret_cast<const void*>(&site_ends_kernel<true, false>),
+                           reinterpret_cast<const void*>(&site_ends_kernel<true, true>)},
+                          most_out);
 }
 
 long long siteends_run_sites(int n_cu, long long n_sites, long long n_frag, int max_end, const SiteEndsParams& p) {

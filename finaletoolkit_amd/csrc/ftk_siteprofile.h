@@ -1,6 +1,8 @@
 // Launcher of the site-profile kernel in ftk_siteprofile.hip (internal).
 #pragma once
 
+#include <initializer_list>
+
 #include "ftk_internal.h"
 
 namespace ftk {
@@ -40,6 +42,11 @@ long long site_run_sites(int n_cu, long long n_sites, long long n_frag, int max_
 // workgroups each (kSiteRunsPerCu workgroups per compute unit are kept, not runs).
 long long site_run_sites_of(int n_cu, long long n_sites, long long n_frag, int max_end, int half_width, int lmax,
                             long long run_candidates, long long groups_per_run);
+
+// The most dynamic LDS a workgroup of `kernels` may take on this device: min(cap, the device's LDS per workgroup); above
+// the 64 KiB a kernel gets without asking, the kernels' limit is raised to it.  hipErrorInvalidValue: the device cannot
+// hold the 12 * kSiteMaxBins bytes of the widest weighted row or track.  Once per context (the caller keeps the result).
+hipError_t site_lds_limit(int device, int cap, std::initializer_list<const void*> kernels, int* limit_out);
 
 // Run r = sites [run_off[r], run_off[r + 1]) of `site` (sorted by group, then centre), all of group run_group[r]:
 // sum[run_group[r] * n_bins + k] and cnt[...] (may be NULL) += the run's profile; both zeroed by the caller.  `weights`

@@ -5,26 +5,18 @@
 //
 // site_profile_kernel  one workgroup per RUN of sites; the host sorted the sites by (group, centre) and cut the list
 //                      into runs that stay inside one group (site_run_sites).  The run's profile lives in LDS: n_bins
-//                      64-bit sums and n_bins 32-bit counts (12 bytes per bin, 48 KiB at most).  A wave takes one site
-//                      at a time; its candidate range comes from the 512-bp index as weighted_window_kernel takes its
-//                      own: [index_bound(c - H - lmax), index_bound(c + H, 1)).  The lanes stride over the candidates,
-//                      kSiteUnroll loads in flight per lane and column, with coalesced reads of start, end and mapq (9
-//                      bytes per candidate; 13 with the weight, which is read only when weights are used).  The
-//                      predicate is branch-free; the bin's quotient is estimated in float (d + H < 2^21 is exact
-//                      there) and corrected by one step either way, so it is the integer quotient.  A passing
-//                      candidate adds to its bin with LDS atomics; without weights the sum is the count times
-//                      FTK_WEIGHT_ONE and only the count is kept.  At the end of the run the non-zero bins go to the
-//                      zeroed outputs of the run's group with one 64-bit global atomic each.
+//                      64-bit sums and n_bins 32-bit counts (12 bytes per bin, 48 KiB at most).  The scan is the shared
+//                      one of ftk_sitescan.h: a wave takes one site at a time and its lanes stride over the site's
+//                      candidates.  The predicate is branch-free and the bin is the integer quotient (quot).  A passing
+//                      candidate adds to its bin with LDS atomics; at the end of the run the non-zero bins go to the
+//                      zeroed outputs of the run's group.
 #include <algorithm>
 
-#include "ftk_device.h"
-#include "ftk_siteprofile.h"
+#include "ftk_sitescan.h"
 
 namespace ftk {
 
 namespace {
-
-constexpr int kSiteUnroll = 4;
 
 template <bool WEIGHTED>
 __global__ __launch_bounds__(kSiteThreads) void site_profile_kernel(ContigView cv, const uint32_t* __restrict__ weights,
@@ -35,12 +27,8 @@ __global__ __launch_bounds__(kSiteThreads) void site_profile_kernel(ContigView c
                                                                     unsigned long long* __restrict__ cnt_out) {
     extern __shared__ unsigned long long sum_s[];  // n_bins sums (WEIGHTED only), then n_bins counts
     unsigned int* cnt_s = reinterpret_cast<unsigned int*>(sum_s + p.n_bins);
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    for (int k = tid; k < p.n_bins; k += kSiteThreads) {
-        sum_s[k] = 0;
-        cnt_s[k] = 0;
-    }
-    __syncthreads();
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    site_cells_clear<WEIGHTED>(sum_s, cnt_s, p.n_bins);
     const int s0 = run_off[blockIdx.x], s1 = run_off[blockIdx.x + 1];
     const int H = p.half_width, b = p.bin_size;
     const float rinv = 1.0f / (float)b;
@@ -48,52 +36,36 @@ __global__ __launch_bounds__(kSiteThreads) void site_profile_kernel(ContigView c
         const uint32_t word = site[si];
         const int c = (int)(word & ~kSiteFlipBit);
         const bool flip = (word & kSiteFlipBit) != 0;
-        const int lo = index_bound(cv, (long long)c - H - p.lmax, 0);
-        int hi = index_bound(cv, (long long)c + H, 1);
-        if (hi < lo) hi = lo;
-        for (int base = lo; base < hi; base += 64 * kSiteUnroll) {
-            int fs[kSiteUnroll], fe[kSiteUnroll], q[kSiteUnroll];
-            uint32_t wt[kSiteUnroll];
-            bool valid[kSiteUnroll];
-#pragma unroll
-            for (int u = 0; u < kSiteUnroll; ++u) {
-                const int j = base + u * 64 + lane;  // (hi <= n < 2^31 - 1024: no overflow)
-                valid[u] = j < hi;
-                const int i = valid[u] ? j : base;  // (lo <= base < hi <= n: a fragment of the contig)
-                fs[u] = cv.start[i];
-                fe[u] = cv.end[i];
-                q[u] = cv.mapq[i];
-                wt[u] = WEIGHTED ? weights[i] : 0u;
+        site_scan<WEIGHTED>(cv, weights, c, H, p.lmax, lane, [&](bool valid, int fs, int fe, int q, uint32_t wt) {
+            const int len = fe - fs;
+            const int mid = (int)(((unsigned)fs + (unsigned)fe) >> 1);  // coordinates < 2^30
+            const int d = mid - c;
+            const bool ok = valid & (q >= p.mapq_min) & (len >= p.min_len) & (len <= p.max_len) & (d >= -H) & (d < H);
+            int k = quot(ok ? d + H : 0, b, rinv);  // 0 <= x < 2 H <= 2^21
+            if (flip) k = p.n_bins - 1 - k;
+            if (ok) {  // 0 <= k < n_bins
+                atomicAdd(&cnt_s[k], 1u);
+                if (WEIGHTED) atomicAdd(&sum_s[k], (unsigned long long)wt);
             }
-#pragma unroll
-            for (int u = 0; u < kSiteUnroll; ++u) {
-                const int len = fe[u] - fs[u];
-                const int mid = (int)(((unsigned)fs[u] + (unsigned)fe[u]) >> 1);  // coordinates < 2^30
-                const int d = mid - c;
-                const bool ok = valid[u] & (q[u] >= p.mapq_min) & (len >= p.min_len) & (len <= p.max_len) & (d >= -H) & (d < H);
-                const int x = ok ? d + H : 0;  // 0 <= x < 2 H <= 2^21
-                int k = (int)((float)x * rinv);  // within one of x / b
-                const int r = x - k * b;
-                k += (r >= b) - (r < 0);
-                if (flip) k = p.n_bins - 1 - k;
-                if (ok) {  // 0 <= k < n_bins
-                    atomicAdd(&cnt_s[k], 1u);
-                    if (WEIGHTED) atomicAdd(&sum_s[k], (unsigned long long)wt[u]);
-                }
-            }
-        }
+        });
     }
-    __syncthreads();
-    const size_t row = (size_t)run_group[blockIdx.x] * (size_t)p.n_bins;
-    for (int k = tid; k < p.n_bins; k += kSiteThreads) {
-        const unsigned long long n = cnt_s[k];
-        const unsigned long long w = WEIGHTED ? sum_s[k] : n * FTK_WEIGHT_ONE;
-        if (w) atomicAdd(&sum_out[row + k], w);
-        if (cnt_out && n) atomicAdd(&cnt_out[row + k], n);
-    }
+    site_cells_flush<WEIGHTED>(sum_s, cnt_s, p.n_bins, (size_t)run_group[blockIdx.x] * (size_t)p.n_bins, sum_out, cnt_out);
 }
 
 }  // namespace
+
+hipError_t site_lds_limit(int device, int cap, std::initializer_list<const void*> kernels, int* limit_out) {
+    int limit = 0;
+    hipError_t e = hipDeviceGetAttribute(&limit, hipDeviceAttributeMaxSharedMemoryPerBlock, device);
+    if (e != hipSuccess) return e;
+    if (limit < 12 * kSiteMaxBins) return hipErrorInvalidValue;  // (no gfx9 device: 64 KiB is the least any has)
+    limit = std::min(cap, limit);
+    if (limit > (64 << 10))
+        for (const void* k : kernels)
+            if ((e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, limit)) != hipSuccess) return e;
+    *limit_out = limit;
+    return hipSuccess;
+}
 
 long long site_run_sites_of(int n_cu, long long n_sites, long long n_frag, int max_end, int half_width, int lmax,
                             long long run_candidates, long long groups_per_run) {

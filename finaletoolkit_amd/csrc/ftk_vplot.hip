@@ -10,22 +10,19 @@
 //                    many rows as the LDS budget holds (ftk_vplot.h).  blockIdx.y is the tile; the last one may hold
 //                    fewer rows.  A tile takes only the lengths of its own rows, so its candidate range reaches back by
 //                    its own longest passing length - min(contig's longest, the tile's last length) - and the tiles of
-//                    short rows read less.  Inside, the loop is site_profile_kernel's: a wave takes one site at a
-//                    time, the lanes stride over the candidates with kVplotUnroll coalesced loads in flight per lane
-//                    and column, the predicate is branch-free, and both quotients are estimated in float (L - len_lo <
-//                    2^16 and d + H < 2^21 are exact there) and corrected by one step either way.  A passing candidate
-//                    adds to its cell with LDS atomics.  At the end of the run the non-zero cells go to the zeroed
-//                    outputs with one 64-bit global atomic per array.
+//                    short rows read less.  Inside, the scan is the shared one of ftk_sitescan.h: a wave takes one
+//                    site at a time and its lanes stride over the site's candidates.  The predicate is branch-free, and
+//                    both the row and the column are integer quotients (quot: L - len_lo < 2^16 and d + H < 2^21).  A
+//                    passing candidate adds to its cell with LDS atomics.  At the end of the run the non-zero cells go
+//                    to the zeroed outputs.
 #include <algorithm>
 
-#include "ftk_device.h"
+#include "ftk_sitescan.h"
 #include "ftk_vplot.h"
 
 namespace ftk {
 
 namespace {
-
-constexpr int kVplotUnroll = 4;
 
 template <bool WEIGHTED>
 __global__ __launch_bounds__(kSiteThreads) void site_vplot_kernel(ContigView cv, const uint32_t* __restrict__ weights,
@@ -36,18 +33,14 @@ __global__ __launch_bounds__(kSiteThreads) void site_vplot_kernel(ContigView cv,
                                                                   unsigned long long* __restrict__ cnt_out) {
     extern __shared__ unsigned long long vp_s[];  // WEIGHTED: tile_rows * n_bins sums, then as many counts; else the counts alone
     unsigned int* cnt_s = reinterpret_cast<unsigned int*>(WEIGHTED ? vp_s + p.tile_rows * p.n_bins : vp_s);
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int row0 = (int)blockIdx.y * p.tile_rows;              // < n_rows: the grid holds ceil(n_rows / tile_rows) tiles
     const int rows = min(p.tile_rows, p.n_rows - row0);
     const int cells = rows * p.n_bins;                           // <= tile_rows * n_bins: what the launch gave the block
     const int tlo = p.len_lo + row0 * p.len_bin, thi = tlo + rows * p.len_bin - 1;  // the tile's lengths: len_lo <= tlo <= thi <= len_hi
     const int lmax = min(p.contig_lmax, thi);                    // the longest fragment that can pass in this tile
     if (lmax < tlo) return;                                      // (the whole block: the contig has no fragment this long)
-    for (int k = tid; k < cells; k += kSiteThreads) {
-        if (WEIGHTED) vp_s[k] = 0;
-        cnt_s[k] = 0;
-    }
-    __syncthreads();
+    site_cells_clear<WEIGHTED>(vp_s, cnt_s, cells);
     const int s0 = run_off[blockIdx.x], s1 = run_off[blockIdx.x + 1];
     const int H = p.half_width, b = p.bin_size, lb = p.len_bin;
     const float rinv = 1.0f / (float)b, linv = 1.0f / (float)lb;
@@ -55,75 +48,32 @@ __global__ __launch_bounds__(kSiteThreads) void site_vplot_kernel(ContigView cv,
         const uint32_t word = site[si];
         const int c = (int)(word & ~kSiteFlipBit);
         const bool flip = (word & kSiteFlipBit) != 0;
-        const int lo = index_bound(cv, (long long)c - H - lmax, 0);
-        int hi = index_bound(cv, (long long)c + H, 1);
-        if (hi < lo) hi = lo;
-        for (int base = lo; base < hi; base += 64 * kVplotUnroll) {
-            int fs[kVplotUnroll], fe[kVplotUnroll], q[kVplotUnroll];
-            uint32_t wt[kVplotUnroll];
-            bool valid[kVplotUnroll];
-#pragma unroll
-            for (int u = 0; u < kVplotUnroll; ++u) {
-                const int j = base + u * 64 + lane;  // (hi <= n < 2^31 - 1024: no overflow)
-                valid[u] = j < hi;
-                const int i = valid[u] ? j : base;  // (lo <= base < hi <= n: a fragment of the contig)
-                fs[u] = cv.start[i];
-                fe[u] = cv.end[i];
-                q[u] = cv.mapq[i];
-                wt[u] = WEIGHTED ? weights[i] : 0u;
+        site_scan<WEIGHTED>(cv, weights, c, H, lmax, lane, [&](bool valid, int fs, int fe, int q, uint32_t wt) {
+            const int len = fe - fs;
+            const int mid = (int)(((unsigned)fs + (unsigned)fe) >> 1);  // coordinates < 2^30
+            const int d = mid - c;
+            const bool ok = valid & (q >= p.mapq_min) & (len >= tlo) & (len <= thi) & (d >= -H) & (d < H);
+            int k = quot(ok ? d + H : 0, b, rinv);           // 0 <= x < 2 H <= 2^21
+            if (flip) k = p.n_bins - 1 - k;
+            const int r = quot(ok ? len - tlo : 0, lb, linv);  // 0 <= y < rows * lb <= 2^16
+            if (ok) {  // 0 <= r < rows, 0 <= k < n_bins
+                const int cell = r * p.n_bins + k;
+                atomicAdd(&cnt_s[cell], 1u);
+                if (WEIGHTED) atomicAdd(&vp_s[cell], (unsigned long long)wt);
             }
-#pragma unroll
-            for (int u = 0; u < kVplotUnroll; ++u) {
-                const int len = fe[u] - fs[u];
-                const int mid = (int)(((unsigned)fs[u] + (unsigned)fe[u]) >> 1);  // coordinates < 2^30
-                const int d = mid - c;
-                const bool ok = valid[u] & (q[u] >= p.mapq_min) & (len >= tlo) & (len <= thi) & (d >= -H) & (d < H);
-                const int x = ok ? d + H : 0;  // 0 <= x < 2 H <= 2^21
-                int k = (int)((float)x * rinv);  // within one of x / b
-                const int rk = x - k * b;
-                k += (rk >= b) - (rk < 0);
-                if (flip) k = p.n_bins - 1 - k;
-                const int y = ok ? len - tlo : 0;  // 0 <= y < rows * lb <= 2^16
-                int r = (int)((float)y * linv);  // within one of y / lb
-                const int rr = y - r * lb;
-                r += (rr >= lb) - (rr < 0);
-                if (ok) {  // 0 <= r < rows, 0 <= k < n_bins
-                    const int cell = r * p.n_bins + k;
-                    atomicAdd(&cnt_s[cell], 1u);
-                    if (WEIGHTED) atomicAdd(&vp_s[cell], (unsigned long long)wt[u]);
-                }
-            }
-        }
+        });
     }
-    __syncthreads();
     // the tile's rows lie behind one another in the group's matrix: cell (r, k) is output cell (row0 + r) * n_bins + k
     const size_t first = ((size_t)run_group[blockIdx.x] * (size_t)p.n_rows + (size_t)row0) * (size_t)p.n_bins;
-    for (int k = tid; k < cells; k += kSiteThreads) {
-        const unsigned long long n = cnt_s[k];
-        const unsigned long long w = WEIGHTED ? vp_s[k] : n * FTK_WEIGHT_ONE;
-        if (w) atomicAdd(&sum_out[first + k], w);
-        if (cnt_out && n) atomicAdd(&cnt_out[first + k], n);
-    }
+    site_cells_flush<WEIGHTED>(vp_s, cnt_s, cells, first, sum_out, cnt_out);
 }
 
 }  // namespace
 
 hipError_t vplot_lds_budget(int device, int* budget_out) {
-    int limit = 0;
-    hipError_t e = hipDeviceGetAttribute(&limit, hipDeviceAttributeMaxSharedMemoryPerBlock, device);
-    if (e != hipSuccess) return e;
-    if (limit < 12 * kSiteMaxBins) return hipErrorInvalidValue;  // one row of the widest matrix (no gfx9 device: 64 KiB is the least any has)
-    const int budget = std::min(kVplotLdsBytes, limit);
-    if (budget > (64 << 10)) {
-        if ((e = hipFuncSetAttribute(reinterpret_cast<const void*>(&site_vplot_kernel<true>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, budget)) != hipSuccess)
-            return e;
-        if ((e = hipFuncSetAttribute(reinterpret_cast<const void*>(&site_vplot_kernel<false>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, budget)) != hipSuccess)
-            return e;
-    }
-    *budget_out = budget;
-    return hipSuccess;
+    return site_lds_limit(device, kVplotLdsBytes,
+                          {reinterpret_cast<const void*>(&site_vplot_kernel<true>), reinterpret_cast<const void*>(&site_vplot_kernel<false>)},
+                          budget_out);
 }
 
 long long vplot_run_sites(int n_cu, long long n_sites, long long n_frag, int max_end, const VplotParams& p) {

@@ -820,6 +820,22 @@ class Engine:
         return sums, n_weighted
 
     # -- site-aggregated midpoint profiles (csrc/ftk_siteprofile.hip) --------------------
+    @staticmethod
+    def _site_inputs(centres, flip, groups):
+        """The sites of a site call as its leading arguments, ``(centre, flip, group, n_sites)`` - contiguous int32 /
+        uint8 / int32 behind the pointers, NULL for an array that was not given or has no site - and ``out``, which
+        gives an output array's pointer: for one without an element that of a spare cell (the call fails or writes
+        nothing)."""
+        c = np.ascontiguousarray(centres, dtype=np.int32)
+        fl = None if flip is None else np.ascontiguousarray(np.asarray(flip) != 0, dtype=np.uint8)
+        gr = None if groups is None else np.ascontiguousarray(groups, dtype=np.int32)
+        for other, what in ((fl, "flip"), (gr, "groups")):
+            if other is not None and other.shape != c.shape:
+                raise ValueError(f"{what} should have one entry per site")
+        keep = np.empty(1, np.int64)
+        sites = tuple(L.ptr(a) if a is not None and len(c) else None for a in (c, fl, gr)) + (len(c),)
+        return sites, lambda a, _alive=(c, fl, gr): L.ptr(a if a.size else keep)  # (`out` keeps the arrays behind `sites`)
+
     def site_profile(self, name: str, centres: Sequence, flip=None, groups=None, n_groups: int = 1, half_width: int = 1000,
                      bin_size: int = 1, quality_threshold=30, min_length=None, max_length=None, weighted: bool = False):
         """``(sums, counts)`` int64 of shape ``(n_groups, 2 * half_width // bin_size)`` (``ftk_site_profile``): the
@@ -830,21 +846,14 @@ class Engine:
         where ``flip[i]`` is set (a site on the - strand).  ``weighted=False``: every fragment weighs ``_lib.WEIGHT_ONE``
         and the contig needs no weight column.  ``flip=None``: no site is flipped; ``groups=None``: all in group 0.  Sites
         come in any order and are independent: one listed twice counts twice."""
-        c = np.ascontiguousarray(centres, dtype=np.int32)
-        fl = None if flip is None else np.ascontiguousarray(np.asarray(flip) != 0, dtype=np.uint8)
-        gr = None if groups is None else np.ascontiguousarray(groups, dtype=np.int32)
-        for other, what in ((fl, "flip"), (gr, "groups")):
-            if other is not None and other.shape != c.shape:
-                raise ValueError(f"{what} should have one entry per site")
+        sites, out = self._site_inputs(centres, flip, groups)
         n_bins = 2 * int(half_width) // max(int(bin_size), 1)
         shape = (max(int(n_groups), 0), min(max(n_bins, 0), 4096))
         sums, counts = np.zeros(shape, np.int64), np.zeros(shape, np.int64)
-        keep = np.empty(1, np.int64)  # (a pointer for outputs without an element: the call fails or writes nothing)
         self._check(self.lib.ftk_site_profile(
-            self.ctx, self.contig_id(name), L.ptr(c) if len(c) else None, L.ptr(fl) if fl is not None and len(c) else None,
-            L.ptr(gr) if gr is not None and len(c) else None, len(c), int(n_groups), int(half_width), int(bin_size),
+            self.ctx, self.contig_id(name), *sites, int(n_groups), int(half_width), int(bin_size),
             int(quality_threshold), -1 if min_length is None else int(min_length), -1 if max_length is None else int(max_length),
-            int(bool(weighted)), L.ptr(sums if sums.size else keep), L.ptr(counts if counts.size else keep)))
+            int(bool(weighted)), out(sums), out(counts)))
         return sums, counts
 
     # -- fragment length x offset maps around sites (csrc/ftk_vplot.hip) ----------------
@@ -858,24 +867,16 @@ class Engine:
         = (L - len_lo) // len_bin`` and ``k = (d + half_width) // bin_size`` - ``k`` counted from the other end where
         ``flip[i]`` is set; the length axis is never reversed.  ``weighted``, ``flip``, ``groups`` and the sites' order:
         as in ``site_profile``."""
-        c = np.ascontiguousarray(centres, dtype=np.int32)
-        fl = None if flip is None else np.ascontiguousarray(np.asarray(flip) != 0, dtype=np.uint8)
-        gr = None if groups is None else np.ascontiguousarray(groups, dtype=np.int32)
-        for other, what in ((fl, "flip"), (gr, "groups")):
-            if other is not None and other.shape != c.shape:
-                raise ValueError(f"{what} should have one entry per site")
+        sites, out = self._site_inputs(centres, flip, groups)
         n_bins = 2 * int(half_width) // max(int(bin_size), 1)
         n_rows = (int(len_hi) - int(len_lo) + 1) // max(int(len_bin), 1)
         shape = [max(int(n_groups), 0), min(max(n_rows, 0), 4096), min(max(n_bins, 0), 4096)]
         if shape[0] * shape[1] * shape[2] > 1 << 28:  # (the call fails and writes nothing)
             shape[0] = 0
         sums, counts = np.zeros(shape, np.int64), np.zeros(shape, np.int64)
-        keep = np.empty(1, np.int64)  # (a pointer for outputs without an element: the call fails or writes nothing)
         self._check(self.lib.ftk_site_vplot(
-            self.ctx, self.contig_id(name), L.ptr(c) if len(c) else None, L.ptr(fl) if fl is not None and len(c) else None,
-            L.ptr(gr) if gr is not None and len(c) else None, len(c), int(n_groups), int(half_width), int(bin_size),
-            int(len_lo), int(len_hi), int(len_bin), int(mapq_min), int(bool(weighted)), L.ptr(sums if sums.size else keep),
-            L.ptr(counts if counts.size else keep)))
+            self.ctx, self.contig_id(name), *sites, int(n_groups), int(half_width), int(bin_size),
+            int(len_lo), int(len_hi), int(len_bin), int(mapq_min), int(bool(weighted)), out(sums), out(counts)))
         return sums, counts
 
     # -- fragment-end profiles and OCF window sums around sites (csrc/ftk_siteends.hip) --
@@ -894,27 +895,19 @@ class Engine:
         flank]``, in genome orientation (``flip`` is not applied; ``0 <= flank < peak``, ``peak + flank < half_width``).
         ``OCF = (left_down - left_up) + (right_up - right_down)``.  ``weighted``, ``flip``, ``groups`` and the sites'
         order: as in ``site_profile``."""
-        c = np.ascontiguousarray(centres, dtype=np.int32)
-        fl = None if flip is None else np.ascontiguousarray(np.asarray(flip) != 0, dtype=np.uint8)
-        gr = None if groups is None else np.ascontiguousarray(groups, dtype=np.int32)
-        for other, what in ((fl, "flip"), (gr, "groups")):
-            if other is not None and other.shape != c.shape:
-                raise ValueError(f"{what} should have one entry per site")
+        sites, out = self._site_inputs(centres, flip, groups)
         n_bins = 2 * int(half_width) // max(int(bin_size), 1)
         shape = [max(int(n_groups), 0), 2, min(max(n_bins, 0), 4096)]
         if shape[0] * shape[1] * shape[2] > 1 << 28:  # (the call fails and writes nothing)
             shape[0] = 0
         sums, counts = np.zeros(shape, np.int64), np.zeros(shape, np.int64)
         per_site = peak is not None
-        site_sums, site_counts = np.zeros((len(c), 4), np.int64), np.zeros((len(c), 4), np.int64)
-        keep = np.empty(1, np.int64)  # (a pointer for outputs without an element: the call fails or writes nothing)
+        site_sums, site_counts = np.zeros((sites[3], 4), np.int64), np.zeros((sites[3], 4), np.int64)
         self._check(self.lib.ftk_site_ends(
-            self.ctx, self.contig_id(name), L.ptr(c) if len(c) else None, L.ptr(fl) if fl is not None and len(c) else None,
-            L.ptr(gr) if gr is not None and len(c) else None, len(c), int(n_groups), int(half_width), int(bin_size),
+            self.ctx, self.contig_id(name), *sites, int(n_groups), int(half_width), int(bin_size),
             int(quality_threshold), -1 if min_length is None else int(min_length), -1 if max_length is None else int(max_length),
-            int(bool(weighted)), int(peak) if per_site else 0, int(flank) if per_site else 0, L.ptr(sums if sums.size else keep),
-            L.ptr(counts if counts.size else keep), (L.ptr(site_sums if len(c) else keep)) if per_site else None,
-            (L.ptr(site_counts if len(c) else keep)) if per_site else None))
+            int(bool(weighted)), int(peak) if per_site else 0, int(flank) if per_site else 0, out(sums), out(counts),
+            out(site_sums) if per_site else None, out(site_counts) if per_site else None))
         return (sums, counts, site_sums, site_counts) if per_site else (sums, counts)
 
     # -- periodograms of score runs (csrc/ftk_spectrum.hip) --------------------------------

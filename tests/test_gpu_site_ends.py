@@ -266,6 +266,39 @@ def test_site_lists(engine, world):
     assert (cnt["many_groups"].sum(axis=(1, 2)) > 0).sum() > 0.8 * len(lists["many_groups"][0])
 
 
+def test_more_runs_than_one_split_launch_holds(engine, world, monkeypatch):
+    """More than 2^19 runs (one group per site) of two workgroups each (``FTK_SITE_ENDS_SPLIT=1``): a launch takes 2^19
+    runs, not the 2^20 of an unsplit one, and the call splits its launches.  One bin, so the restatement is two
+    bisections per site and end on the sorted ends and a running sum of the weights - as the helper's per-site rows are."""
+    monkeypatch.setenv("FTK_SITE_ENDS_SPLIT", "1")
+    rng = np.random.default_rng(21)
+    n = (1 << 19) + 37
+    centres = rng.integers(2_500, 42_000, n).astype(np.int32)  # (clear of the copies: 10^5 sites on them would take seconds)
+    centres[:3] = (1_075, U_EVEN, D_LONG)
+    groups = rng.permutation(n).astype(np.int32)
+    flip = rng.integers(0, 2, n).astype(np.uint8)
+    cols, w = world["cols"], world["weights"]["zeros20"]
+    engine.set_weights("se:plain", w)
+    H, peak, flank = 300, 60, 10
+    s, e = (np.asarray(cols[k], np.int64) for k in range(2))
+    keep = passing(cols, 30, 120, 180)
+    c = centres.astype(np.int64)
+    want = [np.zeros((n, 2, 1), np.int64), np.zeros((n, 2, 1), np.int64), np.zeros((n, 4), np.int64), np.zeros((n, 4), np.int64)]
+    for kind, x in enumerate((s[keep], e[keep] - 1)):  # 0: the U ends, 1: the D ends
+        o = np.argsort(x, kind="stable")
+        x, run = x[o], np.concatenate([[0], np.cumsum(w.astype(np.int64)[keep][o])])
+        lo, hi = np.searchsorted(x, c - H, "left"), np.searchsorted(x, c + H, "left")
+        track = kind ^ flip  # a flipped site's ends count in the other track (and in the same, only, bin)
+        want[0][groups, track, 0], want[1][groups, track, 0] = run[hi] - run[lo], hi - lo
+        for side, mid in enumerate((c - peak, c + peak)):  # genome orientation: no flip; closed on both sides
+            lo, hi = np.searchsorted(x, mid - flank, "left"), np.searchsorted(x, mid + flank, "right")
+            want[2][:, 2 * side + kind], want[3][:, 2 * side + kind] = run[hi] - run[lo], hi - lo
+    got = engine.site_ends("se:plain", centres, flip, groups, n, H, 2 * H, 30, 120, 180, weighted=True, peak=peak, flank=flank)
+    assert_same(got, tuple(want), "split launches")
+    assert want[1][groups[0]].sum() >= 2 * N_DUP and (want[1][1 << 19:] > 0).any()  # groups of the second launch count
+    assert (want[3][groups >= 1 << 19] > 0).any()  # and so do rows of its sites
+
+
 # ---- 5. weights --------------------------------------------------------------------------------------------------------------
 def test_weights(engine, world):
     from finaletoolkit_amd import _lib as L
