@@ -52,7 +52,8 @@ _FLAT_BY_MODULE = {
     "utils": ("frag_generator", "frag_array", "frags_in_region", "agg_bw", "get_intervals", "overlaps", "gen_kmers",
               "chrom_sizes_to_dict", "chrom_sizes_to_list", "reverse_complement", "frag_export", "frag_filter",
               "frag_depth", "frag_depth_track", "frag_gc_bias", "frag_gc_coverage", "gc_weights", "read_gc_bias_table",
-              "frag_site_profile", "read_sites", "frag_vplot", "VPlot", "frag_wps_spectrum", "WpsSpectrum", "frag_ocf", "OCF"),
+              "frag_site_profile", "read_sites", "frag_vplot", "VPlot", "frag_wps_spectrum", "WpsSpectrum", "frag_ocf", "OCF",
+              "frag_wps_peaks", "WpsPeaks"),
     "genome": ("GenomeGaps", "ContigGaps", "ucsc_hg19_gap_bed", "b37_gap_bed", "ucsc_hg38_gap_bed"),
     "io": ("Fragment", "AlignmentWrapper"),
 }

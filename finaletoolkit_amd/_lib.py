@@ -32,6 +32,9 @@ OPEN_HI = 2 ** 31 - 1
 LEN_OPEN = -1
 GC_MAX_LEN = 1000  # FTK_GC_MAX_LEN
 WEIGHT_ONE = 65536  # FTK_WEIGHT_ONE
+PEAKS_MAX_REGION = 1024  # FTK_PEAKS_MAX_REGION
+PEAKS_MAX_GAP = 63  # FTK_PEAKS_MAX_GAP
+PEAKS_TILE = 1024  # kPeaksTile: positions per workgroup of the mark pass
 SPECTRUM_TILE = 16 << 10  # kSpectrumLdsSamples: a run of up to this many samples is folded out of LDS, a longer one from memory
 POLICY = {"midpoint": 0, "any": 1}
 POLICY_FETCH = 2  # no intersect test: the index query alone (AlignmentWrapper.fetch)
@@ -69,6 +72,7 @@ EXPORTS = [
     "ftk_site_vplot",
     "ftk_site_ends",
     "ftk_track_spectrum", "ftk_wps_spectrum",
+    "ftk_track_peaks", "ftk_wps_peaks",
 ]
 
 
@@ -347,6 +351,9 @@ def load() -> C.CDLL:
     lib.ftk_site_ends.argtypes = [vp, C.c_int, vp, vp, vp, i64, i32, i32, i32, i32, i32, i32, C.c_int, i32, i32, vp, vp, vp, vp]
     lib.ftk_track_spectrum.argtypes = [vp, vp, vp, i64, vp, i32, C.c_double, C.c_int, vp, vp]
     lib.ftk_wps_spectrum.argtypes = [vp, C.c_int, vp, vp, i64, i64, i32, i32, i32, i32, vp, i32, C.c_double, C.c_int, i64, vp, vp]
+    peaks_out = [C.POINTER(vp)] * 6 + [C.POINTER(i64), vp]  # run, start, stop, summit, height, area, n_calls, stats
+    lib.ftk_track_peaks.argtypes = [vp, vp, vp, i64, i64, i32, i32, i32, i32] + peaks_out
+    lib.ftk_wps_peaks.argtypes = [vp, C.c_int, vp, vp, i64, i64, i32, i32, i32, i32, i32, i32, vp, vp, i32, i32, i32, i32, i64] + peaks_out
     lib.ftk_comm_unique_id.argtypes = [C.c_char_p]
     lib.ftk_comm_create.argtypes = [vp, C.c_int, C.c_int, C.c_char_p, C.POINTER(vp)]
     lib.ftk_comm_size.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]

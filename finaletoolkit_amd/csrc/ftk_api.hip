@@ -152,7 +152,7 @@ class Scratch {
     }
 
   private:
-    static constexpr int kMaxBufs = 16;
+    static constexpr int kMaxBufs = 48;
     struct Buf {
         void *var, *d, *host;  // the caller's pointer variable; the buffer in the scratch (place()); the user's host array or nullptr
         size_t bytes, off;
@@ -1274,3 +1274,4 @@ static int wps_params(ftk_ctx* ctx, const ContigData& c, int64_t chrom_size, int
 #include "ftk_api_vplot.inc"
 #include "ftk_api_siteends.inc"
 #include "ftk_api_spectrum.inc"
+#include "ftk_api_peaks.inc"

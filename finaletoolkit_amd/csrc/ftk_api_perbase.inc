@@ -235,6 +235,59 @@ int plan_interval_tiles(ftk_ctx* ctx, Scratch& s, const int64_t* iv_start, const
     return FTK_OK;
 }
 }  // extern "C++"
+
+// The device half of ftk_wps_adjust over runs whose scores are already on the device: the tile lists of both kinds
+// counted and filled from the run offsets, the running median (or mean) and the Savitzky-Golay pass.  The caller
+// validates the runs, declares the buffers in its own Scratch and owns every copy; ftk_wps_peaks runs it batch after
+// batch on scores that never leave the device.
+struct AdjustChain {
+    int W = 0, tile = 0;
+    bool fast = false;  // the histogram median in front of the sort kernel
+    int64_t n_iv = 0;
+    AdjustTile *d_tiles = nullptr, *d_fast = nullptr;
+    int *d_todo = nullptr, *d_pre0 = nullptr, *d_pre1 = nullptr;
+    int64_t* d_offs = nullptr;
+
+    // at most n_iv runs with total_out outputs between them (of any one launch of the call)
+    void declare(Scratch& s, int64_t n_iv_, int W_, bool use_mean, int64_t total_out) {
+        // FTK_ADJUST_HIST=0: every interval through the sort kernel (the tests hold the two medians together)
+        static const bool use_hist = !(getenv("FTK_ADJUST_HIST") && atoi(getenv("FTK_ADJUST_HIST")) == 0);
+        W = W_;
+        n_iv = n_iv_;
+        adjust_sort_size(W, &tile);
+        fast = use_hist && !use_mean;
+        s.tmp(&d_tiles, (size_t)tiles_ub(total_out));
+        if (fast) {
+            s.tmp(&d_fast, (size_t)(total_out / kAdjustFastTile + n_iv));
+            s.tmp(&d_todo, (size_t)n_iv + 2);
+        }
+        s.tmp(&d_offs, (size_t)n_iv + 1);
+        s.tmp(&d_pre0, (size_t)n_iv + 1);
+        s.tmp(&d_pre1, (size_t)n_iv + 1);
+    }
+    int64_t tiles_ub(int64_t total_out) const { return total_out / tile + n_iv; }
+    // the tiles of a run of len scores, added to *n_tiles / *n_fast
+    void count(int64_t len, int64_t* n_tiles, int64_t* n_fast) const {
+        const int64_t m = len - W;
+        *n_tiles += (m + tile - 1) / tile;
+        if (fast) *n_fast += (m + kAdjustFastTile - 1) / kAdjustFastTile;
+    }
+    // offs_src: n + 1 run offsets in device-readable memory.  Touches nothing but the chain's own arrays whatever they hold.
+    void counts(hipStream_t st, const int64_t* offs_src, int64_t n) const {
+        launch_adjust_tile_counts(st, offs_src, d_offs, (int)n, W, tile, fast ? kAdjustFastTile : 0, d_pre0, d_pre1, d_todo);
+    }
+    // behind counts(), for the same n runs: their n_tiles / n_fast tiles filled, d_in filtered into d_adj and, with sw, that
+    // smoothed into d_out
+    void run(hipStream_t st, int64_t n, int64_t n_tiles, int64_t n_fast, const double* d_in, const double* d_sub, int use_mean,
+             double* d_adj, int sw, const double* d_coef, const double* d_edge, double* d_out) const {
+        AdjustTile* fast_tiles = n_fast ? d_fast : nullptr;
+        int* todo = n_fast ? d_todo : nullptr;
+        launch_adjust_tile_fill(st, d_offs, (int)n, W, tile, n_fast ? kAdjustFastTile : 0, d_pre0, d_pre1, d_tiles, (int)n_tiles,
+                                fast_tiles, (int)n_fast);
+        launch_adjust_filter(st, d_in, d_tiles, (int)n_tiles, d_sub, W, use_mean, d_adj, fast_tiles, (int)n_fast, todo, (int)n);
+        if (sw) launch_savgol(st, d_adj, d_tiles, (int)n_tiles, d_coef, d_edge, sw, d_out);
+    }
+};
 }  // namespace
 
 int ftk_wps(ftk_ctx* ctx, int contig_id, int64_t start, int64_t stop, int64_t chrom_size, int32_t window_size,
@@ -583,11 +636,6 @@ int ftk_wps_adjust(ftk_ctx* ctx, const double* scores, const int64_t* offsets, i
     const int sw = savgol_window;
     if (sw < 0 || (sw > 0 && (!(sw & 1) || !savgol_coef || !savgol_edge)))
         return fail(ctx, FTK_ERR_INVALID, "savgol_window must be odd and come with coef/edge arrays");
-    int tile;
-    adjust_sort_size(W, &tile);
-    // FTK_ADJUST_HIST=0: every interval through the sort kernel (the tests hold the two medians together)
-    static const bool use_hist = !(getenv("FTK_ADJUST_HIST") && atoi(getenv("FTK_ADJUST_HIST")) == 0);
-    const bool fast = use_hist && !use_mean;
     // The tiles are counted here and BUILT on the device from the run offsets.  The device's half starts FIRST: the
     // offsets go into page-locked memory and the counting kernel out (it reads and writes nothing but its own arrays,
     // whatever the offsets hold), and the runs are checked on the host while it runs.
@@ -600,24 +648,14 @@ int ftk_wps_adjust(ftk_ctx* ctx, const double* scores, const int64_t* offsets, i
                             (long long)len, W);
         }
     if (total_out < 0 || total_in > (int64_t(1) << 40)) return fail(ctx, FTK_ERR_INVALID, "run offsets out of range");
-    const int64_t tiles_ub = total_out / tile + n_iv, fast_ub = fast ? total_out / kAdjustFastTile + n_iv : 0;
-    if (tiles_ub > INT32_MAX - 1024) return fail(ctx, FTK_ERR_INVALID, "too many tiles in one call");
     HIPCHK(ctx, hipSetDevice(ctx->device));
     const bool in_dev = is_device_ptr(scores);
     const int half = sw / 2;
-    AdjustTile *d_tiles = nullptr, *d_fast = nullptr;
-    int *d_todo = nullptr, *d_pre0 = nullptr, *d_pre1 = nullptr;
-    int64_t* d_offs = nullptr;
     double *d_sub = nullptr, *d_coef = nullptr, *d_edge = nullptr, *d_staged = nullptr, *d_out = nullptr, *d_adj = nullptr;
     Scratch s(ctx);
-    s.tmp(&d_tiles, (size_t)tiles_ub);
-    if (fast) {
-        s.tmp(&d_fast, (size_t)fast_ub);
-        s.tmp(&d_todo, (size_t)n_iv + 2);
-    }
-    s.tmp(&d_offs, (size_t)n_iv + 1);
-    s.tmp(&d_pre0, (size_t)n_iv + 1);
-    s.tmp(&d_pre1, (size_t)n_iv + 1);
+    AdjustChain chain;
+    chain.declare(s, n_iv, W, use_mean != 0, total_out);
+    if (chain.tiles_ub(total_out) > INT32_MAX - 1024) return fail(ctx, FTK_ERR_INVALID, "too many tiles in one call");
     if (edge_sub) s.tmp(&d_sub, n_iv);
     if (sw) {
         s.tmp(&d_coef, sw);
@@ -641,8 +679,7 @@ int ftk_wps_adjust(ftk_ctx* ctx, const double* scores, const int64_t* offsets, i
         memcpy(ctx->param_stage, offsets, bytes);  // (this call synchronises the stream before it returns)
         void* stage_dev = nullptr;  // the device's address of the page-locked block: the first kernel reads it in place
         HIPCHK(ctx, hipHostGetDevicePointer(&stage_dev, ctx->param_stage, 0));
-        launch_adjust_tile_counts(ctx->stream, (const int64_t*)stage_dev, d_offs, (int)n_iv, W, tile, fast ? kAdjustFastTile : 0,
-                                  d_pre0, d_pre1, d_todo);
+        chain.counts(ctx->stream, (const int64_t*)stage_dev, n_iv);
     }
     int64_t n_tiles = 0, n_fast = 0;
     for (int64_t i = 0; i < n_iv; ++i) {
@@ -658,16 +695,12 @@ int ftk_wps_adjust(ftk_ctx* ctx, const double* scores, const int64_t* offsets, i
             return fail(ctx, FTK_ERR_INVALID, "run %lld: savgol_window (%d) exceeds the filtered length (%lld)",
                         (long long)i, sw, (long long)m);
         }
-        n_tiles += (m + tile - 1) / tile;
-        if (fast) n_fast += (m + kAdjustFastTile - 1) / kAdjustFastTile;
+        chain.count(len, &n_tiles, &n_fast);
     }
     if (n_tiles == 0) {
         HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
         return FTK_OK;
     }
-    if (!n_fast) { d_fast = nullptr; d_todo = nullptr; }
-    launch_adjust_tile_fill(ctx->stream, d_offs, (int)n_iv, W, tile, n_fast ? kAdjustFastTile : 0, d_pre0, d_pre1, d_tiles,
-                            (int)n_tiles, d_fast, (int)n_fast);
     const double* d_in = scores;
     if (!in_dev) {
         HIPCHK(ctx, hipMemcpyAsync(d_staged, scores, total_in * 8, hipMemcpyHostToDevice, ctx->stream));
@@ -680,9 +713,7 @@ int ftk_wps_adjust(ftk_ctx* ctx, const double* scores, const int64_t* offsets, i
             HIPCHK(ctx, hipMemcpyAsync(d_edge, savgol_edge, (size_t)2 * half * sw * 8, hipMemcpyHostToDevice,
                                        ctx->stream));
     }
-    launch_adjust_filter(ctx->stream, d_in, d_tiles, (int)n_tiles, d_sub, W, use_mean, d_adj, d_fast, (int)n_fast, d_todo,
-                         (int)n_iv);
-    if (sw) launch_savgol(ctx->stream, d_adj, d_tiles, (int)n_tiles, d_coef, d_edge, sw, d_out);
+    chain.run(ctx->stream, n_iv, n_tiles, n_fast, d_in, d_sub, use_mean, d_adj, sw, d_coef, d_edge, d_out);
     HIPCHK(ctx, hipGetLastError());
     return s.finish(/*must_sync=*/true);  // (the coefficient arrays are pageable staging)
 }

@@ -957,6 +957,73 @@ class Engine:
             0 if batch_bases is None else int(batch_bases), L.ptr(res), L.ptr(ssw)))
         return res, ssw
 
+    # -- nucleosome calls from adjusted score runs (csrc/ftk_peaks.hip) ----------------------
+    PEAK_DTYPE = np.dtype([("run", np.int32), ("start", np.int64), ("stop", np.int64), ("summit", np.int64),
+                           ("height", np.float64), ("area", np.float64)])
+
+    def _peaks_call(self, fn, n_runs, *args):
+        """Calls ``fn(ctx, *args, outputs...)`` of the peaks pair and takes the library's blocks home:
+        ``(calls, stats)`` - a ``PEAK_DTYPE`` record array ordered by ``(run, start)`` and the int64 counters
+        ``[n_runs, 6]`` (regions, open, short, long, flat, calls)."""
+        ptrs = [C.c_void_p() for _ in self.PEAK_DTYPE.names]
+        n = C.c_int64()
+        stats = np.zeros((n_runs, 6), np.int64)
+        keep = np.empty(1, np.int64)
+        try:
+            self._check(fn(self.ctx, *args, *[C.byref(p) for p in ptrs], C.byref(n), L.ptr(stats if n_runs else keep)))
+            calls = np.zeros(n.value, self.PEAK_DTYPE)
+            for name, p in zip(self.PEAK_DTYPE.names, ptrs):
+                dt = self.PEAK_DTYPE[name]
+                if n.value:  # (one copy: out of the library's block into the records)
+                    calls[name] = np.frombuffer((C.c_char * (n.value * dt.itemsize)).from_address(p.value), dt)
+        finally:
+            for p in ptrs:
+                if p.value:
+                    self.lib.ftk_buffer_free(p.value)
+        return calls, stats
+
+    def track_peaks(self, scores, offsets, skip=0, max_gap=5, min_region=50, short_max=150, max_region=450):
+        """``(calls, stats)``: nucleosome calls of the float64 score runs ``scores[offsets[i]:offsets[i+1]]``
+        (``ftk_track_peaks``; the rule is in ``include/ftk.h``, "peaks"): regions of positive scores joined over gaps of
+        at most ``max_gap`` inside ``[skip, n - skip)``, the windows above the region's median, the window of largest
+        area for a region of up to ``short_max`` positions and every window of ``min_region .. short_max`` positions for
+        a longer one (up to ``max_region``).  ``calls``: a record array (``Engine.PEAK_DTYPE``: run, start, stop, summit,
+        height, area; positions count from the run's start) ordered by ``(run, start)``; ``stats``: int64 ``[n_runs, 6]``
+        (regions, open, short, long, flat, calls).  ``scores``: a host array, a device tensor or a device address."""
+        offs = np.ascontiguousarray(offsets, dtype=np.int64)
+        n_runs = max(len(offs) - 1, 0)
+        if not (isinstance(scores, (int, np.integer)) or hasattr(scores, "data_ptr")):
+            scores = np.ascontiguousarray(scores, dtype=np.float64)
+        keep = np.empty(1, np.int64)
+        return self._peaks_call(
+            self.lib.ftk_track_peaks, n_runs, L.ptr(int(scores) if isinstance(scores, np.integer) else scores),
+            L.ptr(offs if len(offs) else keep), n_runs, int(skip), int(max_gap), int(min_region), int(short_max), int(max_region))
+
+    def wps_peaks(self, name: str, starts, stops, chrom_size: int, window_size=120, min_length=120, max_length=180,
+                  quality_threshold=30, median_window_size=1000, savgol_window_size=21, savgol_poly_deg=2, savgol=True,
+                  max_gap=5, min_region=50, short_max=150, max_region=450, batch_bases=None):
+        """``track_peaks`` of the adjusted WPS of the intervals ``[starts[i], stops[i])`` of resident contig ``name``
+        (``ftk_wps_peaks``): the scores of ``wps_intervals``, the running median and Savitzky-Golay pass of
+        ``wps_adjust`` and the calls, in device scratch, ``batch_bases`` bases of intervals at a time (``None``: the
+        library's choice) - no per-base value reaches the host.  ``skip`` is ``savgol_window_size // 2`` (0 without
+        ``savgol``).  A call's ``run`` is its interval's number and its positions are contig positions.  An interval
+        shorter than ``median_window_size + max(savgol_window_size, 1)`` has no callable track: no call, zero counters.
+        The same calls as ``track_peaks(wps_adjust(*wps_intervals(...)), ...)`` with positions moved to the contig."""
+        s = np.ascontiguousarray(starts, dtype=np.int64)
+        e = np.ascontiguousarray(stops, dtype=np.int64)
+        if s.shape != e.shape:
+            raise ValueError("starts and stops differ in length")
+        sw = int(savgol_window_size) if savgol else 0
+        coef = edge = None
+        if sw:
+            coef, edge = savgol_operators(sw, int(savgol_poly_deg))
+        keep = np.empty(1, np.int64)
+        return self._peaks_call(
+            self.lib.ftk_wps_peaks, len(s), self.contig_id(name), L.ptr(s if len(s) else keep), L.ptr(e if len(s) else keep), len(s),
+            int(chrom_size), int(window_size), int(min_length), int(max_length), int(quality_threshold),
+            int(median_window_size), sw, L.ptr(coef), L.ptr(edge), int(max_gap), int(min_region), int(short_max),
+            int(max_region), 0 if batch_bases is None else int(batch_bases))
+
     # -- WPS post-processing --------------------------------------------------------
     def wps_adjust(self, scores, offsets, median_window_size=1000, mean=False, edge_sub=None, savgol_window_size=21,
                    savgol_poly_deg=2, savgol=True, out=None):

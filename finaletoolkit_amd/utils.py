@@ -17,7 +17,7 @@ from .exceptions import InvalidInputError
 from .source import get_engine, open_source
 
 __all__ = ["chrom_sizes_to_list", "chrom_sizes_to_dict", "get_intervals", "overlaps", "frags_in_region", "frag_generator",
-           "frag_array", "frag_export", "frag_filter", "frag_gc_coverage", "frag_site_profile", "frag_vplot", "VPlot", "frag_ocf", "OCF", "frag_wps_spectrum", "WpsSpectrum", "read_sites", "gc_weights", "read_gc_bias_table", "read_region_mask", "agg_bw", "gen_kmers", "reverse_complement", "validate_compatible_contigs", "valid_interval",
+           "frag_array", "frag_export", "frag_filter", "frag_gc_coverage", "frag_site_profile", "frag_vplot", "VPlot", "frag_ocf", "OCF", "frag_wps_spectrum", "WpsSpectrum", "frag_wps_peaks", "WpsPeaks", "read_sites", "gc_weights", "read_gc_bias_table", "read_region_mask", "agg_bw", "gen_kmers", "reverse_complement", "validate_compatible_contigs", "valid_interval",
            "_none_eq", "_none_geq", "_none_leq"]
 
 FragTuple = Tuple[str, int, int, int, bool]
@@ -1192,6 +1192,161 @@ def frag_wps_spectrum(input_file, interval_file, chrom_sizes=None, output_file=N
         writers.write_wps_spectrum_rows(os.fspath(output_file), res)
     if verbose:
         sys.stderr.write(f"frag_wps_spectrum: {len(intervals)} intervals in {time.time() - t0:.3f} s\n")
+    return res
+
+
+class WpsPeaks(NamedTuple):
+    """Result of ``frag_wps_peaks``, one row of ``stats`` / ``callable`` / ``median_spacing`` per interval (of the interval
+    file, in its order; whole-contig mode: per contig of the input, in the order the contigs were met)."""
+    intervals: list             # (contig, start, stop, name)
+    calls: np.ndarray           # WPS_PEAK_DTYPE records ordered by (interval, start); contig positions
+    stats: np.ndarray           # int64 (n_intervals, 6): regions, open, short, long, flat, calls
+    callable: np.ndarray        # int64 per interval: positions of its callable track
+    median_spacing: np.ndarray  # float64 per interval: median distance between consecutive call centres; nan below two calls
+
+
+WPS_PEAK_DTYPE = np.dtype([("interval", np.int64), ("start", np.int64), ("stop", np.int64), ("summit", np.int64),
+                           ("height", np.float64), ("area", np.float64)])
+PEAKS_MAX_GAP = 63                # FTK_PEAKS_MAX_GAP
+PEAKS_MAX_REGION = 1024           # FTK_PEAKS_MAX_REGION
+PEAKS_MAX_MEDIAN_WINDOW = 2048    # the running median of ``ftk_wps_adjust``
+
+
+def _check_wps_peaks_args(input_file, chrom_sizes, output_file, summary_file, median_window_size, savgol_window_size,
+                          savgol_poly_deg, savgol, max_gap, min_region, short_max, max_region, chunk_size):
+    if output_file is not None and not str(output_file).endswith((".bed", ".bed.gz")):
+        raise ValueError("output_file should have .bed or .bed.gz as suffix")
+    if summary_file is not None and not str(summary_file).endswith((".tsv", ".tsv.gz")):
+        raise ValueError("summary_file should have .tsv or .tsv.gz as suffix")
+    W = int(median_window_size)
+    if W < 2 or W % 2 or W > PEAKS_MAX_MEDIAN_WINDOW:
+        raise ValueError(f"invalid median_window_size ({W}): an even number in [2, {PEAKS_MAX_MEDIAN_WINDOW}]")
+    if savgol:
+        sw, deg = int(savgol_window_size), int(savgol_poly_deg)
+        if sw < 3 or sw % 2 == 0:
+            raise ValueError(f"invalid savgol_window_size ({sw}): an odd number, 3 at least")
+        if not 0 <= deg < sw:
+            raise ValueError(f"invalid savgol_poly_deg ({deg}): it should be below savgol_window_size ({sw})")
+    if not 0 <= int(max_gap) <= PEAKS_MAX_GAP:
+        raise ValueError(f"invalid max_gap ({max_gap}): 0 .. {PEAKS_MAX_GAP}")
+    if not 1 <= int(min_region) <= int(short_max) <= int(max_region) <= PEAKS_MAX_REGION:
+        raise ValueError(f"invalid region lengths ({min_region}, {short_max}, {max_region}): 1 <= min_region <= short_max <= "
+                         f"max_region <= {PEAKS_MAX_REGION}")
+    if int(chunk_size) < 1:
+        raise ValueError(f"invalid chunk_size ({chunk_size}): at least 1")
+    if chrom_sizes is None and not _is_alignment_file(input_file):
+        raise ValueError("chrom_sizes must be specified for BED/Fragment files")
+
+
+def _median_spacing(starts, stops) -> float:
+    centres = starts + (stops - starts) // 2
+    return float(np.median(np.diff(centres))) if len(centres) >= 2 else float("nan")
+
+
+def frag_wps_peaks(input_file, interval_file=None, chrom_sizes=None, output_file=None, summary_file=None, window_size: int = 120,
+                   min_length: int = 120, max_length: int = 180, quality_threshold: int = 30, median_window_size: int = 1000,
+                   savgol_window_size: int = 21, savgol_poly_deg: int = 2, savgol: bool = True, max_gap: int = 5,
+                   min_region: int = 50, short_max: int = 150, max_region: int = 450, chunk_size: int = 1 << 20, workers=None,
+                   verbose=False) -> WpsPeaks:
+    """Nucleosome calls from the adjusted windowed protection score (Snyder et al. 2016): per interval of
+    ``interval_file`` (BED), or over every contig of the input when there is none, the WPS of ``frag.wps`` is adjusted as
+    ``frag.adjust_wps`` does (running median over ``median_window_size``, Savitzky-Golay with ``savgol_window_size`` /
+    ``savgol_poly_deg`` unless ``savgol`` is off) and called by the rule of ``include/ftk.h``, "peaks": regions of positive
+    adjusted score joined over gaps of up to ``max_gap``, their windows above the region's median, the window of largest
+    area in a region of up to ``short_max`` positions and every window of ``min_region .. short_max`` positions in a
+    longer one (up to ``max_region``).  All of it runs on the GPU, contig by contig as the input is decoded
+    (``Engine.wps_peaks``): only the calls come back to the host.
+
+    An interval's callable track is what the adjustment leaves of it - ``median_window_size / 2 + savgol_window_size // 2``
+    positions less at either end; an interval too short for one has no call.  Whole-contig mode cuts a contig into
+    chunks of ``chunk_size`` positions, each widened by ``median_window_size / 2 + savgol_window_size // 2 + max_region +
+    max_gap + 1`` on both sides, and keeps a call with the chunk that holds its ``start``: the calls do not depend on
+    ``chunk_size``.  (The counters other than ``calls`` are summed over the chunks there: a region inside an overlap
+    counts in both.)
+
+    Chromosome sizes: the BAM header, else the ``chrom_sizes`` file, else ``ValueError``.  An interval on a contig the
+    input lacks raises ``ValueError``, as in ``frag.coverage``.  ``output_file`` (``.bed`` / ``.bed.gz``):
+    ``writers.write_wps_peaks_rows``; ``summary_file`` (``.tsv`` / ``.tsv.gz``): ``writers.write_wps_peaks_summary``."""
+    import os
+    import sys
+    import time
+
+    from . import writers
+    from .source import ContigFeed
+    _check_wps_peaks_args(input_file, chrom_sizes, output_file, summary_file, median_window_size, savgol_window_size,
+                          savgol_poly_deg, savgol, max_gap, min_region, short_max, max_region, chunk_size)
+    t0 = time.time()
+    W, sw = int(median_window_size), int(savgol_window_size) if savgol else 0
+    skip, chunk = sw // 2, int(chunk_size)
+    pad = W // 2 + skip + int(max_region) + int(max_gap) + 1
+    sizes = None if _is_alignment_file(input_file) else chrom_sizes_to_dict(chrom_sizes)
+    whole = interval_file is None
+    intervals = [] if whole else get_intervals(interval_file)
+    by_contig: dict[str, list[int]] = {}
+    for i, iv in enumerate(intervals):
+        by_contig.setdefault(iv[0], []).append(i)
+    if sizes is not None:
+        for c in by_contig:
+            if c not in sizes:
+                raise ValueError(f"{c} is not in chrom_sizes")
+    args = dict(window_size=window_size, min_length=min_length, max_length=max_length, quality_threshold=quality_threshold,
+                median_window_size=W, savgol_window_size=savgol_window_size, savgol_poly_deg=savgol_poly_deg, savgol=bool(savgol),
+                max_gap=max_gap, min_region=min_region, short_max=short_max, max_region=max_region)
+    parts, stat_rows = [], {}
+    left = dict(by_contig)
+    eng = get_engine()
+    feed = ContigFeed(input_file, workers, names=None if whole else list(by_contig))
+    try:
+        for src, c in feed:
+            if whole:
+                if sizes is not None and c not in sizes:
+                    raise ValueError(f"{c} is not in chrom_sizes")
+                size = int(src.lengths[c]) if sizes is None else int(sizes[c])
+                idx = [len(intervals)]
+                intervals.append((c, 0, size, "."))
+                core = np.arange(0, max(size, 1), chunk, dtype=np.int64)
+                core_end = np.minimum(core + chunk, size)
+                calls, stats = eng.wps_peaks(src.key(c), np.maximum(core - pad, 0), np.minimum(core_end + pad, size), size, **args)
+                calls = calls[(calls["start"] >= core[calls["run"]]) & (calls["start"] < core_end[calls["run"]])]
+                which = np.full(len(calls), idx[0], np.int64)
+                stat_rows[idx[0]] = stats.sum(axis=0)
+                stat_rows[idx[0]][5] = len(calls)
+            else:
+                idx = left.pop(c, None)
+                if idx is None:
+                    continue
+                size = int(src.lengths[c]) if sizes is None else int(sizes[c])
+                calls, stats = eng.wps_peaks(src.key(c), [intervals[i][1] for i in idx], [intervals[i][2] for i in idx], size, **args)
+                which = np.asarray(idx, np.int64)[calls["run"]]
+                stat_rows.update(zip(idx, stats))
+            part = np.zeros(len(calls), WPS_PEAK_DTYPE)
+            part["interval"] = which
+            for name in WPS_PEAK_DTYPE.names[1:]:
+                part[name] = calls[name]
+            parts.append(part)
+            if verbose:
+                sys.stderr.write(f"frag_wps_peaks: {c}: {len(idx)} intervals, {len(part)} calls\n")
+        src = feed.finish()
+    except BaseException:
+        feed.close()
+        raise
+    for c in left:  # contigs the file does not hold: the ValueError of frag.coverage
+        src.require(c)
+    calls = np.concatenate(parts) if parts else np.zeros(0, WPS_PEAK_DTYPE)
+    calls = calls[np.argsort(calls["interval"], kind="stable")]  # (an interval's calls are in start order already)
+    n = len(intervals)
+    stats = np.array([stat_rows[i] for i in range(n)], np.int64).reshape(n, 6)
+    lens = np.array([max(iv[2] - iv[1], 0) for iv in intervals], np.int64)
+    callable_ = np.where(lens >= W + max(sw, 1), lens - W - 2 * skip, 0)
+    bounds = np.searchsorted(calls["interval"], np.arange(n + 1))
+    spacing = np.array([_median_spacing(calls["start"][a:b], calls["stop"][a:b]) for a, b in zip(bounds[:-1], bounds[1:])], np.float64)
+    res = WpsPeaks(intervals, calls, stats, callable_, spacing)
+    if output_file is not None:
+        writers.write_wps_peaks_rows(os.fspath(output_file), res)
+    if summary_file is not None:
+        writers.write_wps_peaks_summary(os.fspath(summary_file), res)
+    if verbose:
+        sys.stderr.write(f"frag_wps_peaks: {n} intervals, {len(calls)} calls in {time.time() - t0:.3f} s\n")
     return res
 
 

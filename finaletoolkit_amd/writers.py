@@ -382,3 +382,33 @@ def write_wps_spectrum_rows(output_file: str, spectrum) -> None:
     for (c, a, b, name), n, mean, row in zip(spectrum.intervals, spectrum.n_bases, spectrum.band_mean, spectrum.power):
         rows.append("\t".join([str(c), str(a), str(b), str(name), str(int(n)), num(mean)] + [num(x) for x in row]) + "\n")
     _emit(output_file, "".join(rows), (".tsv",), (".tsv.gz",), message)
+
+
+def write_wps_peaks_rows(output_file: str, peaks) -> None:
+    """One row per call of a ``utils.WpsPeaks``, ordered by interval and start, without a header line: ``contig start stop
+    name centre summit height area`` - ``[start, stop)`` the call's window, ``name`` its interval's name (``.`` in
+    whole-contig mode), ``centre = start + (stop - start) // 2``, the floats with six significant digits; ``.bed`` as text,
+    ``.bed.gz`` as gzip."""
+    message = "output_file should have .bed or .bed.gz as suffix"
+    if not output_file.endswith((".bed", ".bed.gz")):
+        raise ValueError(message)
+    rows = []
+    for i, a, b, summit, height, area in peaks.calls.tolist():
+        c, _, _, name = peaks.intervals[i]
+        rows.append(f"{c}\t{a}\t{b}\t{name}\t{a + (b - a) // 2}\t{summit}\t{format(height, '.6g')}\t{format(area, '.6g')}\n")
+    _emit(output_file, "".join(rows), (".bed",), (".bed.gz",), message)
+
+
+def write_wps_peaks_summary(output_file: str, peaks) -> None:
+    """One row per interval of a ``utils.WpsPeaks``, in its order, behind the header line ``contig start stop name callable
+    regions open short long flat calls median_spacing``: the interval, the positions of its callable track, the six
+    counters of the rule and the median distance between consecutive call centres (six significant digits, ``nan`` below
+    two calls); ``.tsv`` as text, ``.tsv.gz`` as gzip."""
+    message = "summary_file should have .tsv or .tsv.gz as suffix"
+    if not output_file.endswith((".tsv", ".tsv.gz")):
+        raise ValueError(message)
+    rows = ["contig\tstart\tstop\tname\tcallable\tregions\topen\tshort\tlong\tflat\tcalls\tmedian_spacing\n"]
+    for (c, a, b, name), n, stats, gap in zip(peaks.intervals, peaks.callable, peaks.stats, peaks.median_spacing):
+        rows.append("\t".join([str(c), str(a), str(b), str(name), str(int(n))] + [str(int(x)) for x in stats]
+                              + ["nan" if gap != gap else format(float(gap), ".6g")]) + "\n")
+    _emit(output_file, "".join(rows), (".tsv",), (".tsv.gz",), message)

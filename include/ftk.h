@@ -857,6 +857,67 @@ int ftk_wps_spectrum(ftk_ctx* ctx, int contig_id, const int64_t* iv_start, const
                      const int32_t* periods, int32_t n_per, double taper, int detrend, int64_t batch_bases, double* out,
                      double* ssw_out);
 
+/* ---- peaks: nucleosome calls from the adjusted WPS -----------------------------------------------------
+ * The step the per-base WPS, its adjustment (ftk_wps_adjust) and its periodogram lead up to in Snyder et al. 2016: the
+ * positions of nucleosomes, called on the device so that no per-base value crosses to the host.  A call set is small,
+ * about one record per 190 bases.
+ *
+ * THE RULE.  The input is a run a[0..n) of finite float64 adjusted scores.  Parameters: skip >= 0, 0 <= max_gap <=
+ * FTK_PEAKS_MAX_GAP, 1 <= min_region <= short_max <= max_region <= FTK_PEAKS_MAX_REGION.
+ *  1. Callable track: [lo, hi) = [skip, n - skip), empty when hi <= lo.  (The fused call takes skip = savgol_window / 2,
+ *     the points of the polynomial edge fit, and 0 without Savitzky-Golay.)
+ *  2. Regions: take the positions of the track with a > 0.  Two neighbouring positive positions belong to one region
+ *     when at most max_gap positions lie between them.  A region [r0, r1) begins and ends on a positive position.
+ *  3. Open regions: r0 - lo <= max_gap or hi - r1 <= max_gap - positions outside the track could still join it.  Not called.
+ *  4. Length L = r1 - r0.  L < min_region: short, not called.  L > max_region: long, not called.
+ *  5. Median m of the L values of the region, the gap values included: the middle element of the sorted values for odd
+ *     L, (s[L/2 - 1] + s[L/2]) / 2 in float64 for even L.
+ *  6. Windows: the maximal runs of positions of the region with a > m, strictly.  None (all values equal): the region
+ *     is flat, not called.
+ *  7. A window's area: the sum of its values in float64, added to 0 left to right, one addition per value, never reassociated.
+ *  8. L <= short_max: the one window of largest area, the leftmost of equals, whatever its own length.
+ *     L >  short_max: every window whose length lies in [min_region, short_max].
+ *  9. A call is (run, start, stop, summit, height, area): [start, stop) the window, summit the leftmost position of the
+ *     window's largest value, height that value.  Calls come ordered by (run, start).
+ * 10. Per run six int64 counters, in this order: regions, open, short, long, flat, calls.
+ * A closed region and its calls depend on the scores within max_gap + 1 positions of it alone, and a run of n scores
+ * yields at most n / (max_gap + 2) + 1 regions and n / (min_region + 1) + 1 calls: the room for both is reserved from the
+ * lengths, nothing waits for the device between the passes, and a call is the same bits in every call that asks for it.
+ *
+ * ftk_track_peaks: run r is scores[offsets[r], offsets[r+1]) (scores: host or device; offsets: host, n_runs + 1 entries,
+ * non-negative and non-decreasing).  start / stop / summit count from the run's first score.  The six columns come back
+ * in host blocks of the library's, *n_calls entries each (NULL when there is no call), to be released with
+ * ftk_buffer_free; stats: n_runs * 6 counters of the caller's (host or device).
+ * ftk_wps_peaks: the runs are the adjusted WPS of the intervals [iv_start[i], iv_stop[i]) of a resident contig - the
+ * scores of the interval form of the WPS call, converted to float64, put through ftk_wps_adjust's running median
+ * (median_window) and Savitzky-Golay pass (savgol_window with its coef / edge arrays; 0: none) and called with skip =
+ * savgol_window / 2, all in device scratch, in consecutive batches of at most batch_bases bases (0: the library's
+ * choice, 2^25; an interval longer than that is a batch of its own).  run is the interval's number; start / stop /
+ * summit are contig positions (interval start + median_window / 2 + position in the adjusted run).  An interval shorter
+ * than median_window + max(savgol_window, 1) has no callable track: no call, zero counters, no error.  stats: n_iv * 6
+ * counters in host memory.  The same calls as the three calls in a row, without a per-base value reaching the host.
+ * FTK_ERR_INVALID: a NULL argument, device pointers for offsets / the interval, savgol and (fused call) stats arrays,
+ * decreasing offsets, a parameter outside the ranges above, the median / savgol window rules of ftk_wps_adjust, a
+ * negative batch_bases, a score that is not finite (found on the device: the call fails after the passes have run).
+ * A failing call hands out no block.  n_runs == 0 / n_iv == 0 is valid. */
+#define FTK_PEAKS_MAX_REGION 1024
+#define FTK_PEAKS_MAX_GAP 63
+#define FTK_PEAKS_REGIONS 0
+#define FTK_PEAKS_OPEN 1
+#define FTK_PEAKS_SHORT 2
+#define FTK_PEAKS_LONG 3
+#define FTK_PEAKS_FLAT 4
+#define FTK_PEAKS_CALLS 5
+int ftk_track_peaks(ftk_ctx* ctx, const double* scores, const int64_t* offsets, int64_t n_runs, int64_t skip, int32_t max_gap,
+                    int32_t min_region, int32_t short_max, int32_t max_region, int32_t** run, int64_t** start, int64_t** stop,
+                    int64_t** summit, double** height, double** area, int64_t* n_calls, int64_t* stats);
+int ftk_wps_peaks(ftk_ctx* ctx, int contig_id, const int64_t* iv_start, const int64_t* iv_stop, int64_t n_iv,
+                  int64_t chrom_size, int32_t window_size, int32_t min_len, int32_t max_len, int32_t mapq_min,
+                  int32_t median_window, int32_t savgol_window, const double* savgol_coef, const double* savgol_edge,
+                  int32_t max_gap, int32_t min_region, int32_t short_max, int32_t max_region, int64_t batch_bases,
+                  int32_t** run, int64_t** start, int64_t** stop, int64_t** summit, double** height, double** area,
+                  int64_t* n_calls, int64_t* stats);
+
 /* ---- multi-GPU (SURVEY 8-e, 8-b's export list) -------------------------------------------------
  * One process and one ftk_ctx per GPU.  Contigs / genome runs are dealt to the ranks by the host and every window,
  * bin and base depends on its own contig's fragments only, so the data path has no collective.  What remains are the

@@ -9,7 +9,9 @@ KBENCH=vplot: the length x offset map of the same sites (lengths 100-399 in 60 r
 KBENCH=siteends: the U / D end profiles and per-site OCF window sums of the same sites beside ftk_site_profile, both LDS arrangements
 of the widest weighted profile, and the route there was before (the columns to host memory + the rule in numpy).
 KBENCH=spectrum: the WPS periodogram of 2 000 regions x 10 000 bases at periods 120-280 - the transform alone, the fused call, and
-the route there was before (ftk_wps_intervals to host memory + a numpy matrix product on the host threads)."""
+the route there was before (ftk_wps_intervals to host memory + a numpy matrix product on the host threads).
+KBENCH=peaks: nucleosome calls on the same regions - the two peak passes alone on a resident adjusted track, ftk_wps_adjust on the
+same runs, the fused call, and the route there was before (scores and adjusted track carried through host memory)."""
 import os
 import sys
 
@@ -508,6 +510,71 @@ if "spectrum" in which:
     print("spectrum checksum: fused vs host route, largest difference over the largest value",
           float(np.abs(got - want).max()) / scale, "fused == transform bits",
           bool(np.array_equal(got.view(np.float64).reshape(NR, len(periods), 2), d_spec.cpu().numpy())))
+if "peaks" in which:
+    # Nucleosome calls: the spectrum mode's regions (KBENCH_PEAKS_REGIONS x KBENCH_PEAKS_BASES, 2 000 x 10 000), median window
+    # 1000, savgol(21, 2), the default rule.  Four times, wall clock around the whole call: (a) the two peak passes alone on
+    # an adjusted track that is on the device (the calls come home: some tens of bytes each); (b) ftk_wps_adjust on the
+    # same runs, device to device; (c) the fused call; (d) the route there was before - ftk_wps_intervals to host memory,
+    # float64 on the host, ftk_wps_adjust host to host, ftk_track_peaks from the host.  The passes' floor: the track is
+    # read about twice (mark, then the regions), 8 bytes a base, at the HBM rate.
+    import time
+    rng = np.random.default_rng(193)
+    NR, NB = int(os.environ.get("KBENCH_PEAKS_REGIONS", "2000")), int(os.environ.get("KBENCH_PEAKS_BASES", "10000"))
+    W, SW = 1000, 21
+    r_start = np.sort(rng.integers(0, size - NB, NR)).astype(np.int64)
+    r_stop = r_start + NB
+    scores, offs = eng.wps_intervals("c", r_start, r_stop, size)
+    raw = np.asarray(scores, np.float64)
+    adj_offs = offs - np.arange(NR + 1) * W
+    n_adj = int(adj_offs[-1])
+    d_raw = torch.from_numpy(raw).to(dev)
+    d_adj = torch.zeros(n_adj, dtype=torch.float64, device=dev)
+    torch.cuda.synchronize()
+
+    def adjust():
+        eng.wps_adjust(d_raw.data_ptr(), offs, W, savgol_window_size=SW, out=d_adj.data_ptr())
+
+    def passes():
+        return eng.track_peaks(d_adj, adj_offs, skip=SW // 2)
+
+    def fused():
+        return eng.wps_peaks("c", r_start, r_stop, size, median_window_size=W, savgol_window_size=SW)
+
+    def two_step():
+        sc, o = eng.wps_intervals("c", r_start, r_stop, size)
+        return eng.track_peaks(eng.wps_adjust(np.asarray(sc, np.float64), o, W, savgol_window_size=SW), adj_offs, skip=SW // 2)
+
+    def wall(fn, name):
+        fn()
+        torch.cuda.synchronize()
+        ts = []
+        for _ in range(max(reps // 4, 3)):
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            ts.append(time.perf_counter() - t0)
+        ts = np.array(ts)
+        print(f"{name:34s} median {np.median(ts) * 1e3:9.3f} ms  min {ts.min() * 1e3:9.3f} ms", flush=True)
+        return float(np.median(ts))
+
+    adjust()
+    torch.cuda.synchronize()
+    print(f"peaks: {n} fragments, {NR} regions x {NB} bases, {n_adj} adjusted scores", flush=True)
+    for _ in range(2):  # twice: the spread between the two passes is the noise
+        t_pk = wall(passes, "peaks, the two passes alone")
+        t_ad = wall(adjust, "ftk_wps_adjust, device to device")
+        t_fu = wall(fused, "peaks, fused call")
+        t_2s = wall(two_step, "intervals + adjust + peaks by host")
+        floor = 2 * 8 * n_adj / (bench.HBM_PEAK_GBS * 1e9)
+        print(f"  passes: {floor / t_pk:.1%} of their HBM floor ({floor * 1e3:.3f} ms), {t_pk / t_ad:.2f} x ftk_wps_adjust;  "
+              f"two-step route / fused call: {t_2s / t_fu:.2f} x", flush=True)
+    (c_f, s_f), (c_2, s_2), (c_p, s_p) = fused(), two_step(), passes()
+    for c in (c_2, c_p):  # a track's positions count from its run's start: to the contig, as the fused call's do
+        for name in ("start", "stop", "summit"):
+            c[name] += r_start[c["run"]] + W // 2
+    print("peaks checksum: calls", len(c_f), "counters", s_f.sum(axis=0).tolist(), "fused == two-step bits",
+          bool(c_f.tobytes() == c_2.tobytes() and np.array_equal(s_f, s_2)), "fused == passes bits",
+          bool(c_f.tobytes() == c_p.tobytes() and np.array_equal(s_f, s_p)))
 if "gc" in which:
     rng = np.random.default_rng(6)
     packed = rng.integers(0, 256, (size + 3) // 4, dtype=np.uint8)
