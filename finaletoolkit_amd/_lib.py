@@ -35,6 +35,10 @@ WEIGHT_ONE = 65536  # FTK_WEIGHT_ONE
 PEAKS_MAX_REGION = 1024  # FTK_PEAKS_MAX_REGION
 PEAKS_MAX_GAP = 63  # FTK_PEAKS_MAX_GAP
 PEAKS_TILE = 1024  # kPeaksTile: positions per workgroup of the mark pass
+PREFENDS_MAX_HALF = 2048  # FTK_PREFENDS_MAX_HALF
+PREFENDS_MAX_THR = 4096  # FTK_PREFENDS_MAX_THR
+PREFENDS_TILE = 4096  # kPrefTile: positions per workgroup of the preferred-end passes
+PREFENDS_BATCH_TILES = 4096  # kPrefBatchTiles: tiles the call plans, counts and writes at a time
 SPECTRUM_TILE = 16 << 10  # kSpectrumLdsSamples: a run of up to this many samples is folded out of LDS, a longer one from memory
 POLICY = {"midpoint": 0, "any": 1}
 POLICY_FETCH = 2  # no intersect test: the index query alone (AlignmentWrapper.fetch)
@@ -73,6 +77,7 @@ EXPORTS = [
     "ftk_site_ends",
     "ftk_track_spectrum", "ftk_wps_spectrum",
     "ftk_track_peaks", "ftk_wps_peaks",
+    "ftk_preferred_ends",
 ]
 
 
@@ -354,6 +359,8 @@ def load() -> C.CDLL:
     peaks_out = [C.POINTER(vp)] * 6 + [C.POINTER(i64), vp]  # run, start, stop, summit, height, area, n_calls, stats
     lib.ftk_track_peaks.argtypes = [vp, vp, vp, i64, i64, i32, i32, i32, i32] + peaks_out
     lib.ftk_wps_peaks.argtypes = [vp, C.c_int, vp, vp, i64, i64, i32, i32, i32, i32, i32, i32, vp, vp, i32, i32, i32, i32, i64] + peaks_out
+    # run, pos, kind, count, total, n_w, n_calls, stats
+    lib.ftk_preferred_ends.argtypes = [vp, C.c_int, vp, vp, i64, i64, i32, i32, i32, vp, i32, i32, i32, i32] + [C.POINTER(vp)] * 6 + [C.POINTER(i64), vp]
     lib.ftk_comm_unique_id.argtypes = [C.c_char_p]
     lib.ftk_comm_create.argtypes = [vp, C.c_int, C.c_int, C.c_char_p, C.POINTER(vp)]
     lib.ftk_comm_size.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]

@@ -1275,3 +1275,4 @@ static int wps_params(ftk_ctx* ctx, const ContigData& c, int64_t chrom_size, int
 #include "ftk_api_siteends.inc"
 #include "ftk_api_spectrum.inc"
 #include "ftk_api_peaks.inc"
+#include "ftk_api_prefends.inc"

@@ -264,6 +264,13 @@ class Engine:
         self._check(self.lib.ftk_frags_info(self.ctx, self.contig_id(name), C.byref(n), C.byref(ml), C.byref(me)))
         return int(n.value), int(ml.value), int(me.value)
 
+    def frags_packed(self, name: str) -> bool:
+        """Does the resident contig hold the packed (length, mapq) column (``ftk_frags_packed``)?  Calls whose filter
+        allows it read that column instead of ``end`` and ``mapq``."""
+        present = C.c_int32()
+        self._check(self.lib.ftk_frags_packed(self.ctx, self.contig_id(name), C.byref(present), None, None))
+        return bool(present.value)
+
     def release(self, name: str):
         self._check(self.lib.ftk_frags_release(self.ctx, self._ids.pop(name)))
         self._bam.pop(name, None)
@@ -1023,6 +1030,55 @@ class Engine:
             int(chrom_size), int(window_size), int(min_length), int(max_length), int(quality_threshold),
             int(median_window_size), sw, L.ptr(coef), L.ptr(edge), int(max_gap), int(min_region), int(short_max),
             int(max_region), 0 if batch_bases is None else int(batch_bases))
+
+    # -- preferred fragment ends (csrc/ftk_prefends.hip) ----------------------------------------
+    PREFERRED_END_DTYPE = np.dtype([("run", np.int32), ("pos", np.int64), ("kind", np.int32), ("count", np.int32),
+                                    ("total", np.int64), ("n_w", np.int32)])
+
+    def preferred_ends(self, name: str, starts, stops, chrom_size: int, half=500, mode="combined", min_count=2, thresholds=None,
+                       min_length=None, max_length=None, quality_threshold=30):
+        """``(calls, stats)``: the preferred ends of the intervals ``[starts[i], stops[i])`` of resident contig ``name``
+        (``ftk_preferred_ends``; the rule is in ``include/ftk.h``, "preferred ends"): the positions whose end count ``e``
+        is at least ``min_count`` and whose window total ``T`` over ``half`` bases on either side satisfies
+        ``T * 2**20 <= thresholds[min(e, len(thresholds) - 1)] * n_w``.  ``mode``: ``"combined"`` (U + D ends, kind 2) or
+        ``"split"`` (U ends, kind 0, and D ends, kind 1, each against its own total).  ``thresholds``: the ``uint64``
+        table (``None``: ``utils.preferred_end_thresholds()``).  ``calls``: a record array
+        (``Engine.PREFERRED_END_DTYPE``: run, pos, kind, count, total, n_w; ``run`` the interval's number, ``pos`` a
+        contig position) ordered by ``(run, pos, kind)``; ``stats``: int64 ``[n_intervals, 6]`` (U ends, D ends, tested
+        a, tested b, calls a, calls b)."""
+        s = np.ascontiguousarray(starts, dtype=np.int64)
+        e = np.ascontiguousarray(stops, dtype=np.int64)
+        if s.shape != e.shape or s.ndim != 1:
+            raise ValueError("starts and stops should be one-dimensional and equal in length")
+        if mode not in ("combined", "split"):
+            raise ValueError(f"invalid mode ({mode!r}): 'combined' or 'split'")
+        if thresholds is None:
+            from .utils import preferred_end_thresholds
+            thresholds = preferred_end_thresholds()
+        thr = np.ascontiguousarray(thresholds, dtype=np.uint64)
+        if thr.ndim != 1:
+            raise ValueError("thresholds should be one-dimensional")
+        n_iv = len(s)
+        ptrs = [C.c_void_p() for _ in self.PREFERRED_END_DTYPE.names]
+        n = C.c_int64()
+        stats = np.zeros((n_iv, 6), np.int64)
+        keep = np.empty(1, np.int64)
+        try:
+            self._check(self.lib.ftk_preferred_ends(
+                self.ctx, self.contig_id(name), L.ptr(s if n_iv else keep), L.ptr(e if n_iv else keep), n_iv, int(chrom_size),
+                int(half), int(mode == "split"), int(min_count), L.ptr(thr if len(thr) else keep), len(thr),
+                L.LEN_OPEN if min_length is None else int(min_length), L.LEN_OPEN if max_length is None else int(max_length),
+                int(quality_threshold), *[C.byref(p) for p in ptrs], C.byref(n), L.ptr(stats if n_iv else keep)))
+            calls = np.zeros(n.value, self.PREFERRED_END_DTYPE)
+            for col, p in zip(self.PREFERRED_END_DTYPE.names, ptrs):
+                dt = self.PREFERRED_END_DTYPE[col]
+                if n.value:  # (one copy: out of the library's block into the records)
+                    calls[col] = np.frombuffer((C.c_char * (n.value * dt.itemsize)).from_address(p.value), dt)
+        finally:
+            for p in ptrs:
+                if p.value:
+                    self.lib.ftk_buffer_free(p.value)
+        return calls, stats
 
     # -- WPS post-processing --------------------------------------------------------
     def wps_adjust(self, scores, offsets, median_window_size=1000, mean=False, edge_sub=None, savgol_window_size=21,

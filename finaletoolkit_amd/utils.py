@@ -17,7 +17,7 @@ from .exceptions import InvalidInputError
 from .source import get_engine, open_source
 
 __all__ = ["chrom_sizes_to_list", "chrom_sizes_to_dict", "get_intervals", "overlaps", "frags_in_region", "frag_generator",
-           "frag_array", "frag_export", "frag_filter", "frag_gc_coverage", "frag_site_profile", "frag_vplot", "VPlot", "frag_ocf", "OCF", "frag_wps_spectrum", "WpsSpectrum", "frag_wps_peaks", "WpsPeaks", "read_sites", "gc_weights", "read_gc_bias_table", "read_region_mask", "agg_bw", "gen_kmers", "reverse_complement", "validate_compatible_contigs", "valid_interval",
+           "frag_array", "frag_export", "frag_filter", "frag_gc_coverage", "frag_site_profile", "frag_vplot", "VPlot", "frag_ocf", "OCF", "frag_wps_spectrum", "WpsSpectrum", "frag_wps_peaks", "WpsPeaks", "frag_preferred_ends", "PreferredEnds", "preferred_end_thresholds", "read_sites", "gc_weights", "read_gc_bias_table", "read_region_mask", "agg_bw", "gen_kmers", "reverse_complement", "validate_compatible_contigs", "valid_interval",
            "_none_eq", "_none_geq", "_none_leq"]
 
 FragTuple = Tuple[str, int, int, int, bool]
@@ -1347,6 +1347,173 @@ def frag_wps_peaks(input_file, interval_file=None, chrom_sizes=None, output_file
         writers.write_wps_peaks_summary(os.fspath(summary_file), res)
     if verbose:
         sys.stderr.write(f"frag_wps_peaks: {n} intervals, {len(calls)} calls in {time.time() - t0:.3f} s\n")
+    return res
+
+
+class PreferredEnds(NamedTuple):
+    """Result of ``frag_preferred_ends``, one row of ``stats`` / ``share`` per interval (of the interval file, in its order;
+    whole-contig mode: per contig of the input, in the order the contigs were met)."""
+    intervals: list      # (contig, start, stop, name)
+    calls: np.ndarray    # PREFERRED_END_DTYPE records ordered by (interval, pos, kind); contig positions
+    stats: np.ndarray    # int64 (n_intervals, 6): U ends, D ends, tested a, tested b, calls a, calls b
+    share: np.ndarray    # float64 per interval: the share of its ends that lie on called positions; nan without ends
+
+
+PREFERRED_END_DTYPE = np.dtype([("interval", np.int64), ("pos", np.int64), ("kind", np.int32), ("count", np.int32),
+                                ("total", np.int64), ("n_w", np.int32)])
+PREFENDS_MAX_HALF = 2048   # FTK_PREFENDS_MAX_HALF
+PREFENDS_MAX_THR = 4096    # FTK_PREFENDS_MAX_THR
+PREFENDS_SCALE_BITS = 20   # a table entry is a mean in units of 2^-20 ends per base
+
+
+def preferred_end_thresholds(alpha: float = 0.01, n: int = 256) -> np.ndarray:
+    """The ``uint64`` table of ``Engine.preferred_ends`` for a Poisson test at level ``alpha``: ``thr[0] = 0`` and, for
+    ``1 <= k < n``, ``thr[k]`` is the largest integer ``q`` in ``[0, k * 2**20]`` with ``P(X >= k | Poisson(q / 2**20)) <
+    alpha`` - the largest mean, in units of 2^-20 ends per base, at which ``k`` ends on one base are still significant.
+    ``P(X >= k | Poisson(m))`` is the regularised lower incomplete gamma function ``gammainc(k, m)``, which grows with
+    ``m``, so ``q`` is found by bisection over the integers.  Counts of ``n - 1`` and more share the last entry."""
+    alpha, n = float(alpha), int(n)
+    if not 0.0 < alpha < 1.0:
+        raise ValueError(f"invalid alpha ({alpha}): it should lie inside (0, 1)")
+    if not 2 <= n <= PREFENDS_MAX_THR:
+        raise ValueError(f"invalid n ({n}): 2 .. {PREFENDS_MAX_THR}")
+    from scipy.special import gammainc
+    k = np.arange(1, n, dtype=np.int64)
+    unit = float(1 << PREFENDS_SCALE_BITS)
+
+    def ok(q):
+        return gammainc(k.astype(np.float64), q / unit) < alpha
+    lo = np.zeros(n - 1, np.int64)          # ok(lo) holds: P = 0
+    hi = k << PREFENDS_SCALE_BITS           # the search ends here
+    top = ok(hi)
+    while np.any(hi - lo > 1):
+        mid = (lo + hi) // 2
+        good = ok(mid)
+        lo = np.where(good, mid, lo)
+        hi = np.where(good, hi, mid)
+    thr = np.zeros(n, np.uint64)
+    thr[1:] = np.where(top, k << PREFENDS_SCALE_BITS, lo).astype(np.uint64)
+    return thr
+
+
+def _check_preferred_ends_args(input_file, chrom_sizes, output_file, summary_file, half_window, alpha, min_count, min_length,
+                               max_length, chunk_size):
+    if output_file is not None and not str(output_file).endswith((".bed", ".bed.gz")):
+        raise ValueError("output_file should have .bed or .bed.gz as suffix")
+    if summary_file is not None and not str(summary_file).endswith((".tsv", ".tsv.gz")):
+        raise ValueError("summary_file should have .tsv or .tsv.gz as suffix")
+    if not 1 <= int(half_window) <= PREFENDS_MAX_HALF:
+        raise ValueError(f"invalid half_window ({half_window}): 1 .. {PREFENDS_MAX_HALF}")
+    if not 0.0 < float(alpha) < 1.0:
+        raise ValueError(f"invalid alpha ({alpha}): it should lie inside (0, 1)")
+    if int(min_count) < 1:
+        raise ValueError(f"invalid min_count ({min_count}): at least 1")
+    if min_length is not None and int(min_length) < 0:
+        raise ValueError(f"invalid min_length ({min_length}): it should not be negative")
+    if max_length is not None and int(max_length) < 0:
+        raise ValueError(f"invalid max_length ({max_length}): it should not be negative")
+    if min_length is not None and max_length is not None and int(min_length) > int(max_length):
+        raise ValueError(f"min_length ({min_length}) exceeds max_length ({max_length})")
+    if int(chunk_size) < 1:
+        raise ValueError(f"invalid chunk_size ({chunk_size}): at least 1")
+    if chrom_sizes is None and not _is_alignment_file(input_file):
+        raise ValueError("chrom_sizes must be specified for BED/Fragment files")
+
+
+def frag_preferred_ends(input_file, interval_file=None, chrom_sizes=None, output_file=None, summary_file=None,
+                        half_window: int = 500, alpha: float = 0.01, min_count: int = 2, split: bool = False, min_length=None,
+                        max_length=None, quality_threshold: int = 30, chunk_size: int = 1 << 22, workers=None,
+                        verbose=False) -> PreferredEnds:
+    """Preferred fragment-end coordinates (Chan et al. 2016, Jiang et al. 2018; ``split``: U and D ends apart, Sun et al.
+    2019): per interval of ``interval_file`` (BED), or over every contig of the input when there is none, the positions on
+    which at least ``min_count`` fragments end and significantly more than a Poisson model predicts whose mean is the end
+    density of the window of ``half_window`` bases on either side (``alpha``: the level of the one-sided test).  The rule
+    is stated in ``include/ftk.h``, "preferred ends"; the test becomes an integer comparison with the table of
+    ``preferred_end_thresholds(alpha)``.  Every base is tested on the GPU, contig by contig as the input is decoded
+    (``Engine.preferred_ends``): only the calls come back to the host.
+
+    Windows read the contig, not the interval: whole-contig mode cuts a contig into chunks of ``chunk_size`` positions
+    without overlap and the result does not depend on ``chunk_size``.  BED intervals are clipped to the contig.
+
+    Chromosome sizes: the BAM header, else the ``chrom_sizes`` file, else ``ValueError``.  An interval on a contig the
+    input lacks raises ``ValueError``, as in ``frag.coverage``.  ``output_file`` (``.bed`` / ``.bed.gz``):
+    ``writers.write_preferred_end_rows``; ``summary_file`` (``.tsv`` / ``.tsv.gz``): ``writers.write_preferred_end_summary``."""
+    import os
+    import sys
+    import time
+
+    from . import writers
+    from .source import ContigFeed
+    _check_preferred_ends_args(input_file, chrom_sizes, output_file, summary_file, half_window, alpha, min_count, min_length,
+                               max_length, chunk_size)
+    t0 = time.time()
+    chunk = int(chunk_size)
+    sizes = None if _is_alignment_file(input_file) else chrom_sizes_to_dict(chrom_sizes)
+    whole = interval_file is None
+    intervals = [] if whole else get_intervals(interval_file)
+    by_contig: dict[str, list[int]] = {}
+    for i, iv in enumerate(intervals):
+        by_contig.setdefault(iv[0], []).append(i)
+    if sizes is not None:
+        for c in by_contig:
+            if c not in sizes:
+                raise ValueError(f"{c} is not in chrom_sizes")
+    args = dict(half=int(half_window), mode="split" if split else "combined", min_count=int(min_count),
+                thresholds=preferred_end_thresholds(alpha), min_length=min_length, max_length=max_length,
+                quality_threshold=quality_threshold)
+    parts, stat_rows = [], {}
+    left = dict(by_contig)
+    eng = get_engine()
+    feed = ContigFeed(input_file, workers, names=None if whole else list(by_contig))
+    try:
+        for src, c in feed:
+            if whole:
+                if sizes is not None and c not in sizes:
+                    raise ValueError(f"{c} is not in chrom_sizes")
+                size = int(src.lengths[c]) if sizes is None else int(sizes[c])
+                idx = [len(intervals)]
+                intervals.append((c, 0, size, "."))
+                cut = np.arange(0, max(size, 1), chunk, dtype=np.int64)
+                calls, stats = eng.preferred_ends(src.key(c), cut, np.minimum(cut + chunk, size), size, **args)
+                which = np.full(len(calls), idx[0], np.int64)  # (chunks follow one another: the calls are in position order)
+                stat_rows[idx[0]] = stats.sum(axis=0)
+            else:
+                idx = left.pop(c, None)
+                if idx is None:
+                    continue
+                size = int(src.lengths[c]) if sizes is None else int(sizes[c])
+                a = np.clip(np.array([intervals[i][1] for i in idx], np.int64), 0, size)
+                b = np.clip(np.array([intervals[i][2] for i in idx], np.int64), a, size)
+                calls, stats = eng.preferred_ends(src.key(c), a, b, size, **args)
+                which = np.asarray(idx, np.int64)[calls["run"]]
+                stat_rows.update(zip(idx, stats))
+            part = np.zeros(len(calls), PREFERRED_END_DTYPE)
+            part["interval"] = which
+            for name in PREFERRED_END_DTYPE.names[1:]:
+                part[name] = calls[name]
+            parts.append(part)
+            if verbose:
+                sys.stderr.write(f"frag_preferred_ends: {c}: {len(idx)} intervals, {len(part)} calls\n")
+        src = feed.finish()
+    except BaseException:
+        feed.close()
+        raise
+    for c in left:  # contigs the file does not hold: the ValueError of frag.coverage
+        src.require(c)
+    calls = np.concatenate(parts) if parts else np.zeros(0, PREFERRED_END_DTYPE)
+    calls = calls[np.argsort(calls["interval"], kind="stable")]  # (an interval's calls are in (pos, kind) order already)
+    n = len(intervals)
+    stats = np.array([stat_rows[i] for i in range(n)], np.int64).reshape(n, 6)
+    on_calls = np.bincount(calls["interval"], weights=calls["count"], minlength=n)[:n] if n else np.zeros(0)
+    ends = (stats[:, 0] + stats[:, 1]).astype(np.float64)
+    share = np.divide(on_calls, ends, out=np.full(n, np.nan), where=ends > 0)
+    res = PreferredEnds(intervals, calls, stats, share)
+    if output_file is not None:
+        writers.write_preferred_end_rows(os.fspath(output_file), res)
+    if summary_file is not None:
+        writers.write_preferred_end_summary(os.fspath(summary_file), res)
+    if verbose:
+        sys.stderr.write(f"frag_preferred_ends: {n} intervals, {len(calls)} calls in {time.time() - t0:.3f} s\n")
     return res
 
 

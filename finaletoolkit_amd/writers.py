@@ -412,3 +412,40 @@ def write_wps_peaks_summary(output_file: str, peaks) -> None:
         rows.append("\t".join([str(c), str(a), str(b), str(name), str(int(n))] + [str(int(x)) for x in stats]
                               + ["nan" if gap != gap else format(float(gap), ".6g")]) + "\n")
     _emit(output_file, "".join(rows), (".tsv",), (".tsv.gz",), message)
+
+
+def write_preferred_end_rows(output_file: str, ends) -> None:
+    """One row per call of a ``utils.PreferredEnds``, ordered by interval, position and kind, without a header line:
+    ``contig pos pos+1 name kind count window_total expected neglog10_p`` - ``name`` the interval's name (``.`` in
+    whole-contig mode), ``kind`` ``U`` / ``D`` / ``B`` (both ends, combined mode), ``expected = window_total / n_w`` the
+    mean of the Poisson model, ``p = P(X >= count)`` under it (``scipy.special.gammainc(count, expected)``), both computed
+    here for the calls alone, the floats with six significant digits; ``.bed`` as text, ``.bed.gz`` as gzip."""
+    message = "output_file should have .bed or .bed.gz as suffix"
+    if not output_file.endswith((".bed", ".bed.gz")):
+        raise ValueError(message)
+    calls = ends.calls
+    rows = []
+    if len(calls):
+        from scipy.special import gammainc
+        expected = calls["total"].astype(np.float64) / calls["n_w"].astype(np.float64)
+        with np.errstate(divide="ignore"):
+            score = -np.log10(gammainc(calls["count"].astype(np.float64), expected))
+        for (i, pos, kind, count, total, _), m, s in zip(calls.tolist(), expected.tolist(), score.tolist()):
+            c, _, _, name = ends.intervals[i]
+            rows.append(f"{c}\t{pos}\t{pos + 1}\t{name}\t{'UDB'[kind]}\t{count}\t{total}\t{format(m, '.6g')}\t{format(s + 0.0, '.6g')}\n")
+    _emit(output_file, "".join(rows), (".bed",), (".bed.gz",), message)
+
+
+def write_preferred_end_summary(output_file: str, ends) -> None:
+    """One row per interval of a ``utils.PreferredEnds``, in its order, behind the header line ``contig start stop name
+    u_ends d_ends tested_a tested_b calls_a calls_b share``: the interval, the six counters of the rule and the share of
+    its ends that lie on called positions (six significant digits, ``nan`` without ends); ``.tsv`` as text, ``.tsv.gz`` as
+    gzip."""
+    message = "summary_file should have .tsv or .tsv.gz as suffix"
+    if not output_file.endswith((".tsv", ".tsv.gz")):
+        raise ValueError(message)
+    rows = ["contig\tstart\tstop\tname\tu_ends\td_ends\ttested_a\ttested_b\tcalls_a\tcalls_b\tshare\n"]
+    for (c, a, b, name), stats, share in zip(ends.intervals, ends.stats, ends.share):
+        rows.append("\t".join([str(c), str(a), str(b), str(name)] + [str(int(x)) for x in stats]
+                              + ["nan" if share != share else format(float(share), ".6g")]) + "\n")
+    _emit(output_file, "".join(rows), (".tsv",), (".tsv.gz",), message)

@@ -918,6 +918,61 @@ int ftk_wps_peaks(ftk_ctx* ctx, int contig_id, const int64_t* iv_start, const in
                   int32_t** run, int64_t** start, int64_t** stop, int64_t** summit, double** height, double** area,
                   int64_t* n_calls, int64_t* stats);
 
+/* ---- preferred ends: Poisson-tested fragment-end calls --------------------------------------------------
+ * The end-signature feature of Chan et al. 2016 / Jiang et al. 2018 (one combined track) and Sun et al. 2019 (U and D
+ * ends apart): the contig positions on which significantly more fragments end than the end density of the window
+ * centred on them predicts.  Every base is tested on the device and only the calls reach the host - under a uniform
+ * null at 30x and alpha = 0.01 about 0.6 % of the positions.
+ *
+ * THE RULE.  Everything in it is an integer.
+ *  1. Ends: a fragment [start, end) of the resident contig passes with mapq >= mapq_min, min_len <= end - start <=
+ *     max_len (FTK_LEN_OPEN = no bound) and end > start.  Its U end is on base start, its D end on base end - 1 (the
+ *     convention of ftk_site_ends); a fragment of length 1 puts both on one base.  u(b) / d(b) count the U / D ends on
+ *     base b of [0, chrom_size); ends on bases outside that range do not exist.  The read1 columns of a BAM contig play
+ *     no part.
+ *  2. Tracks: mode FTK_PREFENDS_COMBINED has one track e = u + d of kind FTK_PREFENDS_KIND_B (2); mode
+ *     FTK_PREFENDS_SPLIT has two, e = u of kind FTK_PREFENDS_KIND_U (0) and e = d of kind FTK_PREFENDS_KIND_D (1), each
+ *     tested against its own window total.
+ *  3. Window: with half = h, 1 <= h <= FTK_PREFENDS_MAX_HALF: w_lo = max(b - h, 0), w_hi = min(b + h, chrom_size - 1),
+ *     n_w = w_hi - w_lo + 1, T(b) = the sum of e over [w_lo, w_hi], the base itself included.  The window reads the
+ *     contig and never stops at the bounds of the interval being called: whether a position is called does not depend
+ *     on how the caller cuts the contig.
+ *  4. Decision: with the caller's table thr[0 .. n_thr), 2 <= n_thr <= FTK_PREFENDS_MAX_THR, every entry < 2^40, a
+ *     position is called on a track iff, in unsigned 64-bit arithmetic,
+ *         e(b) >= min_count                                        (min_count >= 1)   and
+ *         T(b) * 2^20 <= thr[min(e(b), n_thr - 1)] * n_w(b).
+ *     Nothing overflows: T < 2^32 and n_w <= 4097.  thr[k] is the largest mean, in units of 2^-20 ends per base, at
+ *     which k ends on one base are still significant; an entry of 0 means "never".  The library does not interpret the
+ *     table (finaletoolkit_amd.utils.preferred_end_thresholds builds the Poisson one).
+ *  5. A call is (run, pos, kind, count, total, n_w): run the interval's number, pos a contig position, count = e,
+ *     total = T.  Calls come ordered by (run, pos, kind).
+ *  6. Per interval six int64 counters, in this order: U ends on its positions, D ends on its positions, positions
+ *     tested on track a (e >= min_count), positions tested on track b, calls on track a, calls on track b.  Split mode:
+ *     a = U, b = D.  Combined mode: a is the combined track and the b slots hold 0.
+ * Intervals [iv_start[i], iv_stop[i]) may overlap, touch, be empty or come in any order; each is a run of its own.
+ *
+ * ftk_preferred_ends: the six columns come back in host blocks of the library's, *n_calls entries each (NULL when there
+ * is no call), to be released with ftk_buffer_free; stats: n_iv * 6 counters in host memory.  The intervals are walked
+ * tile by tile in batches whose device scratch is bounded, so a whole chromosome may be one interval.  The call reads
+ * the packed (length, mapq) column of the contig where the filter allows it and the wide columns otherwise, with the
+ * same calls either way.  A call is the same bytes in every call that asks for it.
+ * FTK_ERR_INVALID: a NULL argument (the interval and stats arrays may be NULL when n_iv == 0), device pointers for the
+ * interval, table or stats arrays, n_iv < 0, an interval with start < 0, stop < start or stop > chrom_size, chrom_size
+ * outside [0, 2^30), half, mode, min_count, n_thr or a table entry outside the ranges above.  FTK_ERR_NO_CONTIG: an
+ * unknown contig.  A failing call hands out no block and writes no counter.  n_iv == 0, empty intervals and an empty
+ * contig are valid: no calls, zero counters. */
+#define FTK_PREFENDS_MAX_HALF 2048
+#define FTK_PREFENDS_MAX_THR 4096
+#define FTK_PREFENDS_COMBINED 0
+#define FTK_PREFENDS_SPLIT 1
+#define FTK_PREFENDS_KIND_U 0
+#define FTK_PREFENDS_KIND_D 1
+#define FTK_PREFENDS_KIND_B 2
+int ftk_preferred_ends(ftk_ctx* ctx, int contig_id, const int64_t* iv_start, const int64_t* iv_stop, int64_t n_iv,
+                       int64_t chrom_size, int32_t half, int32_t mode, int32_t min_count, const uint64_t* thr, int32_t n_thr,
+                       int32_t min_len, int32_t max_len, int32_t mapq_min, int32_t** run, int64_t** pos, int32_t** kind,
+                       int32_t** count, int64_t** total, int32_t** n_w, int64_t* n_calls, int64_t* stats /* n_iv * 6, host */);
+
 /* ---- multi-GPU (SURVEY 8-e, 8-b's export list) -------------------------------------------------
  * One process and one ftk_ctx per GPU.  Contigs / genome runs are dealt to the ranks by the host and every window,
  * bin and base depends on its own contig's fragments only, so the data path has no collective.  What remains are the

@@ -11,7 +11,9 @@ of the widest weighted profile, and the route there was before (the columns to h
 KBENCH=spectrum: the WPS periodogram of 2 000 regions x 10 000 bases at periods 120-280 - the transform alone, the fused call, and
 the route there was before (ftk_wps_intervals to host memory + a numpy matrix product on the host threads).
 KBENCH=peaks: nucleosome calls on the same regions - the two peak passes alone on a resident adjusted track, ftk_wps_adjust on the
-same runs, the fused call, and the route there was before (scores and adjusted track carried through host memory)."""
+same runs, the fused call, and the route there was before (scores and adjusted track carried through host memory).
+KBENCH=prefends: preferred ends of the whole contig at h = 500 and h = 2048, combined and split, beside ftk_depth_runs and
+ftk_cleavage of the same region (the same tile skeleton), with the call's byte floor."""
 import os
 import sys
 
@@ -575,6 +577,57 @@ if "peaks" in which:
     print("peaks checksum: calls", len(c_f), "counters", s_f.sum(axis=0).tolist(), "fused == two-step bits",
           bool(c_f.tobytes() == c_2.tobytes() and np.array_equal(s_f, s_2)), "fused == passes bits",
           bool(c_f.tobytes() == c_p.tobytes() and np.array_equal(s_f, s_p)))
+if "prefends" in which:
+    # Preferred ends of the whole contig as one interval: the whole call (per batch of tiles the count pass, the scan, one
+    # read-back, the write pass, the calls copied to host blocks) at h = 500 and h = 2048 in both modes, beside
+    # ftk_depth_runs (whole call) and ftk_cleavage (launch into a device buffer) of the same region.  Byte floor: the
+    # columns of every candidate of a 4 096-base tile (counted from the sorted starts as in the depth mode; 6 B with the
+    # packed column, else 9 B) times (tile + 2 h) / tile for the halo, read by both passes, plus 32 B per call written.
+    import time
+
+    from finaletoolkit_amd import _lib as L
+    from finaletoolkit_amd.utils import preferred_end_thresholds
+    TILE = L.PREFENDS_TILE
+    lmax = eng.info("c")[1]
+    hs = s.cpu().numpy().astype(np.int64)
+    t0 = np.arange(0, size, TILE, dtype=np.int64)
+    t1 = np.minimum(t0 + TILE, size)
+    cand = int((np.searchsorted(hs, ((t1 >> 9) + 1) << 9, side="left")
+                - np.searchsorted(hs, (np.maximum(t0 - lmax, 0) >> 9) << 9, side="left")).sum())
+    col_bytes = 6 if eng.frags_packed("c") else 9
+    thr = preferred_end_thresholds(0.01)
+    cl = torch.empty(size, dtype=torch.float64, device=dev)
+    got = {}
+
+    def call(h, mode):
+        got[h, mode] = eng.preferred_ends("c", [0], [size], size, half=h, mode=mode, thresholds=thr)
+
+    def wall(fn, name):
+        fn()
+        torch.cuda.synchronize()
+        ts = []
+        for _ in range(max(reps // 4, 3)):
+            a = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            ts.append(time.perf_counter() - a)
+        ts = np.array(ts)
+        print(f"{name:34s} median {np.median(ts) * 1e3:9.3f} ms  min {ts.min() * 1e3:9.3f} ms", flush=True)
+        return float(np.median(ts))
+
+    print(f"prefends: {n} fragments, {len(t0)} tiles, {cand} candidates ({cand / n:.2f} per fragment), {col_bytes} B per candidate",
+          flush=True)
+    for _ in range(2):  # twice: the spread between the two passes is the noise
+        t_runs = wall(lambda: eng.depth_runs("c", 0, size, 30), "depth runs (whole call)")
+        t_cl = wall(lambda: eng.cleavage("c", 0, size, None, None, 30, out=cl), "cleavage (launch)")
+        for h in (500, 2048):
+            for mode in ("combined", "split"):
+                t = wall(lambda: call(h, mode), f"preferred ends h={h} {mode}")
+                halo = (TILE + 2 * h) / TILE
+                floor = (2 * col_bytes * cand * halo + 32 * len(got[h, mode][0])) / (bench.HBM_PEAK_GBS * 1e9)
+                print(f"  {len(got[h, mode][0])} calls; {t / t_runs:.2f} x depth runs, {t / t_cl:.2f} x cleavage; halo factor x 2 = "
+                      f"{2 * halo:.2f}; {floor / t:.1%} of the byte floor ({floor * 1e3:.3f} ms)", flush=True)
+    print("prefends checksum:", {f"{h}/{mode}": (len(c), st.sum(axis=0).tolist()) for (h, mode), (c, st) in sorted(got.items())})
 if "gc" in which:
     rng = np.random.default_rng(6)
     packed = rng.integers(0, 256, (size + 3) // 4, dtype=np.uint8)
