@@ -670,13 +670,22 @@ __global__ __launch_bounds__(64) FTK_INFLATE_OCC void bgzf_inflate_kernel(const 
                     const unsigned mlen = lbase + (wl & ((1u << xb) - 1u));
                     const unsigned wd = wl >> xb;
                     unsigned D = L.dist[wd & ((1u << kDistRoot) - 1u)];
+                    // the distance's extra bits: behind a code of the root table wd's 32 - xb bits hold them (8 + 13 <= 27)
+                    unsigned wx = wd >> (D & 15u);
                     if (D == 0u && k1 == 0u && lbase != 0u && lbase != 511u) {  // (rarer still: a long distance code)
                         int len = 0;
                         const int ds = long_code(wd, 1, len);
-                        if (ds >= 0) D = dist_entry((unsigned)len, (unsigned)ds);
+                        if (ds >= 0) {
+                            D = dist_entry((unsigned)len, (unsigned)ds);
+                            // ... behind a long one they do not: 5 extra bits of the length, a 15-bit distance code and 13
+                            // extra bits are 33 (48 with a 15-bit length code), so the extra bits are taken from the lane's
+                            // 64 bits at their own offset (<= 35)
+                            const unsigned o = lb + xb + (unsigned)len;
+                            wx = o < 32u ? __builtin_amdgcn_alignbit(w1, w0, o) : w1 >> (o - 32u);
+                        }
                     }
                     const unsigned dbits = D & 15u, dxb = (D >> 4) & 15u, dbase = D >> 8;
-                    const unsigned mdist = dbase + ((wd >> dbits) & ((1u << dxb) - 1u));
+                    const unsigned mdist = dbase + (wx & ((1u << dxb) - 1u));
                     const bool is_match = k1 == 0u && lbase != 0u && lbase != 511u && D != 0u && dbase != 0x7fffffu;
                     nb = is_match ? lb + xb + dbits + dxb : (k1 ? lb : 0u);
                     // token: kind (1 / 2 literals, 3 match) | literal bytes at bits 8 and 16, or length << 2 | distance << 11

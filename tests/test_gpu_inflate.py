@@ -36,11 +36,9 @@ def _inflate_once(engine, image: bytes):
     return rc, buf[:n_out.value].tobytes()
 
 
-def _inflate(engine, image: bytes):
-    """Every symbol loop of the kernel on the same image - the windowed loop with a window's matches copied one after
-    the other (text streams) or resolved on the lanes side by side (BAM streams; ``FTK_INFLATE_VECTOR_MATCHES=1``), and
-    the lane-parallel loop, the default at every launch size (``FTK_INFLATE_LANES`` unset or non-zero; ``=0`` selects the
-    windowed loop) - must agree; the callers then hold the result against zlib."""
+def _inflate_each(engine, image: bytes):
+    """``(rc, bytes, ftk_last_error)`` of every symbol loop of the kernel on the same image, in the order serial windows,
+    vector matches, lane-parallel (see ``_inflate``)."""
     import os
     names = ("FTK_INFLATE_VECTOR_MATCHES", "FTK_INFLATE_LANES")
     keep = {k: os.environ.get(k) for k in names}
@@ -48,14 +46,23 @@ def _inflate(engine, image: bytes):
         got = []
         for vec, lanes in (("0", "0"), ("1", "0"), ("0", "1")):
             os.environ.update(FTK_INFLATE_VECTOR_MATCHES=vec, FTK_INFLATE_LANES=lanes)
-            got.append(_inflate_once(engine, image))
+            rc, data = _inflate_once(engine, image)
+            got.append((rc, data, engine.lib.ftk_last_error(engine.ctx) if rc != L.FTK_OK else None))
     finally:
         for k, v in keep.items():
             if v is None:
                 os.environ.pop(k, None)
             else:
                 os.environ[k] = v
-    serial, vector, lanes = got
+    return got
+
+
+def _inflate(engine, image: bytes):
+    """Every symbol loop of the kernel on the same image - the windowed loop with a window's matches copied one after
+    the other (text streams) or resolved on the lanes side by side (BAM streams; ``FTK_INFLATE_VECTOR_MATCHES=1``), and
+    the lane-parallel loop, the default at every launch size (``FTK_INFLATE_LANES`` unset or non-zero; ``=0`` selects the
+    windowed loop) - must agree; the callers then hold the result against zlib."""
+    serial, vector, lanes = [g[:2] for g in _inflate_each(engine, image)]
     assert serial[0] == vector[0] and (serial[0] != L.FTK_OK or serial[1] == vector[1])
     # (a damaged payload may trip a different check first in the lane-parallel loop: both must refuse it)
     assert (serial[0] == L.FTK_OK) == (lanes[0] == L.FTK_OK) and (serial[0] != L.FTK_OK or serial[1] == lanes[1])
