@@ -1,5 +1,5 @@
 """GPU: the site-aggregated midpoint profile (``csrc/ftk_siteprofile.hip``) - ``Engine.site_profile`` against a numpy
-restatement of its rule written here, exactly equal everywhere (sums and counts are integers): sites on the edges of
+restatement of its rule (``tests/site_profile_helpers.py``), exactly equal everywhere (sums and counts are integers): sites on the edges of
 hand-placed midpoints, at the contig's ends, in a gap and on a run of copies longer than one chunk, every shape from
 one bin to 4096, site lists in any order with repeats, empty groups, more groups than workgroups fit and groups that
 several workgroups flush into; weights past 2^48; the ties to ``window_counts`` and ``weighted_window_sums``; a contig
@@ -21,6 +21,7 @@ import pytest
 
 from tests.gc_genome import LAYOUT, N_DUP, Contig, make_contig
 from tests.helpers import read_frag_gz, write_2bit, write_synthetic_bam
+from tests.site_profile_helpers import restated_profile
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -56,42 +57,6 @@ def profile_contig(rng):
     s, e, q, r1s, rl = s[o], e[o], q[o], r1s[o], rl[o]
     assert (e - s).max() == LONG[1] - LONG[0] and ((e - s) == LONG[1] - LONG[0]).sum() == 1
     return s, e, q, r1s, r1s + rl
-
-
-def restated_profile(cols, w, centres, flip, groups, n_groups, H, b, mapq_min=30, min_len=None, max_len=None):
-    """(sums, counts) int64 of shape (n_groups, 2 H // b): the rule of the module's docstring, site by site.  ``w``:
-    the weight column, or None for FTK_WEIGHT_ONE each.  (The weights are summed in two 16-bit halves, so that
-    ``np.bincount``'s float64 sums stay exact.)"""
-    s, e, q = (np.asarray(cols[k], np.int64) for k in range(3))
-    ln = e - s
-    keep = q >= mapq_min
-    if min_len is not None:
-        keep &= ln >= min_len
-    if max_len is not None:
-        keep &= ln <= max_len
-    mid = ((s + e) >> 1)[keep]
-    wt = np.full(len(mid), ONE, np.int64) if w is None else np.asarray(w, np.int64)[keep]
-    o = np.argsort(mid, kind="stable")
-    mid, wt = mid[o], wt[o]
-    assert (2 * H) % b == 0
-    n_bins = 2 * H // b
-    sums, counts = np.zeros((n_groups, n_bins), np.int64), np.zeros((n_groups, n_bins), np.int64)
-    centres = np.asarray(centres, np.int64)
-    flip = np.zeros(len(centres), bool) if flip is None else np.asarray(flip).astype(bool)
-    groups = np.zeros(len(centres), np.int64) if groups is None else np.asarray(groups, np.int64)
-    lo_i, hi_i = np.searchsorted(mid, centres - H, "left"), np.searchsorted(mid, centres + H, "left")
-    for c, f, g, lo, hi in zip(centres.tolist(), flip.tolist(), groups.tolist(), lo_i.tolist(), hi_i.tolist()):
-        if hi == lo:
-            continue
-        k = (mid[lo:hi] - c + H) // b
-        if f:
-            k = n_bins - 1 - k
-        x = wt[lo:hi]
-        counts[g] += np.bincount(k, minlength=n_bins)
-        low = np.bincount(k, weights=(x & 0xffff).astype(np.float64), minlength=n_bins).astype(np.int64)
-        high = np.bincount(k, weights=(x >> 16).astype(np.float64), minlength=n_bins).astype(np.int64)
-        sums[g] += (high << 16) + low
-    return sums, counts
 
 
 def boundary_sites(H):
