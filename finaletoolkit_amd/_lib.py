@@ -39,6 +39,12 @@ PREFENDS_MAX_HALF = 2048  # FTK_PREFENDS_MAX_HALF
 PREFENDS_MAX_THR = 4096  # FTK_PREFENDS_MAX_THR
 PREFENDS_TILE = 4096  # kPrefTile: positions per workgroup of the preferred-end passes
 PREFENDS_BATCH_TILES = 4096  # kPrefBatchTiles: tiles the call plans, counts and writes at a time
+IFS_MAX_WINDOW_BINS = 64  # FTK_IFS_MAX_WINDOW_BINS
+IFS_MAX_REACH = 1024  # FTK_IFS_MAX_REACH
+IFS_MAX_THR = 4096  # FTK_IFS_MAX_THR
+IFS_MAX_JOIN = 1024  # FTK_IFS_MAX_JOIN
+HOTSPOTS_TILE = 4096  # kIfsTile: windows per workgroup of the hotspot passes
+HOTSPOTS_BATCH_TILES = 4096  # kIfsBatchTiles: tiles the call plans, counts and writes at a time
 SPECTRUM_TILE = 16 << 10  # kSpectrumLdsSamples: a run of up to this many samples is folded out of LDS, a longer one from memory
 POLICY = {"midpoint": 0, "any": 1}
 POLICY_FETCH = 2  # no intersect test: the index query alone (AlignmentWrapper.fetch)
@@ -78,6 +84,7 @@ EXPORTS = [
     "ftk_track_spectrum", "ftk_wps_spectrum",
     "ftk_track_peaks", "ftk_wps_peaks",
     "ftk_preferred_ends",
+    "ftk_ifs_hotspots", "ftk_ifs_track", "ftk_ifs_totals",
 ]
 
 
@@ -361,6 +368,11 @@ def load() -> C.CDLL:
     lib.ftk_wps_peaks.argtypes = [vp, C.c_int, vp, vp, i64, i64, i32, i32, i32, i32, i32, i32, vp, vp, i32, i32, i32, i32, i64] + peaks_out
     # run, pos, kind, count, total, n_w, n_calls, stats
     lib.ftk_preferred_ends.argtypes = [vp, C.c_int, vp, vp, i64, i64, i32, i32, i32, vp, i32, i32, i32, i32] + [C.POINTER(vp)] * 6 + [C.POINTER(i64), vp]
+    # 8 called-window columns, their count, 9 hotspot columns, their count, stats
+    lib.ftk_ifs_hotspots.argtypes = ([vp, C.c_int, vp, vp, i64, i64, i32, i32, i32, i32, i32, i32, vp, i32, i64, i32, i32, i32, i32, i32]
+                                     + [C.POINTER(vp)] * 8 + [C.POINTER(i64)] + [C.POINTER(vp)] * 9 + [C.POINTER(i64), vp])
+    lib.ftk_ifs_track.argtypes = [vp, C.c_int, vp, vp, i64, vp, i64, i32, i32, i32, i32, i32, i32, vp, vp]
+    lib.ftk_ifs_totals.argtypes = [vp, C.c_int, i64, i32, i32, i32, C.POINTER(i64), C.POINTER(i64)]
     lib.ftk_comm_unique_id.argtypes = [C.c_char_p]
     lib.ftk_comm_create.argtypes = [vp, C.c_int, C.c_int, C.c_char_p, C.POINTER(vp)]
     lib.ftk_comm_size.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]

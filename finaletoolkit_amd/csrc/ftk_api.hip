@@ -1276,3 +1276,4 @@ static int wps_params(ftk_ctx* ctx, const ContigData& c, int64_t chrom_size, int
 #include "ftk_api_spectrum.inc"
 #include "ftk_api_peaks.inc"
 #include "ftk_api_prefends.inc"
+#include "ftk_api_hotspots.inc"

@@ -1080,6 +1080,121 @@ class Engine:
                     self.lib.ftk_buffer_free(p.value)
         return calls, stats
 
+    # -- IFS fragmentation hotspots (csrc/ftk_hotspots.hip) ---------------------------------------
+    IFS_WINDOW_DTYPE = np.dtype([("run", np.int32), ("pos", np.int64), ("count", np.int32), ("ifs", np.int64),
+                                 ("bg1", np.int64), ("nb1", np.int32), ("bg2", np.int64), ("nb2", np.int32)])
+    HOTSPOT_DTYPE = np.dtype([("run", np.int32), ("start", np.int64), ("stop", np.int64), ("n_windows", np.int32),
+                              ("summit", np.int64), ("ifs", np.int64), ("count", np.int32), ("bg1", np.int64),
+                              ("nb1", np.int32)])
+
+    @staticmethod
+    def ifs_window_ranges(starts, stops, chrom_size: int, step: int, m: int):
+        """``(k_lo, n)``: the first window and the number of windows of every interval ``[starts[i], stops[i])`` (rule 2 of
+        "IFS hotspots" in ``include/ftk.h``: window ``k`` belongs iff ``starts[i] <= k * step`` and its span ends at or
+        before ``stops[i]``)."""
+        s = np.asarray(starts, dtype=np.int64)
+        e = np.asarray(stops, dtype=np.int64)
+        step, m, size = int(step), int(m), int(chrom_size)
+        n_bins = -(-size // step)
+        k_lo = -(-s // step)
+        k_hi = np.where(e == size, n_bins - m, np.minimum(e // step - m, n_bins - m))
+        return k_lo, np.maximum(k_hi - k_lo + 1, 0)
+
+    def ifs_track(self, name: str, starts, stops, chrom_size: int, step=20, m=10, mean_length=167, min_length=None,
+                  max_length=None, quality_threshold=30, device=False):
+        """``(n, ifs, offsets)``: the midpoint count ``n`` (int32) and the integer IFS ``I`` (int64, in units of
+        ``1 / mean_length``) of every window of the intervals ``[starts[i], stops[i])`` of resident contig ``name``
+        (``ftk_ifs_track``; the rule is in ``include/ftk.h``, "IFS hotspots"), interval ``i`` at
+        ``[offsets[i], offsets[i + 1])``.  ``device``: the two arrays stay on the GPU (torch tensors)."""
+        s = np.ascontiguousarray(starts, dtype=np.int64)
+        e = np.ascontiguousarray(stops, dtype=np.int64)
+        if s.shape != e.shape or s.ndim != 1:
+            raise ValueError("starts and stops should be one-dimensional and equal in length")
+        if not 1 <= int(step) <= 65535 or not 1 <= int(m) <= L.IFS_MAX_WINDOW_BINS or not 0 <= int(chrom_size) < 1 << 30:
+            count = np.zeros(len(s), np.int64)  # (the library refuses the call below)
+        else:
+            count = self.ifs_window_ranges(s, e, chrom_size, step, m)[1]
+        offs = np.zeros(len(s) + 1, np.int64)
+        np.cumsum(count, out=offs[1:])
+        total = int(offs[-1])
+        if device:
+            import torch
+            dev = torch.device("cuda", self.device)
+            n_out = torch.zeros(total, dtype=torch.int32, device=dev)
+            i_out = torch.zeros(total, dtype=torch.int64, device=dev)
+        else:
+            n_out = np.zeros(total, np.int32)
+            i_out = np.zeros(total, np.int64)
+        keep = np.empty(1, np.int64)
+        self._check(self.lib.ftk_ifs_track(
+            self.ctx, self.contig_id(name), L.ptr(s if len(s) else keep), L.ptr(e if len(s) else keep), len(s),
+            L.ptr(np.ascontiguousarray(offs[:-1]) if len(s) else keep), int(chrom_size), int(step), int(m), int(mean_length),
+            L.LEN_OPEN if min_length is None else int(min_length), L.LEN_OPEN if max_length is None else int(max_length),
+            int(quality_threshold), L.ptr(n_out) if total else None, L.ptr(i_out) if total else None))
+        return n_out, i_out, offs
+
+    def ifs_totals(self, name: str, chrom_size: int, min_length=None, max_length=None, quality_threshold=30):
+        """``(N, S)``: the number and the length sum of the passing fragments of resident contig ``name`` whose midpoint
+        lies in ``[0, chrom_size)`` (``ftk_ifs_totals``, reduced on the GPU) - Python integers."""
+        n, sm = C.c_int64(), C.c_int64()
+        self._check(self.lib.ftk_ifs_totals(
+            self.ctx, self.contig_id(name), int(chrom_size), L.LEN_OPEN if min_length is None else int(min_length),
+            L.LEN_OPEN if max_length is None else int(max_length), int(quality_threshold), C.byref(n), C.byref(sm)))
+        return int(n.value), int(sm.value)
+
+    def ifs_hotspots(self, name: str, starts, stops, chrom_size: int, step=20, m=10, mean_length=167, h1=125, h2=250,
+                     min_count=0, thresholds=None, global_mean=0, join=None, min_windows=1, min_length=None, max_length=None,
+                     quality_threshold=30):
+        """``(windows, hotspots, stats)``: the IFS hotspots of the intervals ``[starts[i], stops[i])`` of resident contig
+        ``name`` (``ftk_ifs_hotspots``; the rule is in ``include/ftk.h``, "IFS hotspots"): the windows of ``m`` bins of
+        ``step`` bases whose integer IFS is significantly low against the backgrounds of ``h1`` and ``h2`` bins on either
+        side (``h2 = 0``: one background) and against ``global_mean`` (0: off), merged over gaps of up to ``join``
+        windows (``None``: ``m + 200 // step``, at least 1).  ``thresholds``: the table (``None``:
+        ``utils.ifs_thresholds()``).  ``windows``: the called windows (``Engine.IFS_WINDOW_DTYPE``) ordered by ``(run,
+        pos)``; ``hotspots``: ``Engine.HOTSPOT_DTYPE`` records ordered by ``(run, start)``; ``stats``: int64
+        ``[n_intervals, 6]`` (windows, tested, called, hotspots kept, hotspots dropped, bases covered)."""
+        s = np.ascontiguousarray(starts, dtype=np.int64)
+        e = np.ascontiguousarray(stops, dtype=np.int64)
+        if s.shape != e.shape or s.ndim != 1:
+            raise ValueError("starts and stops should be one-dimensional and equal in length")
+        if thresholds is None:
+            from .utils import ifs_thresholds
+            thresholds = ifs_thresholds()
+        thr = np.ascontiguousarray(thresholds, dtype=np.uint64)
+        if thr.ndim != 1:
+            raise ValueError("thresholds should be one-dimensional")
+        if join is None:
+            join = max(int(m) + 200 // max(int(step), 1), 1)
+        n_iv = len(s)
+        wp = [C.c_void_p() for _ in self.IFS_WINDOW_DTYPE.names]
+        hp = [C.c_void_p() for _ in self.HOTSPOT_DTYPE.names]
+        nw, nh = C.c_int64(), C.c_int64()
+        stats = np.zeros((n_iv, 6), np.int64)
+        keep = np.empty(1, np.int64)
+
+        def home(dtype, ptrs, n):
+            rec = np.zeros(n, dtype)
+            for col, p in zip(dtype.names, ptrs):
+                dt = dtype[col]
+                if n:  # (one copy: out of the library's block into the records)
+                    rec[col] = np.frombuffer((C.c_char * (n * dt.itemsize)).from_address(p.value), dt)
+            return rec
+        try:
+            self._check(self.lib.ftk_ifs_hotspots(
+                self.ctx, self.contig_id(name), L.ptr(s if n_iv else keep), L.ptr(e if n_iv else keep), n_iv, int(chrom_size),
+                int(step), int(m), int(mean_length), int(h1), int(h2), int(min_count), L.ptr(thr if len(thr) else keep), len(thr),
+                int(global_mean), int(join), int(min_windows),
+                L.LEN_OPEN if min_length is None else int(min_length), L.LEN_OPEN if max_length is None else int(max_length),
+                int(quality_threshold), *[C.byref(p) for p in wp], C.byref(nw), *[C.byref(p) for p in hp], C.byref(nh),
+                L.ptr(stats if n_iv else keep)))
+            windows = home(self.IFS_WINDOW_DTYPE, wp, nw.value)
+            hotspots = home(self.HOTSPOT_DTYPE, hp, nh.value)
+        finally:
+            for p in wp + hp:
+                if p.value:
+                    self.lib.ftk_buffer_free(p.value)
+        return windows, hotspots, stats
+
     # -- WPS post-processing --------------------------------------------------------
     def wps_adjust(self, scores, offsets, median_window_size=1000, mean=False, edge_sub=None, savgol_window_size=21,
                    savgol_poly_deg=2, savgol=True, out=None):

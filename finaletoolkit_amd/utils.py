@@ -17,7 +17,7 @@ from .exceptions import InvalidInputError
 from .source import get_engine, open_source
 
 __all__ = ["chrom_sizes_to_list", "chrom_sizes_to_dict", "get_intervals", "overlaps", "frags_in_region", "frag_generator",
-           "frag_array", "frag_export", "frag_filter", "frag_gc_coverage", "frag_site_profile", "frag_vplot", "VPlot", "frag_ocf", "OCF", "frag_wps_spectrum", "WpsSpectrum", "frag_wps_peaks", "WpsPeaks", "frag_preferred_ends", "PreferredEnds", "preferred_end_thresholds", "read_sites", "gc_weights", "read_gc_bias_table", "read_region_mask", "agg_bw", "gen_kmers", "reverse_complement", "validate_compatible_contigs", "valid_interval",
+           "frag_array", "frag_export", "frag_filter", "frag_gc_coverage", "frag_site_profile", "frag_vplot", "VPlot", "frag_ocf", "OCF", "frag_wps_spectrum", "WpsSpectrum", "frag_wps_peaks", "WpsPeaks", "frag_preferred_ends", "PreferredEnds", "preferred_end_thresholds", "frag_hotspots", "IfsHotspots", "ifs_thresholds", "read_sites", "gc_weights", "read_gc_bias_table", "read_region_mask", "agg_bw", "gen_kmers", "reverse_complement", "validate_compatible_contigs", "valid_interval",
            "_none_eq", "_none_geq", "_none_leq"]
 
 FragTuple = Tuple[str, int, int, int, bool]
@@ -1514,6 +1514,230 @@ def frag_preferred_ends(input_file, interval_file=None, chrom_sizes=None, output
         writers.write_preferred_end_summary(os.fspath(summary_file), res)
     if verbose:
         sys.stderr.write(f"frag_preferred_ends: {n} intervals, {len(calls)} calls in {time.time() - t0:.3f} s\n")
+    return res
+
+
+class IfsHotspots(NamedTuple):
+    """Result of ``frag_hotspots``, one row of ``stats`` / ``mean_length`` / ``global_mean`` per interval (of the interval
+    file, in its order; whole-contig mode: per contig of the input, in the order the contigs were met)."""
+    intervals: list          # (contig, start, stop, name)
+    hotspots: np.ndarray     # HOTSPOT_DTYPE records ordered by (interval, start); contig positions
+    windows: np.ndarray      # IFS_WINDOW_DTYPE records, the called windows, ordered by (interval, start)
+    stats: np.ndarray        # int64 (n_intervals, 6): windows, tested, called, hotspots kept, hotspots dropped, bases covered
+    mean_length: np.ndarray  # int64 per interval: L of its contig
+    global_mean: np.ndarray  # int64 per interval: its contig's mean IFS per window in units of 2^-10 (0: not used)
+    step: int                # bases per bin
+    window_bins: int         # m
+
+
+HOTSPOT_DTYPE = np.dtype([("interval", np.int64), ("start", np.int64), ("stop", np.int64), ("n_windows", np.int32),
+                          ("summit", np.int64), ("ifs", np.int64), ("count", np.int32), ("bg1", np.int64), ("nb1", np.int32)])
+IFS_WINDOW_DTYPE = np.dtype([("interval", np.int64), ("start", np.int64), ("stop", np.int64), ("count", np.int32),
+                             ("ifs", np.int64), ("bg1", np.int64), ("nb1", np.int32), ("bg2", np.int64), ("nb2", np.int32)])
+IFS_MAX_WINDOW_BINS = 64   # FTK_IFS_MAX_WINDOW_BINS
+IFS_MAX_REACH = 1024       # FTK_IFS_MAX_REACH
+IFS_MAX_THR = 4096         # FTK_IFS_MAX_THR
+IFS_MAX_JOIN = 1024        # FTK_IFS_MAX_JOIN
+IFS_SCALE_BITS = 10        # a table entry is a mean IFS per window in units of 2^-10
+
+
+def ifs_thresholds(alpha: float = 1e-5, n: int = 256) -> np.ndarray:
+    """The ``uint64`` table of ``Engine.ifs_hotspots`` for a Poisson lower-tail test at level ``alpha``: ``thr[q]`` is the
+    smallest integer ``t`` with ``P(X <= q | Poisson(t / 1024)) <= alpha`` - the smallest mean, in units of 2^-10, at which
+    an integer IFS of ``q`` is significantly low.  ``P(X <= q | Poisson(x))`` is the regularised upper incomplete gamma
+    function ``gammaincc(q + 1, x)``, which falls as ``x`` grows, so ``t`` is found by bisection over the integers between 0
+    (where it is 1) and a Chernoff bound ``q + A + sqrt(A^2 + 2 q A) + 1`` with ``A = -ln(alpha)`` (where it is at most
+    ``alpha``: asserted)."""
+    alpha, n = float(alpha), int(n)
+    if not 0.0 < alpha < 1.0:
+        raise ValueError(f"invalid alpha ({alpha}): it should lie inside (0, 1)")
+    if not 1 <= n <= IFS_MAX_THR:
+        raise ValueError(f"invalid n ({n}): 1 .. {IFS_MAX_THR}")
+    from scipy.special import gammaincc
+    q = np.arange(n, dtype=np.float64)
+    unit = float(1 << IFS_SCALE_BITS)
+
+    def ok(t):
+        return gammaincc(q + 1.0, t / unit) <= alpha
+    A = -np.log(alpha)
+    lo = np.zeros(n, np.int64)  # ok(lo) fails: P = 1
+    hi = np.ceil((q + A + np.sqrt(A * A + 2.0 * q * A) + 1.0) * unit).astype(np.int64)
+    assert np.all(ok(hi)), "the upper bracket of ifs_thresholds is not significant"
+    while np.any(hi - lo > 1):
+        mid = (lo + hi) // 2
+        good = ok(mid)
+        hi = np.where(good, mid, hi)
+        lo = np.where(good, lo, mid)
+    return hi.astype(np.uint64)
+
+
+def _check_hotspots_args(input_file, chrom_sizes, output_file, windows_file, summary_file, step, window, background, alpha,
+                         mean_length, min_count, join, min_windows, min_length, max_length):
+    for f, what in ((output_file, "output_file"), (windows_file, "windows_file")):
+        if f is not None and not str(f).endswith((".bed", ".bed.gz")):
+            raise ValueError(f"{what} should have .bed or .bed.gz as suffix")
+    if summary_file is not None and not str(summary_file).endswith((".tsv", ".tsv.gz")):
+        raise ValueError("summary_file should have .tsv or .tsv.gz as suffix")
+    step, window = int(step), int(window)
+    if not 1 <= step <= 65535:
+        raise ValueError(f"invalid step ({step}): 1 .. 65535")
+    if window < step or window % step:
+        raise ValueError(f"invalid window ({window}): a positive multiple of step ({step})")
+    m = window // step
+    if m > IFS_MAX_WINDOW_BINS:
+        raise ValueError(f"invalid window ({window}): at most {IFS_MAX_WINDOW_BINS} steps")
+    try:
+        bg = [int(b) for b in background]
+    except TypeError:
+        bg = [int(background)]
+    if not 1 <= len(bg) <= 2:
+        raise ValueError("background should hold one or two widths")
+    h = [b // (2 * step) for b in bg]
+    if h[0] < 1:
+        raise ValueError(f"invalid background ({bg[0]}): at least two steps")
+    if len(h) == 2 and h[1] < h[0]:
+        raise ValueError(f"invalid background ({bg}): the second width should not be below the first")
+    if max(h) + m > IFS_MAX_REACH:
+        raise ValueError(f"invalid background ({bg}): half of it and the window exceed {IFS_MAX_REACH} steps")
+    if not 0.0 < float(alpha) < 1.0:
+        raise ValueError(f"invalid alpha ({alpha}): it should lie inside (0, 1)")
+    if mean_length is not None and not 1 <= int(mean_length) <= 65535:
+        raise ValueError(f"invalid mean_length ({mean_length}): 1 .. 65535")
+    if int(min_count) < 0:
+        raise ValueError(f"invalid min_count ({min_count}): it should not be negative")
+    if join is not None and not 1 <= int(join) <= IFS_MAX_JOIN:
+        raise ValueError(f"invalid join ({join}): 1 .. {IFS_MAX_JOIN}")
+    if int(min_windows) < 1:
+        raise ValueError(f"invalid min_windows ({min_windows}): at least 1")
+    if min_length is not None and int(min_length) < 0:
+        raise ValueError(f"invalid min_length ({min_length}): it should not be negative")
+    if max_length is not None and int(max_length) < 0:
+        raise ValueError(f"invalid max_length ({max_length}): it should not be negative")
+    if min_length is not None and max_length is not None and int(min_length) > int(max_length):
+        raise ValueError(f"min_length ({min_length}) exceeds max_length ({max_length})")
+    if chrom_sizes is None and not _is_alignment_file(input_file):
+        raise ValueError("chrom_sizes must be specified for BED/Fragment files")
+    return m, h[0], (h[1] if len(h) == 2 else 0)
+
+
+def frag_hotspots(input_file, interval_file=None, chrom_sizes=None, output_file=None, windows_file=None, summary_file=None,
+                  step: int = 20, window: int = 200, background=(5000, 10000), alpha: float = 1e-5, mean_length=None,
+                  use_global: bool = True, min_count: int = 0, join=None, min_windows: int = 1, min_length=None,
+                  max_length=None, quality_threshold: int = 30, workers=None, verbose=False) -> IfsHotspots:
+    """Fragmentation hotspots from the Integrated Fragmentation Score (Zhou et al. 2022, CRAG): per interval of
+    ``interval_file`` (BED), or over every contig of the input when there is none, the windows of ``window`` bases sliding
+    by ``step`` whose IFS - ``n * (1 + mean fragment length in the window / mean fragment length on the contig)`` over the
+    fragments with their midpoint in the window - is significantly low (Poisson lower tail at level ``alpha``) against
+    the mean IFS of the ``background`` widths around the window (one or two, in bases; half-widths ``b // (2 * step)``
+    steps) and, with ``use_global``, of the contig; called windows at most ``join`` steps apart (default
+    ``window // step + 200 // step``) merge into a hotspot, and a hotspot of fewer than ``min_windows`` windows is dropped.
+    The rule is stated in ``include/ftk.h``, "IFS hotspots"; the test becomes an integer comparison with the table of
+    ``ifs_thresholds(alpha)``.  Every window is scored and tested on the GPU, contig by contig as the input is decoded
+    (``Engine.ifs_hotspots``): only the called windows come back to the host.
+
+    ``mean_length``: ``L`` of the rule; ``None``: per contig, the rounded mean length of the passing fragments with a
+    midpoint on the contig.  That mean and the contig's mean IFS (``global_mean``) come from one reduction on the GPU
+    (``Engine.ifs_totals``).  Backgrounds read the contig, not the interval.  BED intervals are clipped to the contig.
+
+    Chromosome sizes: the BAM header, else the ``chrom_sizes`` file, else ``ValueError``.  An interval on a contig the
+    input lacks raises ``ValueError``, as in ``frag.coverage``.  ``output_file`` (``.bed`` / ``.bed.gz``):
+    ``writers.write_hotspot_rows``; ``windows_file``: ``writers.write_hotspot_windows``; ``summary_file`` (``.tsv`` /
+    ``.tsv.gz``): ``writers.write_hotspot_summary``."""
+    import os
+    import sys
+    import time
+
+    from . import writers
+    from .source import ContigFeed
+    m, h1, h2 = _check_hotspots_args(input_file, chrom_sizes, output_file, windows_file, summary_file, step, window, background,
+                                     alpha, mean_length, min_count, join, min_windows, min_length, max_length)
+    t0 = time.time()
+    step = int(step)
+    join = max(m + 200 // step, 1) if join is None else int(join)
+    sizes = None if _is_alignment_file(input_file) else chrom_sizes_to_dict(chrom_sizes)
+    whole = interval_file is None
+    intervals = [] if whole else get_intervals(interval_file)
+    by_contig: dict[str, list[int]] = {}
+    for i, iv in enumerate(intervals):
+        by_contig.setdefault(iv[0], []).append(i)
+    if sizes is not None:
+        for c in by_contig:
+            if c not in sizes:
+                raise ValueError(f"{c} is not in chrom_sizes")
+    filt = dict(min_length=min_length, max_length=max_length, quality_threshold=quality_threshold)
+    thr = ifs_thresholds(alpha)
+    hot_parts, win_parts, stat_rows, mean_rows, glob_rows = [], [], {}, {}, {}
+    left = dict(by_contig)
+    eng = get_engine()
+    feed = ContigFeed(input_file, workers, names=None if whole else list(by_contig))
+    try:
+        for src, c in feed:
+            if whole:
+                if sizes is not None and c not in sizes:
+                    raise ValueError(f"{c} is not in chrom_sizes")
+                idx = [len(intervals)]
+            else:
+                idx = left.pop(c, None)
+                if idx is None:
+                    continue
+            size = int(src.lengths[c]) if sizes is None else int(sizes[c])
+            if whole:
+                intervals.append((c, 0, size, "."))
+            a = np.clip(np.array([intervals[i][1] for i in idx], np.int64), 0, size)
+            b = np.clip(np.array([intervals[i][2] for i in idx], np.int64), a, size)
+            L, gm = mean_length, 0
+            if L is None or use_global:
+                N, S = eng.ifs_totals(src.key(c), size, **filt)
+                if L is None:
+                    L = min(max((2 * S + N) // (2 * N), 1), 65535) if N else 1
+                L = int(L)
+                n_bins = -(-size // step)
+                if use_global and n_bins:
+                    gm = (N * L + S) * m * 1024 // (n_bins * L)
+            L = int(L)
+            win, hot, stats = eng.ifs_hotspots(src.key(c), a, b, size, step=step, m=m, mean_length=L, h1=h1, h2=h2,
+                                               min_count=int(min_count), thresholds=thr, global_mean=gm, join=join,
+                                               min_windows=int(min_windows), **filt)
+            which = np.asarray(idx, np.int64)
+            hp = np.zeros(len(hot), HOTSPOT_DTYPE)
+            hp["interval"] = which[hot["run"]]
+            for name in HOTSPOT_DTYPE.names[1:]:
+                hp[name] = hot[name]
+            wp = np.zeros(len(win), IFS_WINDOW_DTYPE)
+            wp["interval"] = which[win["run"]]
+            wp["start"] = win["pos"]
+            wp["stop"] = np.minimum(win["pos"] + m * step, size)
+            for name in IFS_WINDOW_DTYPE.names[3:]:
+                wp[name] = win[name]
+            hot_parts.append(hp)
+            win_parts.append(wp)
+            stat_rows.update(zip(idx, stats))
+            mean_rows.update((i, L) for i in idx)
+            glob_rows.update((i, gm) for i in idx)
+            if verbose:
+                sys.stderr.write(f"frag_hotspots: {c}: {len(idx)} intervals, L = {L}, {len(wp)} called windows, {len(hp)} hotspots\n")
+        src = feed.finish()
+    except BaseException:
+        feed.close()
+        raise
+    for c in left:  # contigs the file does not hold: the ValueError of frag.coverage
+        src.require(c)
+    hotspots = np.concatenate(hot_parts) if hot_parts else np.zeros(0, HOTSPOT_DTYPE)
+    hotspots = hotspots[np.argsort(hotspots["interval"], kind="stable")]  # (an interval's records are in start order already)
+    windows = np.concatenate(win_parts) if win_parts else np.zeros(0, IFS_WINDOW_DTYPE)
+    windows = windows[np.argsort(windows["interval"], kind="stable")]
+    n = len(intervals)
+    stats = np.array([stat_rows[i] for i in range(n)], np.int64).reshape(n, 6)
+    res = IfsHotspots(intervals, hotspots, windows, stats, np.array([mean_rows[i] for i in range(n)], np.int64),
+                      np.array([glob_rows[i] for i in range(n)], np.int64), step, m)
+    if output_file is not None:
+        writers.write_hotspot_rows(os.fspath(output_file), res)
+    if windows_file is not None:
+        writers.write_hotspot_windows(os.fspath(windows_file), res)
+    if summary_file is not None:
+        writers.write_hotspot_summary(os.fspath(summary_file), res)
+    if verbose:
+        sys.stderr.write(f"frag_hotspots: {n} intervals, {len(hotspots)} hotspots in {time.time() - t0:.3f} s\n")
     return res
 
 

@@ -449,3 +449,66 @@ def write_preferred_end_summary(output_file: str, ends) -> None:
         rows.append("\t".join([str(c), str(a), str(b), str(name)] + [str(int(x)) for x in stats]
                               + ["nan" if share != share else format(float(share), ".6g")]) + "\n")
     _emit(output_file, "".join(rows), (".tsv",), (".tsv.gz",), message)
+
+
+def _ifs_floats(res, rec):
+    """``(ifs, expected, neglog10_p)`` of IFS records (hotspot summits or called windows): ``ifs = I / L``, ``expected =
+    B m / (n_b L)`` - the first background's mean IFS per window - and ``p = P(X <= floor(I / L))`` under a Poisson model
+    of that mean (``scipy.special.gammaincc``), computed here from the integers for the records alone."""
+    from scipy.special import gammaincc
+    L = res.mean_length[rec["interval"]].astype(np.float64)
+    ifs = rec["ifs"].astype(np.float64) / L
+    expected = rec["bg1"].astype(np.float64) * res.window_bins / (rec["nb1"].astype(np.float64) * L)
+    q = (rec["ifs"] // res.mean_length[rec["interval"]]).astype(np.float64)
+    with np.errstate(divide="ignore"):
+        score = -np.log10(gammaincc(q + 1.0, expected))
+    return ifs.tolist(), expected.tolist(), score.tolist()
+
+
+def write_hotspot_rows(output_file: str, res) -> None:
+    """One row per hotspot of a ``utils.IfsHotspots``, ordered by interval and start, without a header line: ``contig start
+    stop name n_windows summit ifs count expected neglog10_p`` - ``name`` the interval's name (``.`` in whole-contig mode),
+    ``summit`` the start of the hotspot's called window of smallest IFS, and that window's ``ifs = I / L``, fragment
+    ``count``, ``expected = B m / (n_b L)`` (the mean IFS per window of its first background) and Poisson lower tail of
+    ``floor(ifs)``, the floats with six significant digits; ``.bed`` as text, ``.bed.gz`` as gzip."""
+    message = "output_file should have .bed or .bed.gz as suffix"
+    if not output_file.endswith((".bed", ".bed.gz")):
+        raise ValueError(message)
+    hot = res.hotspots
+    rows = []
+    if len(hot):
+        for (i, a, b, nw, summit, _, count, _, _), x, m, s in zip(hot.tolist(), *_ifs_floats(res, hot)):
+            c, _, _, name = res.intervals[i]
+            rows.append(f"{c}\t{a}\t{b}\t{name}\t{nw}\t{summit}\t{format(x, '.6g')}\t{count}\t{format(m, '.6g')}\t{format(s + 0.0, '.6g')}\n")
+    _emit(output_file, "".join(rows), (".bed",), (".bed.gz",), message)
+
+
+def write_hotspot_windows(output_file: str, res) -> None:
+    """One row per called window of a ``utils.IfsHotspots``, ordered by interval and start, without a header line: ``contig
+    start stop name count ifs expected neglog10_p`` with the columns of ``write_hotspot_rows``; ``.bed`` as text,
+    ``.bed.gz`` as gzip."""
+    message = "windows_file should have .bed or .bed.gz as suffix"
+    if not output_file.endswith((".bed", ".bed.gz")):
+        raise ValueError(message)
+    win = res.windows
+    rows = []
+    if len(win):
+        for (i, a, b, count, *_), x, m, s in zip(win.tolist(), *_ifs_floats(res, win)):
+            c, _, _, name = res.intervals[i]
+            rows.append(f"{c}\t{a}\t{b}\t{name}\t{count}\t{format(x, '.6g')}\t{format(m, '.6g')}\t{format(s + 0.0, '.6g')}\n")
+    _emit(output_file, "".join(rows), (".bed",), (".bed.gz",), message)
+
+
+def write_hotspot_summary(output_file: str, res) -> None:
+    """One row per interval of a ``utils.IfsHotspots``, in its order, behind the header line ``contig start stop name
+    mean_length global_mean windows tested called hotspots dropped bases``: the interval, its contig's ``L`` and mean IFS
+    per window (six significant digits; ``nan`` when the test did not use it) and the six counters of the rule; ``.tsv``
+    as text, ``.tsv.gz`` as gzip."""
+    message = "summary_file should have .tsv or .tsv.gz as suffix"
+    if not output_file.endswith((".tsv", ".tsv.gz")):
+        raise ValueError(message)
+    rows = ["contig\tstart\tstop\tname\tmean_length\tglobal_mean\twindows\ttested\tcalled\thotspots\tdropped\tbases\n"]
+    for (c, a, b, name), L, gm, stats in zip(res.intervals, res.mean_length, res.global_mean, res.stats):
+        rows.append("\t".join([str(c), str(a), str(b), str(name), str(int(L)), "nan" if gm == 0 else format(int(gm) / 1024.0, ".6g")]
+                              + [str(int(x)) for x in stats]) + "\n")
+    _emit(output_file, "".join(rows), (".tsv",), (".tsv.gz",), message)

@@ -973,6 +973,87 @@ int ftk_preferred_ends(ftk_ctx* ctx, int contig_id, const int64_t* iv_start, con
                        int32_t min_len, int32_t max_len, int32_t mapq_min, int32_t** run, int64_t** pos, int32_t** kind,
                        int32_t** count, int64_t** total, int32_t** n_w, int64_t* n_calls, int64_t* stats /* n_iv * 6, host */);
 
+/* ---- IFS hotspots: fragmentation hotspot calls from the Integrated Fragmentation Score ----------------------
+ * The Integrated Fragmentation Score of Zhou et al. 2022 (CRAG): in a window sliding over the contig, IFS = n * (1 + mean
+ * fragment length in the window / mean fragment length on the chromosome) over the fragments whose midpoint lies in the
+ * window; a window whose IFS is significantly LOW against its local backgrounds and the chromosome is called, and
+ * neighbouring called windows are merged into a hotspot.  Every window is scored and tested on the device and only the
+ * called windows reach the host - about one in 10^4 at alpha = 1e-5.
+ *
+ * THE RULE.  Everything in it is an integer.
+ *  1. Bins: with step = s, 1 <= s <= 65535, n_bins = ceil(chrom_size / s) and bin j is [j s, (j + 1) s); the last bin
+ *     may be short.  A fragment [start, end) of the resident contig passes with mapq >= mapq_min, min_len <= end - start
+ *     <= max_len (FTK_LEN_OPEN = no bound) and end > start.  Its midpoint is (start + end) >> 1 (the convention of
+ *     ftk_site_profile); midpoints outside [0, chrom_size) do not exist.  c(j) counts the midpoints in bin j, l(j) sums
+ *     their fragments' lengths, and with the caller's mean length L = mean_len, 1 <= L <= 65535, i(j) = c(j) L + l(j) is
+ *     the bin's IFS in units of 1 / L.  The read1 columns of a BAM contig play no part.
+ *  2. Windows: m bins per window, 1 <= m <= FTK_IFS_MAX_WINDOW_BINS.  Window k, 0 <= k <= n_bins - m, is bins k .. k + m -
+ *     1 and spans [k s, min((k + m) s, chrom_size)).  n(k) = the sum of c and I(k) = the sum of i over those bins;
+ *     q(k) = I(k) / L (floor) is the integer IFS.  A contig with n_bins < m has no window.  Window k belongs to interval
+ *     [a, b) iff a <= k s and its span's end <= b.  Intervals [iv_start[i], iv_stop[i]) may overlap, touch, be empty or
+ *     come in any order; each is a run of its own.
+ *  3. Backgrounds: two half-widths in bins, h1 >= 1 and h2 (h2 == 0: the second is off; otherwise h2 >= h1), with
+ *     max(h1, h2) + m <= FTK_IFS_MAX_REACH.  For half-width h the background of window k is bins [max(k - h, 0),
+ *     min(k + m - 1 + h, n_bins - 1)], n_b their number and B the sum of i over them, the window's own bins included.
+ *     The background reads the contig and never stops at the bounds of the interval being called: whether a window is
+ *     called does not depend on how the caller cuts the contig.
+ *  4. Decision: with the caller's table thr[0 .. n_thr), 1 <= n_thr <= FTK_IFS_MAX_THR, every entry < 2^32 - thr[q] a
+ *     mean IFS per window in units of 2^-10 - a window is TESTED iff n(k) >= min_count (min_count >= 0), and a tested
+ *     window is CALLED iff, with q = q(k) and in unsigned 64-bit arithmetic,
+ *         q < n_thr   and   t = thr[q] != 0   and
+ *         B_h m 2^10 >= t n_b_h L   for every active h   and
+ *         (global_mean == 0  or  t <= global_mean)      (global_mean >= 0: the caller's, in the same 2^-10 units).
+ *     There is no shared last entry: a window with q >= n_thr is never significantly low.  Nothing overflows: the
+ *     device counters are 32 bits wide and sums are only ever differences of prefix sums, so every B < 2^32 is exact (the
+ *     caller keeps a background's IFS below 2^32 / L); the left side is < 2^32 2^6 2^10 = 2^48 and the right side
+ *     < 2^32 2^12 2^16 = 2^60.  thr[q] is the smallest mean at which an IFS of q is significantly low.  The library
+ *     does not interpret the table (finaletoolkit_amd.utils.ifs_thresholds builds the Poisson one).
+ *  5. A called window is (run, pos = k s, count = n, ifs = I, bg1 = B_h1, nb1 = n_b_h1, bg2, nb2): run the interval's
+ *     number; bg2 and nb2 are 0 when h2 is off.  Called windows come ordered by (run, pos).
+ *  6. Hotspots: two called windows k1 < k2 of one run with no called window between them belong to one hotspot iff
+ *     k2 - k1 <= join, 1 <= join <= FTK_IFS_MAX_JOIN.  A hotspot of fewer than min_windows (>= 1) called windows is
+ *     dropped.  A hotspot is (run, start = k_first s, stop = the span end of k_last, n_windows, summit, ifs, count, bg1,
+ *     nb1): summit is the pos of its called window of smallest I, the leftmost of equals, and ifs, count, bg1 and nb1
+ *     are that window's.  Hotspots come ordered by (run, start), never join across runs, and are the same however the
+ *     library tiles and batches a run.
+ *  7. Per interval six int64 counters, in this order: windows, tested windows, called windows, hotspots kept, hotspots
+ *     dropped, bases covered by the kept hotspots (the bases of the union of their [start, stop)).
+ *
+ * ftk_ifs_hotspots: the eight called-window columns (w_*, *n_windows entries each) and the nine hotspot columns (h_*,
+ * *n_hotspots entries each) come back in host blocks of the library's (NULL when there is none), to be released with
+ * ftk_buffer_free; stats: n_iv * 6 counters in host memory.  The intervals are walked tile by tile in batches whose
+ * device scratch is bounded, so a whole chromosome may be one interval; the merge runs on the host as the called windows
+ * come home.  The call reads the packed (length, mapq) column of the contig where the filter allows it and the wide
+ * columns otherwise, with the same bytes either way.
+ * FTK_ERR_INVALID: a NULL argument (the interval and stats arrays may be NULL when n_iv == 0), device pointers for the
+ * interval, table or stats arrays, n_iv < 0, an interval with start < 0, stop < start or stop > chrom_size, chrom_size
+ * outside [0, 2^30), step, m, mean_len, h1, h2, min_count, n_thr, a table entry, global_mean, join or min_windows outside
+ * the ranges above.  FTK_ERR_NO_CONTIG: an unknown contig.  A failing call hands out no block and writes no counter.
+ * n_iv == 0, empty intervals and an empty contig are valid: nothing called, zero counters.
+ *
+ * ftk_ifs_track: the per-window form without the test - n(k) (int32) and I(k) (int64) of the windows of interval i, in
+ * window order, at n_out / ifs_out[out_offset[i] ...] (the arrays: host or device; out_offset: host, n_iv non-negative
+ * entries, laid out by the caller as for the interval form of the WPS call).  The same errors as above for the arguments
+ * it has.
+ * ftk_ifs_totals: the number and the length sum of the passing fragments with a midpoint in [0, chrom_size), reduced on
+ * the device - what a caller needs for mean_len and global_mean. */
+#define FTK_IFS_MAX_WINDOW_BINS 64
+#define FTK_IFS_MAX_REACH 1024
+#define FTK_IFS_MAX_THR 4096
+#define FTK_IFS_MAX_JOIN 1024
+int ftk_ifs_hotspots(ftk_ctx* ctx, int contig_id, const int64_t* iv_start, const int64_t* iv_stop, int64_t n_iv,
+                     int64_t chrom_size, int32_t step, int32_t m, int32_t mean_len, int32_t h1, int32_t h2, int32_t min_count,
+                     const uint64_t* thr, int32_t n_thr, int64_t global_mean, int32_t join, int32_t min_windows, int32_t min_len,
+                     int32_t max_len, int32_t mapq_min, int32_t** w_run, int64_t** w_pos, int32_t** w_count, int64_t** w_ifs,
+                     int64_t** w_bg1, int32_t** w_nb1, int64_t** w_bg2, int32_t** w_nb2, int64_t* n_windows, int32_t** h_run,
+                     int64_t** h_start, int64_t** h_stop, int32_t** h_n_windows, int64_t** h_summit, int64_t** h_ifs,
+                     int32_t** h_count, int64_t** h_bg1, int32_t** h_nb1, int64_t* n_hotspots, int64_t* stats /* n_iv * 6, host */);
+int ftk_ifs_track(ftk_ctx* ctx, int contig_id, const int64_t* iv_start, const int64_t* iv_stop, int64_t n_iv,
+                  const int64_t* out_offset, int64_t chrom_size, int32_t step, int32_t m, int32_t mean_len, int32_t min_len,
+                  int32_t max_len, int32_t mapq_min, int32_t* n_out, int64_t* ifs_out);
+int ftk_ifs_totals(ftk_ctx* ctx, int contig_id, int64_t chrom_size, int32_t min_len, int32_t max_len, int32_t mapq_min,
+                   int64_t* n_frags, int64_t* len_sum);
+
 /* ---- multi-GPU (SURVEY 8-e, 8-b's export list) -------------------------------------------------
  * One process and one ftk_ctx per GPU.  Contigs / genome runs are dealt to the ranks by the host and every window,
  * bin and base depends on its own contig's fragments only, so the data path has no collective.  What remains are the

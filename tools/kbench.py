@@ -13,7 +13,10 @@ the route there was before (ftk_wps_intervals to host memory + a numpy matrix pr
 KBENCH=peaks: nucleosome calls on the same regions - the two peak passes alone on a resident adjusted track, ftk_wps_adjust on the
 same runs, the fused call, and the route there was before (scores and adjusted track carried through host memory).
 KBENCH=prefends: preferred ends of the whole contig at h = 500 and h = 2048, combined and split, beside ftk_depth_runs and
-ftk_cleavage of the same region (the same tile skeleton), with the call's byte floor."""
+ftk_cleavage of the same region (the same tile skeleton), with the call's byte floor.
+KBENCH=hotspots: IFS hotspots of the whole contig at the defaults (20-base step, 200-base windows, 5 kb / 10 kb backgrounds,
+alpha = 1e-5) - the whole call, the totals reduction, the per-window track into device arrays - beside preferred ends combined
+at h = 500 on the same contig, with the call's byte floor."""
 import os
 import sys
 
@@ -628,6 +631,65 @@ if "prefends" in which:
                 print(f"  {len(got[h, mode][0])} calls; {t / t_runs:.2f} x depth runs, {t / t_cl:.2f} x cleavage; halo factor x 2 = "
                       f"{2 * halo:.2f}; {floor / t:.1%} of the byte floor ({floor * 1e3:.3f} ms)", flush=True)
     print("prefends checksum:", {f"{h}/{mode}": (len(c), st.sum(axis=0).tolist()) for (h, mode), (c, st) in sorted(got.items())})
+if "hotspots" in which:
+    # IFS hotspots of the whole contig as one interval: the whole call (per batch of tiles the count pass, the scan, one
+    # read-back, the write pass, the called windows copied to host blocks, the merge on the host) at the defaults, the totals
+    # reduction that gives mean_length and global_mean, and the per-window track into device arrays; beside them preferred
+    # ends combined at h = 500, the nearest kernel with the same candidate traffic.  Byte floor, computed as for prefends:
+    # the columns of every candidate of a tile of 4 096 windows (81 920 bases; counted from the sorted starts) times
+    # (tile + 2 (h2 + m)) / tile for the halo, read by both passes, plus 44 B per called window written.
+    import time
+
+    from finaletoolkit_amd import _lib as L
+    from finaletoolkit_amd.utils import ifs_thresholds, preferred_end_thresholds
+    STEP, M, H1, H2 = 20, 10, 125, 250
+    TILE = L.HOTSPOTS_TILE * STEP
+    lmax = eng.info("c")[1]
+    hs = s.cpu().numpy().astype(np.int64)
+    t0 = np.arange(0, size, TILE, dtype=np.int64)
+    t1 = np.minimum(t0 + TILE, size)
+    cand = int((np.searchsorted(hs, ((t1 >> 9) + 1) << 9, side="left")
+                - np.searchsorted(hs, (np.maximum(t0 - lmax, 0) >> 9) << 9, side="left")).sum())
+    col_bytes = 6 if eng.frags_packed("c") else 9
+    thr = ifs_thresholds(1e-5)
+    pthr = preferred_end_thresholds(0.01)
+    N, S = eng.ifs_totals("c", size)
+    Lm = max((2 * S + N) // (2 * N), 1)
+    gm = (N * Lm + S) * M * 1024 // (-(-size // STEP) * Lm)
+    got = {}
+
+    def call():
+        got["hot"] = eng.ifs_hotspots("c", [0], [size], size, step=STEP, m=M, mean_length=Lm, h1=H1, h2=H2, thresholds=thr,
+                                      global_mean=gm)
+
+    def wall(fn, name):
+        fn()
+        torch.cuda.synchronize()
+        ts = []
+        for _ in range(max(reps // 4, 3)):
+            a = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            ts.append(time.perf_counter() - a)
+        ts = np.array(ts)
+        print(f"{name:34s} median {np.median(ts) * 1e3:9.3f} ms  min {ts.min() * 1e3:9.3f} ms", flush=True)
+        return float(np.median(ts))
+
+    print(f"hotspots: {n} fragments, L = {Lm}, global mean {gm / 1024:.3f}, {len(t0)} tiles, {cand} candidates ({cand / n:.2f} per "
+          f"fragment), {col_bytes} B per candidate", flush=True)
+    for _ in range(2):  # twice: the spread between the two passes is the noise
+        t_pe = wall(lambda: eng.preferred_ends("c", [0], [size], size, half=500, mode="combined", thresholds=pthr),
+                    "preferred ends h=500 combined")
+        t_tot = wall(lambda: eng.ifs_totals("c", size), "IFS totals")
+        t_trk = wall(lambda: eng.ifs_track("c", [0], [size], size, step=STEP, m=M, mean_length=Lm, device=True), "IFS track (device arrays)")
+        t = wall(call, "IFS hotspots (whole call)")
+        win, hot, stats = got["hot"]
+        halo = (L.HOTSPOTS_TILE + 2 * (H2 + M)) / L.HOTSPOTS_TILE
+        floor = (2 * col_bytes * cand * halo + 44 * len(win)) / (bench.HBM_PEAK_GBS * 1e9)
+        print(f"  {len(win)} called windows, {len(hot)} hotspots; {t / t_pe:.2f} x preferred ends; halo factor x 2 = {2 * halo:.2f}; "
+              f"{floor / t:.1%} of the byte floor ({floor * 1e3:.3f} ms); totals {t_tot * 1e3:.3f} ms, track {t_trk * 1e3:.3f} ms",
+              flush=True)
+    print("hotspots checksum:", len(got["hot"][0]), len(got["hot"][1]), got["hot"][2].tolist())
 if "gc" in which:
     rng = np.random.default_rng(6)
     packed = rng.integers(0, 256, (size + 3) // 4, dtype=np.uint8)
