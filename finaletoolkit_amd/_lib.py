@@ -37,14 +37,14 @@ PEAKS_MAX_GAP = 63  # FTK_PEAKS_MAX_GAP
 PEAKS_TILE = 1024  # kPeaksTile: positions per workgroup of the mark pass
 PREFENDS_MAX_HALF = 2048  # FTK_PREFENDS_MAX_HALF
 PREFENDS_MAX_THR = 4096  # FTK_PREFENDS_MAX_THR
-PREFENDS_TILE = 4096  # kPrefTile: positions per workgroup of the preferred-end passes
-PREFENDS_BATCH_TILES = 4096  # kPrefBatchTiles: tiles the call plans, counts and writes at a time
+PREFENDS_TILE = 4096  # kCallTile: positions per workgroup of the preferred-end passes
+PREFENDS_BATCH_TILES = 4096  # kCallBatchTiles: tiles the call plans, counts and writes at a time
 IFS_MAX_WINDOW_BINS = 64  # FTK_IFS_MAX_WINDOW_BINS
 IFS_MAX_REACH = 1024  # FTK_IFS_MAX_REACH
 IFS_MAX_THR = 4096  # FTK_IFS_MAX_THR
 IFS_MAX_JOIN = 1024  # FTK_IFS_MAX_JOIN
-HOTSPOTS_TILE = 4096  # kIfsTile: windows per workgroup of the hotspot passes
-HOTSPOTS_BATCH_TILES = 4096  # kIfsBatchTiles: tiles the call plans, counts and writes at a time
+HOTSPOTS_TILE = 4096  # kCallTile: windows per workgroup of the hotspot passes
+HOTSPOTS_BATCH_TILES = 4096  # kCallBatchTiles: tiles the call plans, counts and writes at a time
 SPECTRUM_TILE = 16 << 10  # kSpectrumLdsSamples: a run of up to this many samples is folded out of LDS, a longer one from memory
 POLICY = {"midpoint": 0, "any": 1}
 POLICY_FETCH = 2  # no intersect test: the index query alone (AlignmentWrapper.fetch)

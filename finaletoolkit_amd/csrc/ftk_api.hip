@@ -27,6 +27,7 @@
 #include "ftk_host.h"
 #include "ftk_inflate.h"
 #include "ftk_kernels.h"
+#include "ftk_tilecall.h"
 
 using namespace ftk;
 
@@ -162,6 +163,168 @@ class Scratch {
     Buf bufs_[kMaxBufs];
     int n_ = 0;
 };
+
+struct SyncOnExit {  // pageable staging of this frame may be in flight on any way out
+    ftk_ctx* ctx;
+    ~SyncOnExit() { (void)hipStreamSynchronize(ctx->stream); }
+};
+
+// Records on their way home as N columns: host blocks of the library's that grow with the rows, the caller's
+// (ftk_buffer_free) once the call has succeeded and give() has handed them over.  Whatever is not given away is freed.
+template <int N>
+struct HostCols {
+    const size_t* size;  // bytes per row, column by column
+    void* p[N] = {};
+    int64_t n = 0, cap = 0;
+    explicit HostCols(const size_t* sizes) : size(sizes) {}
+    ~HostCols() { for (void* q : p) free(q); }
+    bool grow(int64_t more) {
+        if (n + more <= cap) return true;
+        const int64_t want = std::max<int64_t>(n + more, 2 * cap);
+        for (int k = 0; k < N; ++k) {
+            void* q = realloc(p[k], (size_t)want * size[k]);
+            if (!q) return false;
+            p[k] = q;
+        }
+        cap = want;
+        return true;
+    }
+    template <class T>
+    T* col(int k) { return static_cast<T*>(p[k]); }
+    // `more` rows of the device columns dev[0 .. N) behind row n (grow(more) has made the room).  Waits for the stream
+    // whatever happens: copies into these blocks may be in flight.  Returns the first error.
+    hipError_t fetch(hipStream_t stream, const void* const* dev, int64_t more) {
+        hipError_t e = hipSuccess;
+        for (int k = 0; k < N && e == hipSuccess; ++k)
+            e = hipMemcpyAsync((char*)p[k] + (size_t)n * size[k], dev[k], (size_t)more * size[k], hipMemcpyDeviceToHost, stream);
+        const hipError_t e2 = hipStreamSynchronize(stream);
+        if (e == hipSuccess && e2 == hipSuccess) n += more;
+        return e != hipSuccess ? e : e2;
+    }
+    // the blocks to the caller's pointers (which hold NULL) when there is a row
+    void give(void** const* out, int64_t* n_out) {
+        if (n == 0) return;
+        for (int k = 0; k < N; ++k) {
+            *out[k] = p[k];
+            p[k] = nullptr;
+        }
+        *n_out = n;
+    }
+};
+
+// May a call with one mapq cut and one pair of length bounds read lq instead of end and mapq?  (FTK_PACKED=0 keeps every
+// launch on the wide columns, as in ftk_kernels.hip.)
+bool call_reads_packed(const ContigView& cv, int mapq_min, int min_len, int max_len) {
+    static const int allow = getenv("FTK_PACKED") ? atoi(getenv("FTK_PACKED")) : 1;
+    PackedCall c;
+    c.has_lq = cv.lq != nullptr;
+    c.wps = true;  // as a WPS launch has them
+    c.wps_q = mapq_min;
+    c.wps_min = min_len;
+    c.wps_max = max_len;
+    return allow != 0 && packed_call_ok(c);
+}
+
+int check_intervals_in_contig(ftk_ctx* ctx, const int64_t* iv_start, const int64_t* iv_stop, int64_t n_iv, int64_t chrom_size) {
+    for (int64_t i = 0; i < n_iv; ++i)
+        if (iv_start[i] < 0 || iv_stop[i] < iv_start[i] || iv_stop[i] > chrom_size)
+            return fail(ctx, FTK_ERR_INVALID, "interval %lld [%lld, %lld) does not lie in [0, %lld)", (long long)i, (long long)iv_start[i],
+                        (long long)iv_stop[i], (long long)chrom_size);
+    return FTK_OK;
+}
+
+// The host side of the tile-call skeleton (ftk_tilecall.h), shared by ftk_preferred_ends and ftk_ifs_hotspots.
+// walk(push_tile) names the call's tiles in order, push_tile(t0, len, run) each; they run in batches of kCallBatchTiles:
+// count pass and scan, ONE read-back (the tiles' n_stats counters and the batch's calls), room for exactly those calls,
+// write pass, the calls home behind the rows `home` holds.  The plan of a batch has one size, so the scratch a whole
+// chromosome takes is that of its fullest batch.  The rule's pieces:
+//   table, table_bytes    the host table the kernels read; its device copy opens the plan
+//   count(d_table, nt, pl)           launches the count pass and the scan of nt tiles
+//   write(nt, pl, cols)              launches the write pass, call r of the batch at row r of the device columns cols[0 .. N)
+//   tally(run, len, counters) -> n   adds a tile's counters to its interval's sums and returns the tile's calls, of which
+//                                    a position has at most calls_per_pos.  The sums are kept on the host: a count pass
+//                                    that has to run again, because the scratch moved when the calls' room was reserved,
+//                                    counts nothing twice.
+//   came_home(from, to) -> bool      rows [from, to) of `home` have arrived (false: out of host memory)
+template <int N, class Count, class Write, class Tally, class Came, class Walk>
+int run_tile_call(ftk_ctx* ctx, const void* table, size_t table_bytes, size_t n_stats, int calls_per_pos, HostCols<N>& home,
+                  Count&& count, Write&& write, Tally&& tally, Came&& came_home, Walk&& walk) {
+    constexpr size_t B = kCallBatchTiles;
+    const size_t plan_bytes = align_up(table_bytes) + 4 * align_up(B * 4) + align_up(B * n_stats * 4) + align_up(8);
+    std::vector<int32_t> t0, tlen, trun;  // the batch's tiles
+    std::vector<uint32_t> tstats;
+    SyncOnExit wait{ctx};
+    TileCallPlan pl{};
+    // the batch's plan at the scratch base, the count pass and the scan
+    auto count_pass = [&](Arena& a) -> int {
+        const size_t nt = t0.size();
+        char* d_table = a.take<char>(table_bytes);
+        int32_t* d_t0 = a.take<int32_t>(B);
+        int32_t* d_len = a.take<int32_t>(B);
+        int32_t* d_run = a.take<int32_t>(B);
+        pl.off = a.take<int32_t>(B);
+        pl.stats = a.take<uint32_t>(B * n_stats);
+        pl.total = a.take<int64_t>(1);
+        pl.tile_t0 = d_t0;
+        pl.tile_len = d_len;
+        pl.tile_run = d_run;
+        HIPCHK(ctx, hipMemcpyAsync(d_table, table, table_bytes, hipMemcpyHostToDevice, ctx->stream));
+        HIPCHK(ctx, hipMemcpyAsync(d_t0, t0.data(), nt * 4, hipMemcpyHostToDevice, ctx->stream));
+        HIPCHK(ctx, hipMemcpyAsync(d_len, tlen.data(), nt * 4, hipMemcpyHostToDevice, ctx->stream));
+        HIPCHK(ctx, hipMemcpyAsync(d_run, trun.data(), nt * 4, hipMemcpyHostToDevice, ctx->stream));
+        count(d_table, (int)nt, pl);
+        HIPCHK(ctx, hipGetLastError());
+        return FTK_OK;
+    };
+    auto run_batch = [&]() -> int {
+        const size_t nt = t0.size();
+        if (int e = reserve_scratch(ctx, plan_bytes)) return e;
+        {
+            Arena a(ctx);
+            if (int e = count_pass(a)) return e;
+        }
+        int64_t n = 0;
+        tstats.resize(nt * n_stats);
+        HIPCHK(ctx, hipMemcpyAsync(tstats.data(), pl.stats, nt * n_stats * 4, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(ctx, hipMemcpyAsync(&n, pl.total, 8, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+        int64_t seen = 0;
+        for (size_t t = 0; t < nt; ++t) seen += tally(trun[t], tlen[t], &tstats[t * n_stats]);
+        if (n != seen || n > (int64_t)nt * kCallTile * calls_per_pos) return fail(ctx, FTK_ERR_HIP, "the call count %lld is out of range", (long long)n);
+        if (n == 0) return FTK_OK;
+        size_t room = plan_bytes;
+        for (int k = 0; k < N; ++k) room += align_up((size_t)n * home.size[k]);
+        const void* before = ctx->scratch;
+        if (int e = reserve_scratch(ctx, room)) return e;
+        Arena a(ctx);
+        if (ctx->scratch != before) {  // the scratch moved: the plan went with the old block
+            if (int e = count_pass(a)) return e;
+        } else {
+            a.off = plan_bytes;
+        }
+        void* cols[N];
+        for (int k = 0; k < N; ++k) cols[k] = a.take<char>((size_t)n * home.size[k]);
+        write((int)nt, pl, cols);
+        HIPCHK(ctx, hipGetLastError());
+        if (!home.grow(n)) return fail(ctx, FTK_ERR_OOM, "out of host memory");
+        HIPCHK(ctx, home.fetch(ctx->stream, cols, n));
+        if (!came_home(home.n - n, home.n)) return fail(ctx, FTK_ERR_OOM, "out of host memory");
+        return FTK_OK;
+    };
+    auto push_tile = [&](int64_t first, int64_t len, int64_t run) -> int {
+        t0.push_back((int32_t)first);
+        tlen.push_back((int32_t)len);
+        trun.push_back((int32_t)run);
+        if (t0.size() < B) return FTK_OK;
+        const int rc = run_batch();
+        t0.clear();
+        tlen.clear();
+        trun.clear();
+        return rc;
+    };
+    if (int rc = walk(push_tile)) return rc;
+    return t0.empty() ? FTK_OK : run_batch();
+}
 
 // The five window-feature outputs of a FeatureRequest / FusedParams, declared in one place (NULL: that feature is off).
 // want_hist without `hist`: the statistics-only call, whose histogram and overflow stay in the scratch.

@@ -87,25 +87,17 @@ int ftk_depth_runs(ftk_ctx* ctx, int contig_id, int64_t start, int64_t stop, int
     for (auto& d : d_run) d = a.take<int32_t>((size_t)total);
     launch_depth_write(ctx->stream, c->v, p, n_tiles, rp, d_run[0], d_run[1], d_run[2]);
     HIPCHK(ctx, hipGetLastError());
-    int32_t* h_run[3] = {nullptr, nullptr, nullptr};
-    hipError_t e = hipSuccess;
-    bool oom = false;
-    for (int k = 0; k < 3; ++k) {
-        h_run[k] = (int32_t*)malloc((size_t)total * 4);
-        if (!h_run[k]) oom = true;
-        else if (e == hipSuccess) e = hipMemcpyAsync(h_run[k], d_run[k], (size_t)total * 4, hipMemcpyDeviceToHost, ctx->stream);
-    }
-    const hipError_t e2 = hipStreamSynchronize(ctx->stream);  // (always: copies into this frame's blocks may be in flight)
-    if (oom || e != hipSuccess || e2 != hipSuccess) {
+    static constexpr size_t kSize[3] = {4, 4, 4};
+    void** const out[3] = {(void**)run_start, (void**)run_end, (void**)run_depth};
+    HostCols<3> home{kSize};
+    SyncOnExit wait{ctx};  // (always: copies into this frame's blocks may be in flight)
+    if (!home.grow(total)) return fail(ctx, FTK_ERR_OOM, "out of host memory");
+    const void* dev[3] = {d_run[0], d_run[1], d_run[2]};
+    if (const hipError_t e = home.fetch(ctx->stream, dev, total)) {
         (void)hipGetLastError();
-        for (auto h : h_run) free(h);
-        if (oom) return fail(ctx, FTK_ERR_OOM, "out of host memory");
-        return fail(ctx, FTK_ERR_HIP, "copy of the runs failed: %s", hipGetErrorString(e != hipSuccess ? e : e2));
+        return fail(ctx, FTK_ERR_HIP, "copy of the runs failed: %s", hipGetErrorString(e));
     }
-    *run_start = h_run[0];
-    *run_end = h_run[1];
-    *run_depth = h_run[2];
-    *n_runs = total;
+    home.give(out, n_runs);
     return FTK_OK;
 }
 

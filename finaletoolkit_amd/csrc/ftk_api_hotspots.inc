@@ -1,26 +1,13 @@
 // Part of ftk_api.hip's translation unit (#included there behind the preferred-ends part) - IFS hotspots:
 // `ftk_ifs_hotspots`, `ftk_ifs_track` and `ftk_ifs_totals` over the kernels of ftk_hotspots.hip.  The hotspot call checks
-// its arguments, then walks the intervals' tiles of windows in batches of kIfsBatchTiles exactly as ftk_preferred_ends
-// walks its tiles of positions: count pass and scan, ONE read-back (the tiles' counters and the batch's calls), room for
-// exactly those calls, write pass, the called windows home into host blocks that grow batch by batch.  The merge (rule 6)
-// is one linear pass on the host over the called windows as they come home; the hotspot that is open at the end of a
-// batch stays open into the next, so hotspots do not depend on where a batch or a tile ends.
+// its arguments and hands its rule's pieces to run_tile_call, which walks the intervals' tiles of windows in batches and
+// brings the called windows home.  The merge (rule 6) is one linear pass on the host over the called windows as they come
+// home; the hotspot that is open at the end of a batch stays open into the next, so hotspots do not depend on where a
+// batch or a tile ends.
 #include "ftk_hotspots.h"
 
 extern "C++" {  // (templates, in a file that is included inside ftk_api.hip's extern "C" block)
 namespace {
-
-// May the call read lq instead of end and mapq?  (FTK_PACKED=0 keeps every launch on the wide columns, as in ftk_kernels.hip.)
-bool ifs_packed(const ContigView& cv, const IfsParams& p) {
-    static const int allow = getenv("FTK_PACKED") ? atoi(getenv("FTK_PACKED")) : 1;
-    PackedCall c;
-    c.has_lq = cv.lq != nullptr;
-    c.wps = true;  // one mapq cut and one pair of length bounds, as a WPS launch has
-    c.wps_q = p.mapq_min;
-    c.wps_min = p.min_len;
-    c.wps_max = p.max_len;
-    return allow != 0 && packed_call_ok(c);
-}
 
 // the windows of interval [a, b): k_lo .. k_hi (rule 2; none: k_hi < k_lo)
 void ifs_interval_windows(int64_t a, int64_t b, int64_t chrom, int64_t s, int64_t m, int64_t n_bins, int64_t* k_lo, int64_t* k_hi) {
@@ -48,40 +35,9 @@ int ifs_open(ftk_ctx* ctx, int contig_id, int64_t chrom_size, int32_t step, int3
     p->max_len = cp.max_len;
     p->mapq_min = cp.mapq_min;
     p->lmax = cp.lmax;
-    p->packed = ifs_packed((*c)->v, *p);
+    p->packed = call_reads_packed((*c)->v, p->mapq_min, p->min_len, p->max_len);
     return FTK_OK;
 }
-
-int ifs_check_intervals(ftk_ctx* ctx, const int64_t* iv_start, const int64_t* iv_stop, int64_t n_iv, int64_t chrom_size) {
-    for (int64_t i = 0; i < n_iv; ++i)
-        if (iv_start[i] < 0 || iv_stop[i] < iv_start[i] || iv_stop[i] > chrom_size)
-            return fail(ctx, FTK_ERR_INVALID, "interval %lld [%lld, %lld) does not lie in [0, %lld)", (long long)i, (long long)iv_start[i],
-                        (long long)iv_stop[i], (long long)chrom_size);
-    return FTK_OK;
-}
-
-// N growing host blocks, the caller's once the call has succeeded
-template <int N>
-struct IfsHostCols {
-    const size_t* size;
-    void* p[N] = {};
-    int64_t n = 0, cap = 0;
-    explicit IfsHostCols(const size_t* sizes) : size(sizes) {}
-    ~IfsHostCols() { for (void* q : p) free(q); }
-    bool grow(int64_t more) {
-        if (n + more <= cap) return true;
-        const int64_t want = std::max<int64_t>(n + more, 2 * cap);
-        for (int k = 0; k < N; ++k) {
-            void* q = realloc(p[k], (size_t)want * size[k]);
-            if (!q) return false;
-            p[k] = q;
-        }
-        cap = want;
-        return true;
-    }
-    template <class T>
-    T* col(int k) { return static_cast<T*>(p[k]); }
-};
 
 constexpr size_t kIfsWinSize[8] = {4, 8, 4, 8, 8, 4, 8, 4};     // run, pos, count, ifs, bg1, nb1, bg2, nb2
 constexpr size_t kIfsHotSize[9] = {4, 8, 8, 4, 8, 8, 4, 8, 4};  // run, start, stop, n_windows, summit, ifs, count, bg1, nb1
@@ -89,7 +45,7 @@ constexpr size_t kIfsHotSize[9] = {4, 8, 8, 4, 8, 8, 4, 8, 4};  // run, start, s
 // Rule 6 over the called windows in (run, pos) order, fed a stretch at a time.
 struct IfsMerge {
     int64_t step, m, chrom, join, min_windows;
-    IfsHostCols<9> hot{kIfsHotSize};
+    HostCols<9> hot{kIfsHotSize};
     int64_t* sums;  // [n_iv][6]
     bool open = false;
     int32_t run = 0, n = 0, best_count = 0, best_nb1 = 0;
@@ -148,11 +104,6 @@ struct IfsMerge {
     }
 };
 
-struct IfsSyncOnExit {  // pageable staging of this frame may be in flight on any way out
-    ftk_ctx* ctx;
-    ~IfsSyncOnExit() { (void)hipStreamSynchronize(ctx->stream); }
-};
-
 }  // namespace
 }  // extern "C++"
 
@@ -193,7 +144,7 @@ int ftk_ifs_hotspots(ftk_ctx* ctx, int contig_id, const int64_t* iv_start, const
         if (thr[k] >= (1ULL << 32)) return fail(ctx, FTK_ERR_INVALID, "threshold %d reaches 2^32", k);
     ContigData* c;
     IfsParams p{};
-    int rc = ifs_check_intervals(ctx, iv_start, iv_stop, n_iv, chrom_size);
+    int rc = check_intervals_in_contig(ctx, iv_start, iv_stop, n_iv, chrom_size);
     if (rc) return rc;
     if ((rc = ifs_open(ctx, contig_id, chrom_size, step, m, mean_len, min_len, max_len, mapq_min, &c, &p))) return rc;
     p.h1 = h1;
@@ -204,125 +155,54 @@ int ftk_ifs_hotspots(ftk_ctx* ctx, int contig_id, const int64_t* iv_start, const
     p.global_mean = (unsigned long long)global_mean;
     HIPCHK(ctx, hipSetDevice(ctx->device));
 
-    constexpr size_t B = kIfsBatchTiles;
-    const size_t plan_bytes = align_up((size_t)n_thr * 4) + 4 * align_up(B * 4) + align_up(B * kIfsStats * 4) + align_up(8);
-    std::vector<uint32_t> thr32(thr, thr + n_thr);
-    std::vector<int32_t> t0, tlen, trun;  // the batch's tiles (pageable staging: every way out waits for the stream)
-    std::vector<uint32_t> tstats;
+    const std::vector<uint32_t> thr32(thr, thr + n_thr);
     std::vector<int64_t> sums((size_t)n_iv * 6, 0);
-    IfsHostCols<8> home{kIfsWinSize};
+    HostCols<8> home{kIfsWinSize};
     IfsMerge merge{step, m, chrom_size, join, min_windows};
     merge.sums = sums.data();
-    IfsSyncOnExit wait{ctx};
-    IfsPlan pl{};
-    // the batch's plan at the scratch base, the count pass and the scan
-    auto count_pass = [&](Arena& a) -> int {
-        const size_t nt = t0.size();
-        uint32_t* d_thr = a.take<uint32_t>((size_t)n_thr);
-        int32_t* d_t0 = a.take<int32_t>(B);
-        int32_t* d_len = a.take<int32_t>(B);
-        int32_t* d_run = a.take<int32_t>(B);
-        pl.off = a.take<int32_t>(B);
-        pl.stats = a.take<uint32_t>(B * kIfsStats);
-        pl.total = a.take<int64_t>(1);
-        pl.tile_k0 = d_t0;
-        pl.tile_len = d_len;
-        pl.tile_run = d_run;
-        p.thr = d_thr;
-        HIPCHK(ctx, hipMemcpyAsync(d_thr, thr32.data(), (size_t)n_thr * 4, hipMemcpyHostToDevice, ctx->stream));
-        HIPCHK(ctx, hipMemcpyAsync(d_t0, t0.data(), nt * 4, hipMemcpyHostToDevice, ctx->stream));
-        HIPCHK(ctx, hipMemcpyAsync(d_len, tlen.data(), nt * 4, hipMemcpyHostToDevice, ctx->stream));
-        HIPCHK(ctx, hipMemcpyAsync(d_run, trun.data(), nt * 4, hipMemcpyHostToDevice, ctx->stream));
-        launch_ifs_count(ctx->stream, c->v, p, (int)nt, pl);
-        HIPCHK(ctx, hipGetLastError());
-        return FTK_OK;
-    };
-    auto run_batch = [&]() -> int {
-        const size_t nt = t0.size();
-        if (int e = reserve_scratch(ctx, plan_bytes)) return e;
-        {
-            Arena a(ctx);
-            if (int e = count_pass(a)) return e;
-        }
-        int64_t n = 0;
-        tstats.resize(nt * kIfsStats);
-        HIPCHK(ctx, hipMemcpyAsync(tstats.data(), pl.stats, nt * kIfsStats * 4, hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(ctx, hipMemcpyAsync(&n, pl.total, 8, hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-        int64_t seen = 0;
-        for (size_t t = 0; t < nt; ++t) {
-            int64_t* st = &sums[(size_t)trun[t] * 6];
-            st[0] += tlen[t];
-            st[1] += tstats[t * kIfsStats];
-            st[2] += tstats[t * kIfsStats + 1];
-            seen += tstats[t * kIfsStats + 1];
-        }
-        if (n != seen || n > (int64_t)nt * kIfsTile) return fail(ctx, FTK_ERR_HIP, "the call count %lld is out of range", (long long)n);
-        if (n == 0) return FTK_OK;
-        const void* before = ctx->scratch;
-        if (int e = reserve_scratch(ctx, plan_bytes + 4 * align_up((size_t)n * 4) + 4 * align_up((size_t)n * 8))) return e;
-        Arena a(ctx);
-        if (ctx->scratch != before) {  // the scratch moved: the plan went with the old block
-            if (int e = count_pass(a)) return e;
-        } else {
-            a.off = plan_bytes;
-        }
-        IfsOut o{};
-        o.run = a.take<int32_t>((size_t)n);
-        o.pos = a.take<int64_t>((size_t)n);
-        o.count = a.take<int32_t>((size_t)n);
-        o.ifs = a.take<int64_t>((size_t)n);
-        o.bg1 = a.take<int64_t>((size_t)n);
-        o.nb1 = a.take<int32_t>((size_t)n);
-        o.bg2 = a.take<int64_t>((size_t)n);
-        o.nb2 = a.take<int32_t>((size_t)n);
-        launch_ifs_write(ctx->stream, c->v, p, (int)nt, pl, o);
-        HIPCHK(ctx, hipGetLastError());
-        if (!home.grow(n)) return fail(ctx, FTK_ERR_OOM, "out of host memory");
-        const void* dev[8] = {o.run, o.pos, o.count, o.ifs, o.bg1, o.nb1, o.bg2, o.nb2};
-        for (int k = 0; k < 8; ++k) {
-            const size_t sz = kIfsWinSize[k];
-            HIPCHK(ctx, hipMemcpyAsync((char*)home.p[k] + (size_t)home.n * sz, dev[k], (size_t)n * sz, hipMemcpyDeviceToHost, ctx->stream));
-        }
-        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-        if (!merge.feed(home.col<int32_t>(0), home.col<int64_t>(1), home.col<int32_t>(2), home.col<int64_t>(3), home.col<int64_t>(4),
-                        home.col<int32_t>(5), home.n, home.n + n))
-            return fail(ctx, FTK_ERR_OOM, "out of host memory");
-        home.n += n;
-        return FTK_OK;
-    };
-    for (int64_t i = 0; i < n_iv; ++i) {
-        int64_t k_lo, k_hi;
-        ifs_interval_windows(iv_start[i], iv_stop[i], chrom_size, step, m, p.n_bins, &k_lo, &k_hi);
-        for (int64_t a = k_lo; a <= k_hi; a += kIfsTile) {
-            t0.push_back((int32_t)a);
-            tlen.push_back((int32_t)std::min<int64_t>(k_hi + 1 - a, kIfsTile));
-            trun.push_back((int32_t)i);
-            if (t0.size() == B) {
-                if ((rc = run_batch())) return rc;
-                t0.clear();
-                tlen.clear();
-                trun.clear();
+    rc = run_tile_call(
+        ctx, thr32.data(), (size_t)n_thr * 4, kIfsStats, 1, home,
+        [&](const void* d_thr, int nt, const TileCallPlan& pl) {
+            p.thr = static_cast<const unsigned*>(d_thr);
+            launch_ifs_count(ctx->stream, c->v, p, nt, pl);
+        },
+        [&](int nt, const TileCallPlan& pl, void* const* col) {
+            IfsOut o{};
+            o.run = (int32_t*)col[0];
+            o.pos = (int64_t*)col[1];
+            o.count = (int32_t*)col[2];
+            o.ifs = (int64_t*)col[3];
+            o.bg1 = (int64_t*)col[4];
+            o.nb1 = (int32_t*)col[5];
+            o.bg2 = (int64_t*)col[6];
+            o.nb2 = (int32_t*)col[7];
+            launch_ifs_write(ctx->stream, c->v, p, nt, pl, o);
+        },
+        [&](int32_t iv, int32_t len, const uint32_t* ts) {
+            int64_t* st = &sums[(size_t)iv * 6];
+            st[0] += len;
+            st[1] += ts[0];
+            st[2] += ts[1];
+            return (int64_t)ts[1];
+        },
+        [&](int64_t from, int64_t to) {
+            return merge.feed(home.col<int32_t>(0), home.col<int64_t>(1), home.col<int32_t>(2), home.col<int64_t>(3), home.col<int64_t>(4),
+                              home.col<int32_t>(5), from, to);
+        },
+        [&](auto&& push_tile) {
+            for (int64_t i = 0; i < n_iv; ++i) {
+                int64_t k_lo, k_hi;
+                ifs_interval_windows(iv_start[i], iv_stop[i], chrom_size, step, m, p.n_bins, &k_lo, &k_hi);
+                for (int64_t a = k_lo; a <= k_hi; a += kCallTile)
+                    if (int e = push_tile(a, std::min<int64_t>(k_hi + 1 - a, kCallTile), i)) return e;
             }
-        }
-    }
-    if (!t0.empty() && (rc = run_batch())) return rc;
+            return (int)FTK_OK;
+        });
+    if (rc) return rc;
     if (!merge.close()) return fail(ctx, FTK_ERR_OOM, "out of host memory");
     if (n_iv > 0) memcpy(stats, sums.data(), sums.size() * 8);
-    if (home.n > 0) {
-        for (int k = 0; k < 8; ++k) {
-            *wout[k] = home.p[k];
-            home.p[k] = nullptr;
-        }
-        *n_windows = home.n;
-    }
-    if (merge.hot.n > 0) {
-        for (int k = 0; k < 9; ++k) {
-            *hout[k] = merge.hot.p[k];
-            merge.hot.p[k] = nullptr;
-        }
-        *n_hotspots = merge.hot.n;
-    }
+    home.give(wout, n_windows);
+    merge.hot.give(hout, n_hotspots);
     return FTK_OK;
 }
 
@@ -336,7 +216,7 @@ int ftk_ifs_track(ftk_ctx* ctx, int contig_id, const int64_t* iv_start, const in
         return fail(ctx, FTK_ERR_INVALID, "interval and offset arrays must be host arrays");
     ContigData* c;
     IfsParams p{};
-    int rc = ifs_check_intervals(ctx, iv_start, iv_stop, n_iv, chrom_size);
+    int rc = check_intervals_in_contig(ctx, iv_start, iv_stop, n_iv, chrom_size);
     if (rc) return rc;
     if ((rc = ifs_open(ctx, contig_id, chrom_size, step, m, mean_len, min_len, max_len, mapq_min, &c, &p))) return rc;
     std::vector<int32_t> t0, tlen;  // (pageable staging: finish(true) waits for the uploads)
@@ -348,9 +228,9 @@ int ftk_ifs_track(ftk_ctx* ctx, int contig_id, const int64_t* iv_start, const in
         if (out_offset[i] < 0) return fail(ctx, FTK_ERR_INVALID, "out_offset[%lld] is negative", (long long)i);
         if (k_hi < k_lo) continue;
         total = std::max(total, out_offset[i] + (k_hi + 1 - k_lo));
-        for (int64_t a = k_lo; a <= k_hi; a += kIfsTile) {
+        for (int64_t a = k_lo; a <= k_hi; a += kCallTile) {
             t0.push_back((int32_t)a);
-            tlen.push_back((int32_t)std::min<int64_t>(k_hi + 1 - a, kIfsTile));
+            tlen.push_back((int32_t)std::min<int64_t>(k_hi + 1 - a, kCallTile));
             tout.push_back(out_offset[i] + (a - k_lo));
         }
     }
@@ -359,7 +239,7 @@ int ftk_ifs_track(ftk_ctx* ctx, int contig_id, const int64_t* iv_start, const in
     if (t0.size() > (size_t)INT32_MAX) return fail(ctx, FTK_ERR_INVALID, "too many tiles");
     HIPCHK(ctx, hipSetDevice(ctx->device));
     const size_t nt = t0.size();
-    IfsSyncOnExit wait{ctx};
+    SyncOnExit wait{ctx};
     Scratch s(ctx);
     IfsOut o{};
     int32_t *d_t0 = nullptr, *d_len = nullptr;
@@ -377,8 +257,8 @@ int ftk_ifs_track(ftk_ctx* ctx, int contig_id, const int64_t* iv_start, const in
     HIPCHK(ctx, hipMemcpyAsync(d_t0, t0.data(), nt * 4, hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(ctx, hipMemcpyAsync(d_len, tlen.data(), nt * 4, hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(ctx, hipMemcpyAsync(d_out, tout.data(), nt * 8, hipMemcpyHostToDevice, ctx->stream));
-    IfsPlan pl{};
-    pl.tile_k0 = d_t0;
+    TileCallPlan pl{};
+    pl.tile_t0 = d_t0;
     pl.tile_len = d_len;
     pl.tile_out = d_out;
     launch_ifs_track(ctx->stream, c->v, p, (long long)nt, pl, o);

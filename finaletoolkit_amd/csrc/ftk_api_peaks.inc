@@ -98,30 +98,17 @@ struct PeaksCall {
         if (bad) return fail(ctx, FTK_ERR_INVALID, "a score is not finite");
         if (n > (uint64_t)b.out_cap) return fail(ctx, FTK_ERR_HIP, "the call count %llu is out of range", (unsigned long long)n);
         if (n == 0) return FTK_OK;
-        void* host[6] = {};
+        static constexpr size_t kSize[6] = {4, 8, 8, 8, 8, 8};
         const void* dev[6] = {b.o_run, b.o_start, b.o_stop, b.o_summit, b.o_height, b.o_area};
-        hipError_t e = hipSuccess;
-        bool oom = false;
-        for (int k = 0; k < 6; ++k) {
-            const size_t bytes = (size_t)n * (k ? 8 : 4);
-            host[k] = malloc(bytes);
-            if (!host[k]) oom = true;
-            else if (e == hipSuccess) e = hipMemcpyAsync(host[k], dev[k], bytes, hipMemcpyDeviceToHost, ctx->stream);
-        }
-        const hipError_t e2 = hipStreamSynchronize(ctx->stream);  // (always: copies into this frame's blocks may be in flight)
-        if (oom || e != hipSuccess || e2 != hipSuccess) {
+        void** const out[6] = {(void**)run, (void**)start, (void**)stop, (void**)summit, (void**)height, (void**)area};
+        HostCols<6> home{kSize};
+        SyncOnExit wait{ctx};  // (always: copies into this frame's blocks may be in flight)
+        if (!home.grow((int64_t)n)) return fail(ctx, FTK_ERR_OOM, "out of host memory");
+        if (const hipError_t e = home.fetch(ctx->stream, dev, (int64_t)n)) {
             (void)hipGetLastError();
-            for (void* h : host) free(h);
-            if (oom) return fail(ctx, FTK_ERR_OOM, "out of host memory");
-            return fail(ctx, FTK_ERR_HIP, "copy of the calls failed: %s", hipGetErrorString(e != hipSuccess ? e : e2));
+            return fail(ctx, FTK_ERR_HIP, "copy of the calls failed: %s", hipGetErrorString(e));
         }
-        *run = (int32_t*)host[0];
-        *start = (int64_t*)host[1];
-        *stop = (int64_t*)host[2];
-        *summit = (int64_t*)host[3];
-        *height = (double*)host[4];
-        *area = (double*)host[5];
-        *n_calls = (int64_t)n;
+        home.give(out, n_calls);
         return FTK_OK;
     }
 };

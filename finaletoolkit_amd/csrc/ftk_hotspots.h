@@ -1,18 +1,13 @@
 // Launchers of the IFS hotspot kernels in ftk_hotspots.hip (internal).  The rule: include/ftk.h, "IFS hotspots".
 #pragma once
 
-#include "ftk_internal.h"
+#include "ftk_tilecall.h"
 
 namespace ftk {
 
-// windows per workgroup (HOTSPOTS_TILE of _lib.py)
-constexpr int kIfsTile = 4096;
 // the two halo instantiations, in bins: the 5 kb / 10 kb backgrounds at a 20-base step (h2 + m = 260) and
 // FTK_IFS_MAX_REACH
 constexpr int kIfsHaloSmall = 512, kIfsHaloLarge = 1024;
-// tiles of one batch: what the single workgroup of the scan walks, and the bound of a batch's plan in the scratch
-constexpr int kIfsBatchTiles = 4096;
-constexpr int kIfsScanWidth = 1024;
 // per-tile counters of the count pass: tested windows, called windows
 constexpr int kIfsStats = 2;
 // workgroups of the totals kernel, one (count, length sum) pair each
@@ -37,17 +32,6 @@ struct IfsParams {
     int packed;  // read lq instead of end and mapq (packed_call_ok said so)
 };
 
-// One batch of tiles: what the passes hand each other, one entry per tile.
-struct IfsPlan {
-    const int32_t* tile_k0;   // first window
-    const int32_t* tile_len;  // windows (1 .. kIfsTile)
-    const int32_t* tile_run;  // its interval's number
-    const int64_t* tile_out;  // track pass: where the tile's first window goes in the outputs
-    uint32_t* stats;          // [n_tiles][kIfsStats] (count pass)
-    int32_t* off;             // exclusive prefix sum of the tiles' called windows (scan)
-    int64_t* total;           // one word: called windows of the batch (scan)
-};
-
 struct IfsOut {
     // called windows (write pass)
     int32_t* run;
@@ -64,11 +48,11 @@ struct IfsOut {
 };
 
 // the count pass and the scan of its counts
-void launch_ifs_count(hipStream_t s, const ContigView& cv, const IfsParams& p, int n_tiles, const IfsPlan& pl);
+void launch_ifs_count(hipStream_t s, const ContigView& cv, const IfsParams& p, int n_tiles, const TileCallPlan& pl);
 // the write pass: called window r of the batch at out.*[r]
-void launch_ifs_write(hipStream_t s, const ContigView& cv, const IfsParams& p, int n_tiles, const IfsPlan& pl, const IfsOut& out);
+void launch_ifs_write(hipStream_t s, const ContigView& cv, const IfsParams& p, int n_tiles, const TileCallPlan& pl, const IfsOut& out);
 // the track pass: n and I of every window of every tile
-void launch_ifs_track(hipStream_t s, const ContigView& cv, const IfsParams& p, long long n_tiles, const IfsPlan& pl, const IfsOut& out);
+void launch_ifs_track(hipStream_t s, const ContigView& cv, const IfsParams& p, long long n_tiles, const TileCallPlan& pl, const IfsOut& out);
 // passing fragments with a midpoint on the contig: kIfsTotalsBlocks pairs (count, length sum) at partial[2 b], [2 b + 1]
 void launch_ifs_totals(hipStream_t s, const ContigView& cv, const IfsParams& p, unsigned long long* partial);
 

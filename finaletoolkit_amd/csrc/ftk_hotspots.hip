@@ -1,13 +1,13 @@
 // IFS fragmentation hotspots (ftk_ifs_hotspots, ftk_ifs_track): the rule of include/ftk.h, "IFS hotspots".
 //
-// One workgroup of 256 threads per tile of kIfsTile windows of one interval, on the tile skeleton of prefends_kernel:
-// the candidates come from the position index, the midpoints are binned with LDS atomics, a DPP wave scan with a
-// cross-wave carry turns the bins into prefix sums.  What differs: the arrays hold BINS of `step` bases, not bases - two
-// 32-bit tracks, c (midpoints) and i = c * L + l (the bin's IFS in units of 1 / L) - over the tile's kIfsTile bins and a
-// halo of HALO >= max(h1, h2) + m bins on either side, so that a window's n and I (m bins) and both backgrounds B (m + 2 h
-// bins) are prefix differences inside the tile's own LDS.  Entry a of a track is bin k0 - HALO + a (k0: the tile's first
-// window); window k0 + i is entries HALO + i .. HALO + i + m - 1.  Bins outside the contig hold no midpoint, so a
-// background needs no clipping here - only n_b is clipped.
+// One workgroup of 256 threads per tile of kCallTile windows of one interval, on the tile-call skeleton of
+// ftk_tilecall.h: the candidates come from the position index, the midpoints are binned with LDS atomics, a DPP wave scan
+// with a cross-wave carry turns the bins into prefix sums.  The kernel's own: the arrays hold BINS of `step` bases, not
+// bases - two 32-bit tracks, c (midpoints) and i = c * L + l (the bin's IFS in units of 1 / L) - over the tile's kCallTile
+// bins and a halo of HALO >= max(h1, h2) + m bins on either side, so that a window's n and I (m bins) and both
+// backgrounds B (m + 2 h bins) are prefix differences inside the tile's own LDS.  Entry a of a track is bin
+// k0 - HALO + a (k0: the tile's first window); window k0 + i is entries HALO + i .. HALO + i + m - 1.  Bins outside the
+// contig hold no midpoint, so a background needs no clipping here - only n_b is clipped.
 //
 // Candidates: a midpoint lies in the bins the tile reads, [first, last), only when first - lmax < start < last (lmax: the
 // longest fragment the filter admits - a midpoint may belong to a fragment that starts far in front of the tile).
@@ -22,37 +22,23 @@
 // Counters are 32 bits wide: a background total below 2^32 is exact, because prefix sums are only ever subtracted
 // (unsigned arithmetic wraps; the scan's additions are plain 32-bit adds).  LDS per workgroup and occupancy of the two
 // instantiations: DESIGN.md, "IFS hotspots".
-#include "ftk_device.h"
 #include "ftk_hotspots.h"
 
 namespace ftk {
 
 namespace {
 
-// the columns of fragment i, off the packed word or the wide columns
-__device__ __forceinline__ void ifs_fetch(const ContigView& cv, int packed, int i, int& fs, int& fe, int& q) {
-    fs = cv.start[i];
-    if (packed) {
-        const int w = cv.lq[i];
-        fe = fs + (w >> kLqBits);
-        q = w & kLqMapqSat;
-    } else {
-        fe = cv.end[i];
-        q = cv.mapq[i];
-    }
-}
-
 template <int HALO>
-__global__ __launch_bounds__(256) void ifs_kernel(ContigView cv, IfsParams p, IfsPlan pl, IfsOut o, int pass) {
-    constexpr int T = kIfsTile, W = T + 2 * HALO, NP = W / 1024, NT = 2, R = T / 256;
+__global__ __launch_bounds__(256) void ifs_kernel(ContigView cv, IfsParams p, TileCallPlan pl, IfsOut o, int pass) {
+    constexpr int T = kCallTile, W = T + 2 * HALO, NP = W / 1024, NT = 2, R = T / 256;
     static_assert(W % 1024 == 0 && R * 4 == 64, "the scan takes 1024 entries a trip; wave 0 scans the 64 (round, wave) counts");
     __shared__ __attribute__((aligned(16))) unsigned trk[NT][W];  // c and i per bin, then their inclusive prefix sums
     __shared__ unsigned wtot[NT][NP][4];
     __shared__ unsigned red[4][kIfsStats];
     __shared__ int wcnt[R * 4], wpre[R * 4];
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int tid = threadIdx.x, wv = tid >> 6;
     const long long k = blockIdx.x;
-    const int k0 = pl.tile_k0[k], len_t = pl.tile_len[k], m = p.m;
+    const int k0 = pl.tile_t0[k], len_t = pl.tile_len[k], m = p.m;
     const int base = k0 - HALO;  // bin of entry 0 (may be negative)
     // the entries this tile reads: 1 <= a_lo, a_hi <= W - 1 (HALO >= reach + m)
     const int a_lo = HALO - p.reach, a_hi = HALO + len_t + m - 1 + p.reach;
@@ -72,60 +58,9 @@ __global__ __launch_bounds__(256) void ifs_kernel(ContigView cv, IfsParams p, If
             atomicAdd(&trk[1][a], p.L + (unsigned)len);
         }
     };
-    // the columns of the first candidates requested in one batch (see depth_kernel)
-    constexpr int PF = 4;
-    int ps[PF], pe[PF], pq[PF];
-#pragma unroll
-    for (int u = 0; u < PF; ++u) {
-        const int i = lo + tid + 256 * u;
-        ps[u] = pe[u] = pq[u] = 0;
-        if (i < hi) ifs_fetch(cv, p.packed, i, ps[u], pe[u], pq[u]);
-    }
-#pragma unroll
-    for (int u = 0; u < PF; ++u)
-        if (lo + tid + 256 * u < hi) apply(ps[u], pe[u], pq[u]);
-    for (int i = lo + PF * 256 + tid; i < hi; i += 256) {
-        int fs, fe, q;
-        ifs_fetch(cv, p.packed, i, fs, fe, q);
-        apply(fs, fe, q);
-    }
+    tile_candidates(cv, p.packed, lo, hi, tid, apply);
     __syncthreads();
-    // thread tid holds the entries j * 1024 + 4 * tid .. + 3 of every trip j
-    {
-        uint4 v[NT][NP];
-        unsigned ex[NT][NP];
-#pragma unroll
-        for (int t = 0; t < NT; ++t)
-#pragma unroll
-            for (int j = 0; j < NP; ++j) {
-                v[t][j] = trk4[t * (W / 4) + j * 256 + tid];
-                const unsigned s = v[t][j].x + v[t][j].y + v[t][j].z + v[t][j].w;
-                const unsigned incl = (unsigned)wave_incl_scan_dpp((int)s);
-                ex[t][j] = incl - s;
-                if (lane == 63) wtot[t][j][wv] = incl;
-            }
-        __syncthreads();
-#pragma unroll
-        for (int t = 0; t < NT; ++t) {
-            unsigned all = 0;
-#pragma unroll
-            for (int j = 0; j < NP; ++j) {
-                unsigned carry = all;
-#pragma unroll
-                for (int w2 = 0; w2 < 4; ++w2) {
-                    const unsigned tt = wtot[t][j][w2];
-                    if (w2 < wv) carry += tt;
-                    all += tt;
-                }
-                uint4 q4;
-                q4.x = carry + ex[t][j] + v[t][j].x;
-                q4.y = q4.x + v[t][j].y;
-                q4.z = q4.y + v[t][j].z;
-                q4.w = q4.z + v[t][j].w;
-                trk4[t * (W / 4) + j * 256 + tid] = q4;
-            }
-        }
-    }
+    tile_tracks_scan(trk, wtot, tid);
     __syncthreads();
     if (pass == kIfsTrack) {
         const long long at = pl.tile_out[k];
@@ -177,26 +112,15 @@ __global__ __launch_bounds__(256) void ifs_kernel(ContigView cv, IfsParams p, If
         st[1] += res == 2;
         flags |= (unsigned)(res == 2) << r;
         const int c = __popcll(__ballot(res == 2));
-        if (lane == 0) wcnt[r * 4 + wv] = c;
+        tile_rank_count(wcnt, r, c, tid);
     }
     if (pass == kIfsCount) {
-#pragma unroll
-        for (int c = 0; c < kIfsStats; ++c) {
-            const unsigned s = wave_sum_u32(st[c]);
-            if (lane == 0) red[wv][c] = s;
-        }
-        __syncthreads();
-        if (tid < kIfsStats) pl.stats[k * kIfsStats + tid] = red[0][tid] + red[1][tid] + red[2][tid] + red[3][tid];
+        tile_stats_reduce(st, red, pl.stats, k, tid);
         return;
     }
-    __syncthreads();
-    if (wv == 0) {
-        const int x = wcnt[lane];
-        wpre[lane] = wave_incl_scan_dpp(x) - x;
-    }
-    __syncthreads();
+    tile_rank_scan(wcnt, wpre, tid);
     const long long off = pl.off[k];
-    const unsigned long long lower = (1ull << lane) - 1;
+    const unsigned long long lower = tile_lower_lanes(tid);
 #pragma unroll
     for (int r = 0; r < R; ++r) {
         const bool called = flags >> r & 1;
@@ -221,30 +145,9 @@ __global__ __launch_bounds__(256) void ifs_kernel(ContigView cv, IfsParams p, If
     }
 }
 
-// One workgroup, kIfsScanWidth tiles a trip: the exclusive prefix sum of the tiles' calls and their total.
-__global__ __launch_bounds__(kIfsScanWidth) void ifs_scan_kernel(IfsPlan pl, int n_tiles) {
-    constexpr int NW = kIfsScanWidth / 64;
-    __shared__ int wt[NW];
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    long long carry = 0;
-    for (int c0 = 0; c0 < n_tiles; c0 += kIfsScanWidth) {
-        const int i = c0 + tid;
-        const int x = i < n_tiles ? (int)pl.stats[(long long)i * kIfsStats + 1] : 0;
-        const int incl = wave_incl_scan_dpp(x);
-        if (lane == 63) wt[wv] = incl;
-        __syncthreads();
-        int before = 0, all = 0;
-#pragma unroll
-        for (int w2 = 0; w2 < NW; ++w2) {
-            const int tt = wt[w2];
-            if (w2 < wv) before += tt;
-            all += tt;
-        }
-        if (i < n_tiles) pl.off[i] = (int32_t)(carry + before + incl - x);
-        carry += all;
-        __syncthreads();
-    }
-    if (tid == 0) *pl.total = carry;
+// the exclusive prefix sum of the tiles' called windows and their total
+__global__ __launch_bounds__(kCallScanWidth) void ifs_scan_kernel(TileCallPlan pl, int n_tiles) {
+    tile_offsets_scan(n_tiles, pl.off, pl.total, [&](long long i) { return pl.stats[i * kIfsStats + 1]; });
 }
 
 // Passing fragments with a midpoint on the contig, their number and their lengths' sum: every workgroup strides over the
@@ -255,7 +158,7 @@ __global__ __launch_bounds__(256) void ifs_totals_kernel(ContigView cv, IfsParam
     unsigned long long cnt = 0, sum = 0;
     for (long long i = (long long)blockIdx.x * 256 + tid; i < cv.n; i += (long long)gridDim.x * 256) {
         int fs, fe, q;
-        ifs_fetch(cv, p.packed, (int)i, fs, fe, q);
+        tile_fetch(cv, p.packed, (int)i, fs, fe, q);
         const int len = fe - fs;
         if (q < p.mapq_min || len < p.min_len || len > p.max_len || len <= 0) continue;
         const long long mid = ((long long)fs + fe) >> 1;
@@ -270,7 +173,7 @@ __global__ __launch_bounds__(256) void ifs_totals_kernel(ContigView cv, IfsParam
     if (tid < 2) partial[2 * blockIdx.x + tid] = red[0][tid] + red[1][tid] + red[2][tid] + red[3][tid];
 }
 
-void launch_any(hipStream_t s, const ContigView& cv, const IfsParams& p, long long n_tiles, const IfsPlan& pl, const IfsOut& out,
+void launch_any(hipStream_t s, const ContigView& cv, const IfsParams& p, long long n_tiles, const TileCallPlan& pl, const IfsOut& out,
                 int pass) {
     if (p.reach + p.m <= kIfsHaloSmall)
         hipLaunchKernelGGL((ifs_kernel<kIfsHaloSmall>), dim3((unsigned)n_tiles), dim3(256), 0, s, cv, p, pl, out, pass);
@@ -280,18 +183,18 @@ void launch_any(hipStream_t s, const ContigView& cv, const IfsParams& p, long lo
 
 }  // namespace
 
-void launch_ifs_count(hipStream_t s, const ContigView& cv, const IfsParams& p, int n_tiles, const IfsPlan& pl) {
+void launch_ifs_count(hipStream_t s, const ContigView& cv, const IfsParams& p, int n_tiles, const TileCallPlan& pl) {
     if (n_tiles <= 0) return;
     launch_any(s, cv, p, n_tiles, pl, IfsOut{}, kIfsCount);
-    hipLaunchKernelGGL(ifs_scan_kernel, dim3(1), dim3(kIfsScanWidth), 0, s, pl, n_tiles);
+    hipLaunchKernelGGL(ifs_scan_kernel, dim3(1), dim3(kCallScanWidth), 0, s, pl, n_tiles);
 }
 
-void launch_ifs_write(hipStream_t s, const ContigView& cv, const IfsParams& p, int n_tiles, const IfsPlan& pl, const IfsOut& out) {
+void launch_ifs_write(hipStream_t s, const ContigView& cv, const IfsParams& p, int n_tiles, const TileCallPlan& pl, const IfsOut& out) {
     if (n_tiles <= 0) return;
     launch_any(s, cv, p, n_tiles, pl, out, kIfsWrite);
 }
 
-void launch_ifs_track(hipStream_t s, const ContigView& cv, const IfsParams& p, long long n_tiles, const IfsPlan& pl, const IfsOut& out) {
+void launch_ifs_track(hipStream_t s, const ContigView& cv, const IfsParams& p, long long n_tiles, const TileCallPlan& pl, const IfsOut& out) {
     if (n_tiles <= 0) return;
     launch_any(s, cv, p, n_tiles, pl, out, kIfsTrack);
 }

@@ -1,11 +1,11 @@
 // Preferred fragment ends (ftk_preferred_ends): the rule of include/ftk.h, "preferred ends".
 //
-// One workgroup of 256 threads per tile of kPrefTile positions of one interval, on the tile skeleton of depth_kernel:
-// the candidates come from the position index, the ends are counted with LDS atomics, a DPP wave scan with a cross-wave
-// carry turns the counts into prefix sums.  What differs: the arrays hold the tile AND a halo of HALO >= h positions on
-// either side, so that T(b) = P[b + h] - P[b - h - 1] for every position of the tile comes out of the tile's own LDS
-// (positions outside the contig hold no end, so the window needs no clipping here - only n_w is clipped); and there are
-// two tracks in split mode.  Entry a of a track is contig position t0 - HALO + a.
+// One workgroup of 256 threads per tile of kCallTile positions of one interval, on the tile-call skeleton of
+// ftk_tilecall.h: the candidates come from the position index, the ends are counted with LDS atomics, a DPP wave scan with
+// a cross-wave carry turns the counts into prefix sums.  The kernel's own: the arrays hold the tile AND a halo of
+// HALO >= h positions on either side, so that T(b) = P[b + h] - P[b - h - 1] for every position of the tile comes out of
+// the tile's own LDS (positions outside the contig hold no end, so the window needs no clipping here - only n_w is
+// clipped); and there are two tracks in split mode.  Entry a of a track is contig position t0 - HALO + a.
 //
 // Candidates: a fragment's U end is `start`, its D end `end - 1`; either lies in [t0 - h, t0 + len + h) only when
 // t0 - h - lmax < start < t0 + len + h (lmax: the longest fragment the filter admits, as in depth_kernel - a D end may
@@ -21,7 +21,6 @@
 // Counters are 32 bits wide: counts up to 2^31 - 1 per position are exact, and a window total below 2^32 is exact too,
 // because prefix sums are only ever subtracted (unsigned arithmetic wraps; the scan's additions are plain 32-bit adds).
 // LDS per workgroup and occupancy of the four instantiations: DESIGN.md, "preferred ends".
-#include "ftk_device.h"
 #include "ftk_prefends.h"
 
 namespace ftk {
@@ -29,14 +28,14 @@ namespace ftk {
 namespace {
 
 template <int HALO, bool SPLIT>
-__global__ __launch_bounds__(256) void prefends_kernel(ContigView cv, PrefParams p, PrefPlan pl, PrefOut o, int write) {
-    constexpr int T = kPrefTile, W = T + 2 * HALO, NP = W / 1024, NT = SPLIT ? 2 : 1, R = T / 256;
+__global__ __launch_bounds__(256) void prefends_kernel(ContigView cv, PrefParams p, TileCallPlan pl, PrefOut o, int write) {
+    constexpr int T = kCallTile, W = T + 2 * HALO, NP = W / 1024, NT = SPLIT ? 2 : 1, R = T / 256;
     static_assert(W % 1024 == 0 && R * 4 == 64, "the scan takes 1024 entries a trip; wave 0 scans the 64 (round, wave) counts");
     __shared__ __attribute__((aligned(16))) unsigned trk[NT][W];  // the counts, then their inclusive prefix sums
     __shared__ unsigned wtot[NT][NP][4];
     __shared__ unsigned red[4][kPrefStats];
     __shared__ int wcnt[R * 4], wpre[R * 4];
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int tid = threadIdx.x, wv = tid >> 6;
     const long long k = blockIdx.x;
     const int t0 = pl.tile_t0[k], len_t = pl.tile_len[k], h = p.half;
     const int base = t0 - HALO;                          // contig position of entry 0 (may be negative)
@@ -65,71 +64,9 @@ __global__ __launch_bounds__(256) void prefends_kernel(ContigView cv, PrefParams
             }
         }
     };
-    auto fetch = [&](int i, int& fs, int& fe, int& q) {
-        fs = cv.start[i];
-        if (p.packed) {
-            const int w = cv.lq[i];
-            fe = fs + (w >> kLqBits);
-            q = w & kLqMapqSat;
-        } else {
-            fe = cv.end[i];
-            q = cv.mapq[i];
-        }
-    };
-    // the columns of the first candidates requested in one batch (see depth_kernel)
-    constexpr int PF = 4;
-    int ps[PF], pe[PF], pq[PF];
-#pragma unroll
-    for (int u = 0; u < PF; ++u) {
-        const int i = lo + tid + 256 * u;
-        ps[u] = pe[u] = pq[u] = 0;
-        if (i < hi) fetch(i, ps[u], pe[u], pq[u]);
-    }
-#pragma unroll
-    for (int u = 0; u < PF; ++u)
-        if (lo + tid + 256 * u < hi) apply(ps[u], pe[u], pq[u]);
-    for (int i = lo + PF * 256 + tid; i < hi; i += 256) {
-        int fs, fe, q;
-        fetch(i, fs, fe, q);
-        apply(fs, fe, q);
-    }
+    tile_candidates(cv, p.packed, lo, hi, tid, apply);
     __syncthreads();
-    // thread tid holds the entries j * 1024 + 4 * tid .. + 3 of every trip j
-    {
-        uint4 v[NT][NP];
-        unsigned ex[NT][NP];
-#pragma unroll
-        for (int t = 0; t < NT; ++t)
-#pragma unroll
-            for (int j = 0; j < NP; ++j) {
-                v[t][j] = trk4[t * (W / 4) + j * 256 + tid];
-                const unsigned s = v[t][j].x + v[t][j].y + v[t][j].z + v[t][j].w;
-                const unsigned incl = (unsigned)wave_incl_scan_dpp((int)s);
-                ex[t][j] = incl - s;
-                if (lane == 63) wtot[t][j][wv] = incl;
-            }
-        __syncthreads();
-#pragma unroll
-        for (int t = 0; t < NT; ++t) {
-            unsigned all = 0;
-#pragma unroll
-            for (int j = 0; j < NP; ++j) {
-                unsigned carry = all;
-#pragma unroll
-                for (int w2 = 0; w2 < 4; ++w2) {
-                    const unsigned tt = wtot[t][j][w2];
-                    if (w2 < wv) carry += tt;
-                    all += tt;
-                }
-                uint4 q4;
-                q4.x = carry + ex[t][j] + v[t][j].x;
-                q4.y = q4.x + v[t][j].y;
-                q4.z = q4.y + v[t][j].z;
-                q4.w = q4.z + v[t][j].w;
-                trk4[t * (W / 4) + j * 256 + tid] = q4;
-            }
-        }
-    }
+    tile_tracks_scan(trk, wtot, tid);
     __syncthreads();
     // e, T and n_w of entry a (position b) of track t.  0: not tested, 1: tested, 2: called
     auto decide = [&](int t, int a, int b, unsigned& e, unsigned& tot, int& nw) -> int {
@@ -159,27 +96,16 @@ __global__ __launch_bounds__(256) void prefends_kernel(ContigView cv, PrefParams
         st[3] += rb == 2;
         flags |= (unsigned)(ra == 2) << (2 * r) | (unsigned)(rb == 2) << (2 * r + 1);
         const int c = __popcll(__ballot(ra == 2)) + __popcll(__ballot(rb == 2));
-        if (lane == 0) wcnt[r * 4 + wv] = c;
+        tile_rank_count(wcnt, r, c, tid);
     }
     if (!write) {
         const unsigned mine[kPrefStats] = {nu, nd, st[0], st[1], st[2], st[3]};
-#pragma unroll
-        for (int c = 0; c < kPrefStats; ++c) {
-            const unsigned s = wave_sum_u32(mine[c]);
-            if (lane == 0) red[wv][c] = s;
-        }
-        __syncthreads();
-        if (tid < kPrefStats) pl.stats[k * kPrefStats + tid] = red[0][tid] + red[1][tid] + red[2][tid] + red[3][tid];
+        tile_stats_reduce(mine, red, pl.stats, k, tid);
         return;
     }
-    __syncthreads();
-    if (wv == 0) {
-        const int x = wcnt[lane];
-        wpre[lane] = wave_incl_scan_dpp(x) - x;
-    }
-    __syncthreads();
+    tile_rank_scan(wcnt, wpre, tid);
     const long long off = pl.off[k];
-    const unsigned long long lower = (1ull << lane) - 1;
+    const unsigned long long lower = tile_lower_lanes(tid);
 #pragma unroll
     for (int r = 0; r < R; ++r) {
         const bool ca = flags >> (2 * r) & 1, cb = flags >> (2 * r + 1) & 1;
@@ -204,39 +130,18 @@ __global__ __launch_bounds__(256) void prefends_kernel(ContigView cv, PrefParams
     }
 }
 
-// One workgroup, kPrefScanWidth tiles a trip: the exclusive prefix sum of the tiles' calls and their total.
-__global__ __launch_bounds__(kPrefScanWidth) void prefends_scan_kernel(PrefPlan pl, int n_tiles) {
-    constexpr int NW = kPrefScanWidth / 64;
-    __shared__ int wt[NW];
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    long long carry = 0;
-    for (int c0 = 0; c0 < n_tiles; c0 += kPrefScanWidth) {
-        const int i = c0 + tid;
-        const int x = i < n_tiles ? (int)(pl.stats[(long long)i * kPrefStats + 4] + pl.stats[(long long)i * kPrefStats + 5]) : 0;
-        const int incl = wave_incl_scan_dpp(x);
-        if (lane == 63) wt[wv] = incl;
-        __syncthreads();
-        int before = 0, all = 0;
-#pragma unroll
-        for (int w2 = 0; w2 < NW; ++w2) {
-            const int tt = wt[w2];
-            if (w2 < wv) before += tt;
-            all += tt;
-        }
-        if (i < n_tiles) pl.off[i] = (int32_t)(carry + before + incl - x);
-        carry += all;
-        __syncthreads();
-    }
-    if (tid == 0) *pl.total = carry;
+// the exclusive prefix sum of the tiles' calls (both tracks) and their total
+__global__ __launch_bounds__(kCallScanWidth) void prefends_scan_kernel(TileCallPlan pl, int n_tiles) {
+    tile_offsets_scan(n_tiles, pl.off, pl.total, [&](long long i) { return pl.stats[i * kPrefStats + 4] + pl.stats[i * kPrefStats + 5]; });
 }
 
 template <int HALO, bool SPLIT>
-void launch_pass(hipStream_t s, const ContigView& cv, const PrefParams& p, int n_tiles, const PrefPlan& pl, const PrefOut& out,
+void launch_pass(hipStream_t s, const ContigView& cv, const PrefParams& p, int n_tiles, const TileCallPlan& pl, const PrefOut& out,
                  int write) {
     hipLaunchKernelGGL((prefends_kernel<HALO, SPLIT>), dim3((unsigned)n_tiles), dim3(256), 0, s, cv, p, pl, out, write);
 }
 
-void launch_any(hipStream_t s, const ContigView& cv, const PrefParams& p, int n_tiles, const PrefPlan& pl, const PrefOut& out,
+void launch_any(hipStream_t s, const ContigView& cv, const PrefParams& p, int n_tiles, const TileCallPlan& pl, const PrefOut& out,
                 int write) {
     if (p.half <= kPrefHaloSmall) {
         if (p.split) launch_pass<kPrefHaloSmall, true>(s, cv, p, n_tiles, pl, out, write);
@@ -249,13 +154,13 @@ void launch_any(hipStream_t s, const ContigView& cv, const PrefParams& p, int n_
 
 }  // namespace
 
-void launch_prefends_count(hipStream_t s, const ContigView& cv, const PrefParams& p, int n_tiles, const PrefPlan& pl) {
+void launch_prefends_count(hipStream_t s, const ContigView& cv, const PrefParams& p, int n_tiles, const TileCallPlan& pl) {
     if (n_tiles <= 0) return;
     launch_any(s, cv, p, n_tiles, pl, PrefOut{}, 0);
-    hipLaunchKernelGGL(prefends_scan_kernel, dim3(1), dim3(kPrefScanWidth), 0, s, pl, n_tiles);
+    hipLaunchKernelGGL(prefends_scan_kernel, dim3(1), dim3(kCallScanWidth), 0, s, pl, n_tiles);
 }
 
-void launch_prefends_write(hipStream_t s, const ContigView& cv, const PrefParams& p, int n_tiles, const PrefPlan& pl,
+void launch_prefends_write(hipStream_t s, const ContigView& cv, const PrefParams& p, int n_tiles, const TileCallPlan& pl,
                            const PrefOut& out) {
     if (n_tiles <= 0) return;
     launch_any(s, cv, p, n_tiles, pl, out, 1);

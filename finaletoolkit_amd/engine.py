@@ -275,6 +275,41 @@ class Engine:
         self._check(self.lib.ftk_frags_release(self.ctx, self._ids.pop(name)))
         self._bam.pop(name, None)
 
+    @staticmethod
+    def _interval_pair(starts, stops, flat=True):
+        """``(s, e, ps, pe)``: the int64 arrays of an interval list and the pointers the library takes for them (those
+        of a stand-in when the list is empty).  ``flat``: the arrays have to be one-dimensional too.  (Two error texts,
+        one per kind of caller: tests match on both, so they stay apart.)"""
+        s = np.ascontiguousarray(starts, dtype=np.int64)
+        e = np.ascontiguousarray(stops, dtype=np.int64)
+        if flat and (s.shape != e.shape or s.ndim != 1):
+            raise ValueError("starts and stops should be one-dimensional and equal in length")
+        if s.shape != e.shape:
+            raise ValueError("starts and stops differ in length")
+        keep = np.empty(1, np.int64)
+        return s, e, L.ptr(s if len(s) else keep), L.ptr(e if len(s) else keep)
+
+    def _library_records(self, call, *dtypes):
+        """``call(*outputs)`` with the output arguments of one record set per dtype - a block pointer per column, then
+        the count - and the library's blocks home: a list of record arrays, one per dtype.  The blocks are freed
+        whatever happens."""
+        sets = [([C.c_void_p() for _ in dt.names], C.c_int64()) for dt in dtypes]
+        try:
+            self._check(call(*[a for ptrs, n in sets for a in (*[C.byref(p) for p in ptrs], C.byref(n))]))
+            recs = []
+            for dt, (ptrs, n) in zip(dtypes, sets):
+                rec = np.zeros(n.value, dt)
+                for col, p in zip(dt.names, ptrs):
+                    if n.value:  # (one copy: out of the library's block into the records)
+                        rec[col] = np.frombuffer((C.c_char * (n.value * dt[col].itemsize)).from_address(p.value), dt[col])
+                recs.append(rec)
+        finally:
+            for ptrs, _ in sets:
+                for p in ptrs:
+                    if p.value:
+                        self.lib.ftk_buffer_free(p.value)
+        return recs
+
     def _filter(self, name, quality_threshold, min_length, max_length, intersect_policy):
         return L.make_filter(quality_threshold, min_length, max_length, intersect_policy,
                              L.FETCH_BAM_READ1 if self.is_bam(name) else L.FETCH_TABIX)
@@ -951,14 +986,11 @@ class Engine:
         (``ftk_wps_spectrum``): the scores of ``wps_intervals`` with the same arguments, written to device scratch and
         transformed there, ``batch_bases`` bases of intervals at a time (``None``: the library's choice) - no per-base
         value reaches the host.  The same bits as ``track_spectrum(*wps_intervals(...), periods, ...)``."""
-        s = np.ascontiguousarray(starts, dtype=np.int64)
-        e = np.ascontiguousarray(stops, dtype=np.int64)
-        if s.shape != e.shape:
-            raise ValueError("starts and stops differ in length")
+        s, _, ps, pe = self._interval_pair(starts, stops, flat=False)
         per, res, ssw = self._spectrum_outputs(len(s), periods, out, ssw_out)
         keep = np.empty(1, np.int64)
         self._check(self.lib.ftk_wps_spectrum(
-            self.ctx, self.contig_id(name), L.ptr(s if len(s) else keep), L.ptr(e if len(s) else keep), len(s), int(chrom_size),
+            self.ctx, self.contig_id(name), ps, pe, len(s), int(chrom_size),
             int(window_size), int(min_length), int(max_length), int(quality_threshold),
             L.ptr(per if len(per) else keep.view(np.int32)), len(per), float(taper), int(bool(detrend)),
             0 if batch_bases is None else int(batch_bases), L.ptr(res), L.ptr(ssw)))
@@ -972,21 +1004,9 @@ class Engine:
         """Calls ``fn(ctx, *args, outputs...)`` of the peaks pair and takes the library's blocks home:
         ``(calls, stats)`` - a ``PEAK_DTYPE`` record array ordered by ``(run, start)`` and the int64 counters
         ``[n_runs, 6]`` (regions, open, short, long, flat, calls)."""
-        ptrs = [C.c_void_p() for _ in self.PEAK_DTYPE.names]
-        n = C.c_int64()
         stats = np.zeros((n_runs, 6), np.int64)
         keep = np.empty(1, np.int64)
-        try:
-            self._check(fn(self.ctx, *args, *[C.byref(p) for p in ptrs], C.byref(n), L.ptr(stats if n_runs else keep)))
-            calls = np.zeros(n.value, self.PEAK_DTYPE)
-            for name, p in zip(self.PEAK_DTYPE.names, ptrs):
-                dt = self.PEAK_DTYPE[name]
-                if n.value:  # (one copy: out of the library's block into the records)
-                    calls[name] = np.frombuffer((C.c_char * (n.value * dt.itemsize)).from_address(p.value), dt)
-        finally:
-            for p in ptrs:
-                if p.value:
-                    self.lib.ftk_buffer_free(p.value)
+        calls, = self._library_records(lambda *out: fn(self.ctx, *args, *out, L.ptr(stats if n_runs else keep)), self.PEAK_DTYPE)
         return calls, stats
 
     def track_peaks(self, scores, offsets, skip=0, max_gap=5, min_region=50, short_max=150, max_region=450):
@@ -1016,17 +1036,13 @@ class Engine:
         ``savgol``).  A call's ``run`` is its interval's number and its positions are contig positions.  An interval
         shorter than ``median_window_size + max(savgol_window_size, 1)`` has no callable track: no call, zero counters.
         The same calls as ``track_peaks(wps_adjust(*wps_intervals(...)), ...)`` with positions moved to the contig."""
-        s = np.ascontiguousarray(starts, dtype=np.int64)
-        e = np.ascontiguousarray(stops, dtype=np.int64)
-        if s.shape != e.shape:
-            raise ValueError("starts and stops differ in length")
+        s, _, ps, pe = self._interval_pair(starts, stops, flat=False)
         sw = int(savgol_window_size) if savgol else 0
         coef = edge = None
         if sw:
             coef, edge = savgol_operators(sw, int(savgol_poly_deg))
-        keep = np.empty(1, np.int64)
         return self._peaks_call(
-            self.lib.ftk_wps_peaks, len(s), self.contig_id(name), L.ptr(s if len(s) else keep), L.ptr(e if len(s) else keep), len(s),
+            self.lib.ftk_wps_peaks, len(s), self.contig_id(name), ps, pe, len(s),
             int(chrom_size), int(window_size), int(min_length), int(max_length), int(quality_threshold),
             int(median_window_size), sw, L.ptr(coef), L.ptr(edge), int(max_gap), int(min_region), int(short_max),
             int(max_region), 0 if batch_bases is None else int(batch_bases))
@@ -1046,10 +1062,7 @@ class Engine:
         (``Engine.PREFERRED_END_DTYPE``: run, pos, kind, count, total, n_w; ``run`` the interval's number, ``pos`` a
         contig position) ordered by ``(run, pos, kind)``; ``stats``: int64 ``[n_intervals, 6]`` (U ends, D ends, tested
         a, tested b, calls a, calls b)."""
-        s = np.ascontiguousarray(starts, dtype=np.int64)
-        e = np.ascontiguousarray(stops, dtype=np.int64)
-        if s.shape != e.shape or s.ndim != 1:
-            raise ValueError("starts and stops should be one-dimensional and equal in length")
+        s, _, ps, pe = self._interval_pair(starts, stops)
         if mode not in ("combined", "split"):
             raise ValueError(f"invalid mode ({mode!r}): 'combined' or 'split'")
         if thresholds is None:
@@ -1059,25 +1072,13 @@ class Engine:
         if thr.ndim != 1:
             raise ValueError("thresholds should be one-dimensional")
         n_iv = len(s)
-        ptrs = [C.c_void_p() for _ in self.PREFERRED_END_DTYPE.names]
-        n = C.c_int64()
         stats = np.zeros((n_iv, 6), np.int64)
         keep = np.empty(1, np.int64)
-        try:
-            self._check(self.lib.ftk_preferred_ends(
-                self.ctx, self.contig_id(name), L.ptr(s if n_iv else keep), L.ptr(e if n_iv else keep), n_iv, int(chrom_size),
-                int(half), int(mode == "split"), int(min_count), L.ptr(thr if len(thr) else keep), len(thr),
-                L.LEN_OPEN if min_length is None else int(min_length), L.LEN_OPEN if max_length is None else int(max_length),
-                int(quality_threshold), *[C.byref(p) for p in ptrs], C.byref(n), L.ptr(stats if n_iv else keep)))
-            calls = np.zeros(n.value, self.PREFERRED_END_DTYPE)
-            for col, p in zip(self.PREFERRED_END_DTYPE.names, ptrs):
-                dt = self.PREFERRED_END_DTYPE[col]
-                if n.value:  # (one copy: out of the library's block into the records)
-                    calls[col] = np.frombuffer((C.c_char * (n.value * dt.itemsize)).from_address(p.value), dt)
-        finally:
-            for p in ptrs:
-                if p.value:
-                    self.lib.ftk_buffer_free(p.value)
+        calls, = self._library_records(lambda *out: self.lib.ftk_preferred_ends(
+            self.ctx, self.contig_id(name), ps, pe, n_iv, int(chrom_size),
+            int(half), int(mode == "split"), int(min_count), L.ptr(thr if len(thr) else keep), len(thr),
+            L.LEN_OPEN if min_length is None else int(min_length), L.LEN_OPEN if max_length is None else int(max_length),
+            int(quality_threshold), *out, L.ptr(stats if n_iv else keep)), self.PREFERRED_END_DTYPE)
         return calls, stats
 
     # -- IFS fragmentation hotspots (csrc/ftk_hotspots.hip) ---------------------------------------
@@ -1106,10 +1107,7 @@ class Engine:
         ``1 / mean_length``) of every window of the intervals ``[starts[i], stops[i])`` of resident contig ``name``
         (``ftk_ifs_track``; the rule is in ``include/ftk.h``, "IFS hotspots"), interval ``i`` at
         ``[offsets[i], offsets[i + 1])``.  ``device``: the two arrays stay on the GPU (torch tensors)."""
-        s = np.ascontiguousarray(starts, dtype=np.int64)
-        e = np.ascontiguousarray(stops, dtype=np.int64)
-        if s.shape != e.shape or s.ndim != 1:
-            raise ValueError("starts and stops should be one-dimensional and equal in length")
+        s, e, ps, pe = self._interval_pair(starts, stops)
         if not 1 <= int(step) <= 65535 or not 1 <= int(m) <= L.IFS_MAX_WINDOW_BINS or not 0 <= int(chrom_size) < 1 << 30:
             count = np.zeros(len(s), np.int64)  # (the library refuses the call below)
         else:
@@ -1127,7 +1125,7 @@ class Engine:
             i_out = np.zeros(total, np.int64)
         keep = np.empty(1, np.int64)
         self._check(self.lib.ftk_ifs_track(
-            self.ctx, self.contig_id(name), L.ptr(s if len(s) else keep), L.ptr(e if len(s) else keep), len(s),
+            self.ctx, self.contig_id(name), ps, pe, len(s),
             L.ptr(np.ascontiguousarray(offs[:-1]) if len(s) else keep), int(chrom_size), int(step), int(m), int(mean_length),
             L.LEN_OPEN if min_length is None else int(min_length), L.LEN_OPEN if max_length is None else int(max_length),
             int(quality_threshold), L.ptr(n_out) if total else None, L.ptr(i_out) if total else None))
@@ -1153,10 +1151,7 @@ class Engine:
         ``utils.ifs_thresholds()``).  ``windows``: the called windows (``Engine.IFS_WINDOW_DTYPE``) ordered by ``(run,
         pos)``; ``hotspots``: ``Engine.HOTSPOT_DTYPE`` records ordered by ``(run, start)``; ``stats``: int64
         ``[n_intervals, 6]`` (windows, tested, called, hotspots kept, hotspots dropped, bases covered)."""
-        s = np.ascontiguousarray(starts, dtype=np.int64)
-        e = np.ascontiguousarray(stops, dtype=np.int64)
-        if s.shape != e.shape or s.ndim != 1:
-            raise ValueError("starts and stops should be one-dimensional and equal in length")
+        s, _, ps, pe = self._interval_pair(starts, stops)
         if thresholds is None:
             from .utils import ifs_thresholds
             thresholds = ifs_thresholds()
@@ -1166,33 +1161,14 @@ class Engine:
         if join is None:
             join = max(int(m) + 200 // max(int(step), 1), 1)
         n_iv = len(s)
-        wp = [C.c_void_p() for _ in self.IFS_WINDOW_DTYPE.names]
-        hp = [C.c_void_p() for _ in self.HOTSPOT_DTYPE.names]
-        nw, nh = C.c_int64(), C.c_int64()
         stats = np.zeros((n_iv, 6), np.int64)
         keep = np.empty(1, np.int64)
-
-        def home(dtype, ptrs, n):
-            rec = np.zeros(n, dtype)
-            for col, p in zip(dtype.names, ptrs):
-                dt = dtype[col]
-                if n:  # (one copy: out of the library's block into the records)
-                    rec[col] = np.frombuffer((C.c_char * (n * dt.itemsize)).from_address(p.value), dt)
-            return rec
-        try:
-            self._check(self.lib.ftk_ifs_hotspots(
-                self.ctx, self.contig_id(name), L.ptr(s if n_iv else keep), L.ptr(e if n_iv else keep), n_iv, int(chrom_size),
-                int(step), int(m), int(mean_length), int(h1), int(h2), int(min_count), L.ptr(thr if len(thr) else keep), len(thr),
-                int(global_mean), int(join), int(min_windows),
-                L.LEN_OPEN if min_length is None else int(min_length), L.LEN_OPEN if max_length is None else int(max_length),
-                int(quality_threshold), *[C.byref(p) for p in wp], C.byref(nw), *[C.byref(p) for p in hp], C.byref(nh),
-                L.ptr(stats if n_iv else keep)))
-            windows = home(self.IFS_WINDOW_DTYPE, wp, nw.value)
-            hotspots = home(self.HOTSPOT_DTYPE, hp, nh.value)
-        finally:
-            for p in wp + hp:
-                if p.value:
-                    self.lib.ftk_buffer_free(p.value)
+        windows, hotspots = self._library_records(lambda *out: self.lib.ftk_ifs_hotspots(
+            self.ctx, self.contig_id(name), ps, pe, n_iv, int(chrom_size),
+            int(step), int(m), int(mean_length), int(h1), int(h2), int(min_count), L.ptr(thr if len(thr) else keep), len(thr),
+            int(global_mean), int(join), int(min_windows),
+            L.LEN_OPEN if min_length is None else int(min_length), L.LEN_OPEN if max_length is None else int(max_length),
+            int(quality_threshold), *out, L.ptr(stats if n_iv else keep)), self.IFS_WINDOW_DTYPE, self.HOTSPOT_DTYPE)
         return windows, hotspots, stats
 
     # -- WPS post-processing --------------------------------------------------------

@@ -727,8 +727,7 @@ SITE_PROFILE_MAX_BINS = 4096  # the bins one profile may have (``ftk_site_profil
 
 
 def _check_site_profile_args(output_file, reference_file, bias, half_width, bin_size, min_length, max_length, min_bias, stride):
-    if output_file is not None and not str(output_file).endswith((".tsv", ".tsv.gz")):
-        raise ValueError("output_file should have .tsv or .tsv.gz as suffix")
+    _check_suffix(output_file, "output_file", "tsv")
     half_width, bin_size = int(half_width), int(bin_size)
     if not 1 <= half_width <= 1 << 20:
         raise ValueError(f"invalid half_width ({half_width}): between 1 and 2**20")
@@ -982,9 +981,8 @@ OCF_MAX_CELLS = 1 << 28  # groups x 2 tracks x bins of one call
 def _check_ocf_args(output_file, profile_file, site_output_file, reference_file, bias, half_width, bin_size, peak, flank, min_length,
                     max_length, min_bias, stride):
     _check_site_profile_args(output_file, reference_file, bias, half_width, bin_size, min_length, max_length, min_bias, stride)
-    for path, what in ((profile_file, "profile_file"), (site_output_file, "site_output_file")):
-        if path is not None and not str(path).endswith((".tsv", ".tsv.gz")):
-            raise ValueError(f"{what} should have .tsv or .tsv.gz as suffix")
+    _check_suffix(profile_file, "profile_file", "tsv")
+    _check_suffix(site_output_file, "site_output_file", "tsv")
     if peak is None or flank is None:
         raise ValueError("invalid windows: peak and flank cannot be None")
     H, p, w = int(half_width), int(peak), int(flank)
@@ -1097,9 +1095,113 @@ def _is_alignment_file(input_file) -> bool:
     return isinstance(input_file, (str, os.PathLike)) and str(input_file).endswith((".sam", ".bam", ".cram"))
 
 
+def _check_suffix(path, what, kind):
+    """``path`` (``None``: no file) should end in ``.kind`` or ``.kind.gz``."""
+    if path is not None and not str(path).endswith((f".{kind}", f".{kind}.gz")):
+        raise ValueError(f"{what} should have .{kind} or .{kind}.gz as suffix")
+
+
+def _check_length_bounds(min_length, max_length):
+    if min_length is not None and int(min_length) < 0:
+        raise ValueError(f"invalid min_length ({min_length}): it should not be negative")
+    if max_length is not None and int(max_length) < 0:
+        raise ValueError(f"invalid max_length ({max_length}): it should not be negative")
+    if min_length is not None and max_length is not None and int(min_length) > int(max_length):
+        raise ValueError(f"min_length ({min_length}) exceeds max_length ({max_length})")
+
+
+def _check_chrom_sizes_given(input_file, chrom_sizes):
+    if chrom_sizes is None and not _is_alignment_file(input_file):
+        raise ValueError("chrom_sizes must be specified for BED/Fragment files")
+
+
+def _over_regions(label, input_file, interval_file, chrom_sizes, workers, verbose, dtypes, row, one_contig, finish, vet=None,
+                  whole_contigs=True):
+    """The walk of the region commands (``frag_wps_spectrum``, ``frag_wps_peaks``, ``frag_preferred_ends``,
+    ``frag_hotspots``): the intervals of ``interval_file`` grouped by contig - or, without one, every contig of the input
+    as one interval ``(contig, 0, size, ".")`` in the order the contigs are met (``whole_contigs`` off: the command has no
+    such mode and the interval file is required) - handed to the command contig by contig
+    as the input is decoded, and the command's answers put back into the intervals' order.
+
+    ``one_contig(engine, key, size, spans, whole) -> (records, rows, note)`` is the command's part: ``spans`` are the
+    ``(start, stop)`` of the contig's intervals; ``records`` holds one record array per dtype of ``dtypes`` whose field
+    ``interval`` numbers the spans from 0, in order inside every span; ``rows`` one row of ``row = (width, dtype)`` values
+    per span; ``note`` ends the contig's verbose line.  ``finish(intervals, records, rows) -> (result, note)`` gets the
+    records of all contigs ordered by interval, the rows as an ``(n_intervals, width)`` array, builds the result and
+    writes its files.  ``vet(intervals)`` may refuse the interval file's rows before anything else is looked at.
+
+    Chromosome sizes: the BAM header, else the ``chrom_sizes`` file.  A contig that is not in ``chrom_sizes`` raises
+    ``ValueError`` before the engine is used, one the input lacks raises the ``ValueError`` of ``frag.coverage``."""
+    import sys
+    import time
+
+    from .source import ContigFeed
+    t0 = time.time()
+    sizes = None if _is_alignment_file(input_file) else chrom_sizes_to_dict(chrom_sizes)
+    whole = whole_contigs and interval_file is None
+    intervals = [] if whole else get_intervals(interval_file)
+    if vet is not None:
+        vet(intervals)
+    by_contig: dict[str, list[int]] = {}
+    for i, iv in enumerate(intervals):
+        by_contig.setdefault(iv[0], []).append(i)
+    if sizes is not None:
+        for c in by_contig:
+            if c not in sizes:
+                raise ValueError(f"{c} is not in chrom_sizes")
+    parts, rows = [[] for _ in dtypes], {}
+    left = dict(by_contig)
+    eng = get_engine()
+    feed = ContigFeed(input_file, workers, names=None if whole else list(by_contig))
+    try:
+        for src, c in feed:
+            if whole:
+                if sizes is not None and c not in sizes:
+                    raise ValueError(f"{c} is not in chrom_sizes")
+                idx = [len(intervals)]
+            else:
+                idx = left.pop(c, None)
+                if idx is None:
+                    continue
+            size = int(src.lengths[c]) if sizes is None else int(sizes[c])
+            if whole:
+                intervals.append((c, 0, size, "."))
+            records, c_rows, note = one_contig(eng, src.key(c), size, [intervals[i][1:3] for i in idx], whole)
+            which = np.asarray(idx, np.int64)
+            for part, rec in zip(parts, records):
+                rec["interval"] = which[rec["interval"]]
+                part.append(rec)
+            rows.update(zip(idx, c_rows))
+            if verbose:
+                sys.stderr.write(f"{label}: {c}: {len(idx)} intervals, {note}\n")
+        src = feed.finish()
+    except BaseException:
+        feed.close()
+        raise
+    for c in left:  # contigs the file does not hold: the ValueError of frag.coverage
+        src.require(c)
+    records = []
+    for part, dt in zip(parts, dtypes):  # (an interval's records are in order already)
+        rec = np.concatenate(part) if part else np.zeros(0, dt)
+        records.append(rec[np.argsort(rec["interval"], kind="stable")])
+    n = len(intervals)
+    res, note = finish(intervals, records, np.array([rows[i] for i in range(n)], row[1]).reshape(n, row[0]))
+    if verbose:
+        sys.stderr.write(f"{label}: {n} intervals{note} in {time.time() - t0:.3f} s\n")
+    return res
+
+
+def _to_interval_records(dtype, calls, **fields):
+    """The engine's records ``calls`` as ``dtype`` records: ``interval`` from ``run``, ``fields`` as given, every other
+    field under its own name."""
+    rec = np.zeros(len(calls), dtype)
+    for name in dtype.names:
+        rec[name] = fields[name] if name in fields else calls["run" if name == "interval" else name]
+    return rec
+
+
 def _check_wps_spectrum_args(input_file, chrom_sizes, output_file, min_period, max_period, band, taper):
-    if output_file is not None and not str(output_file).endswith((".tsv", ".tsv.gz")):
-        raise ValueError("output_file should have .tsv or .tsv.gz as suffix")
+    _check_suffix(output_file, "output_file", "tsv")
     lo, hi = int(min_period), int(max_period)
     if lo > hi:
         raise ValueError(f"invalid periods: min_period ({lo}) is above max_period ({hi})")
@@ -1115,8 +1217,7 @@ def _check_wps_spectrum_args(input_file, chrom_sizes, output_file, min_period, m
         raise ValueError(f"invalid band ({b0}, {b1}): it should lie inside the periods [{lo}, {hi}]")
     if not 0.0 <= float(taper) <= 0.5:
         raise ValueError(f"invalid taper ({taper}): a fraction in [0, 0.5]")
-    if chrom_sizes is None and not _is_alignment_file(input_file):
-        raise ValueError("chrom_sizes must be specified for BED/Fragment files")
+    _check_chrom_sizes_given(input_file, chrom_sizes)
 
 
 def frag_wps_spectrum(input_file, interval_file, chrom_sizes=None, output_file=None, min_period: int = 120, max_period: int = 280,
@@ -1139,60 +1240,37 @@ def frag_wps_spectrum(input_file, interval_file, chrom_sizes=None, output_file=N
     interval of more than 2**22 bases raises too.  ``output_file`` (``.tsv`` / ``.tsv.gz``):
     ``writers.write_wps_spectrum_rows``."""
     import os
-    import sys
-    import time
 
     from . import writers
-    from .source import ContigFeed
     _check_wps_spectrum_args(input_file, chrom_sizes, output_file, min_period, max_period, band, taper)
-    t0 = time.time()
     periods = np.arange(int(min_period), int(max_period) + 1, dtype=np.int64)
-    sizes = None if _is_alignment_file(input_file) else chrom_sizes_to_dict(chrom_sizes)
-    intervals = get_intervals(interval_file)
-    by_contig: dict[str, list[int]] = {}
-    for i, iv in enumerate(intervals):
-        by_contig.setdefault(iv[0], []).append(i)
-    starts = np.array([iv[1] for iv in intervals], dtype=np.int64)
-    stops = np.array([iv[2] for iv in intervals], dtype=np.int64)
-    n_bases = np.maximum(stops - starts, 0)
-    if len(n_bases) and int(n_bases.max()) > SPECTRUM_MAX_BASES:
-        raise ValueError(f"interval {intervals[int(n_bases.argmax())][:3]} holds more than {SPECTRUM_MAX_BASES} bases")
-    if sizes is not None:
-        for c in by_contig:
-            if c not in sizes:
-                raise ValueError(f"{c} is not in chrom_sizes")
-    spectrum = np.zeros((len(intervals), len(periods)), np.complex128)
-    ssw = np.zeros(len(intervals), np.float64)
-    left = dict(by_contig)
-    eng = get_engine()
-    feed = ContigFeed(input_file, workers, names=list(by_contig))
-    try:
-        for src, c in feed:
-            idx = left.pop(c, None)
-            if idx is None:
-                continue
-            size = int(src.lengths[c]) if sizes is None else int(sizes[c])
-            spectrum[idx], ssw[idx] = eng.wps_spectrum(src.key(c), starts[idx], stops[idx], size, periods, window_size, min_length,
-                                                       max_length, quality_threshold, taper, True)
-            if verbose:
-                sys.stderr.write(f"frag_wps_spectrum: {c}: {len(idx)} intervals, {int(n_bases[idx].sum())} bases\n")
-        src = feed.finish()
-    except BaseException:
-        feed.close()
-        raise
-    for c in left:  # contigs the file does not hold: the ValueError of frag.coverage
-        src.require(c)
-    with np.errstate(divide="ignore", invalid="ignore"):
-        power = (spectrum.real ** 2 + spectrum.imag ** 2) / ssw[:, None]
-    power[(ssw == 0) | (n_bases == 0)] = np.nan
-    in_band = (periods >= int(band[0])) & (periods <= int(band[1]))
-    band_mean = power[:, in_band].mean(axis=1) if len(intervals) else np.zeros(0)
-    res = WpsSpectrum(intervals, periods, power, band_mean, n_bases)
-    if output_file is not None:
-        writers.write_wps_spectrum_rows(os.fspath(output_file), res)
-    if verbose:
-        sys.stderr.write(f"frag_wps_spectrum: {len(intervals)} intervals in {time.time() - t0:.3f} s\n")
-    return res
+
+    def bases(intervals):
+        return np.array([max(iv[2] - iv[1], 0) for iv in intervals], np.int64)
+
+    def vet(intervals):
+        n_bases = bases(intervals)
+        if len(n_bases) and int(n_bases.max()) > SPECTRUM_MAX_BASES:
+            raise ValueError(f"interval {intervals[int(n_bases.argmax())][:3]} holds more than {SPECTRUM_MAX_BASES} bases")
+
+    def one_contig(eng, key, size, spans, whole):
+        a, b = (np.array(v, np.int64) for v in zip(*spans))
+        spectrum, ssw = eng.wps_spectrum(key, a, b, size, periods, window_size, min_length, max_length, quality_threshold, taper, True)
+        return (), np.column_stack([spectrum, ssw]), f"{int(np.maximum(b - a, 0).sum())} bases"
+
+    def finish(intervals, records, rows):
+        spectrum, ssw, n_bases = rows[:, :-1], rows[:, -1].real, bases(intervals)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            power = (spectrum.real ** 2 + spectrum.imag ** 2) / ssw[:, None]
+        power[(ssw == 0) | (n_bases == 0)] = np.nan
+        in_band = (periods >= int(band[0])) & (periods <= int(band[1]))
+        band_mean = power[:, in_band].mean(axis=1) if len(intervals) else np.zeros(0)
+        res = WpsSpectrum(intervals, periods, power, band_mean, n_bases)
+        if output_file is not None:
+            writers.write_wps_spectrum_rows(os.fspath(output_file), res)
+        return res, ""
+    return _over_regions("frag_wps_spectrum", input_file, interval_file, chrom_sizes, workers, verbose, (),
+                         (len(periods) + 1, np.complex128), one_contig, finish, vet, whole_contigs=False)
 
 
 class WpsPeaks(NamedTuple):
@@ -1214,10 +1292,8 @@ PEAKS_MAX_MEDIAN_WINDOW = 2048    # the running median of ``ftk_wps_adjust``
 
 def _check_wps_peaks_args(input_file, chrom_sizes, output_file, summary_file, median_window_size, savgol_window_size,
                           savgol_poly_deg, savgol, max_gap, min_region, short_max, max_region, chunk_size):
-    if output_file is not None and not str(output_file).endswith((".bed", ".bed.gz")):
-        raise ValueError("output_file should have .bed or .bed.gz as suffix")
-    if summary_file is not None and not str(summary_file).endswith((".tsv", ".tsv.gz")):
-        raise ValueError("summary_file should have .tsv or .tsv.gz as suffix")
+    _check_suffix(output_file, "output_file", "bed")
+    _check_suffix(summary_file, "summary_file", "tsv")
     W = int(median_window_size)
     if W < 2 or W % 2 or W > PEAKS_MAX_MEDIAN_WINDOW:
         raise ValueError(f"invalid median_window_size ({W}): an even number in [2, {PEAKS_MAX_MEDIAN_WINDOW}]")
@@ -1234,8 +1310,7 @@ def _check_wps_peaks_args(input_file, chrom_sizes, output_file, summary_file, me
                          f"max_region <= {PEAKS_MAX_REGION}")
     if int(chunk_size) < 1:
         raise ValueError(f"invalid chunk_size ({chunk_size}): at least 1")
-    if chrom_sizes is None and not _is_alignment_file(input_file):
-        raise ValueError("chrom_sizes must be specified for BED/Fragment files")
+    _check_chrom_sizes_given(input_file, chrom_sizes)
 
 
 def _median_spacing(starts, stops) -> float:
@@ -1268,86 +1343,45 @@ def frag_wps_peaks(input_file, interval_file=None, chrom_sizes=None, output_file
     input lacks raises ``ValueError``, as in ``frag.coverage``.  ``output_file`` (``.bed`` / ``.bed.gz``):
     ``writers.write_wps_peaks_rows``; ``summary_file`` (``.tsv`` / ``.tsv.gz``): ``writers.write_wps_peaks_summary``."""
     import os
-    import sys
-    import time
 
     from . import writers
-    from .source import ContigFeed
     _check_wps_peaks_args(input_file, chrom_sizes, output_file, summary_file, median_window_size, savgol_window_size,
                           savgol_poly_deg, savgol, max_gap, min_region, short_max, max_region, chunk_size)
-    t0 = time.time()
     W, sw = int(median_window_size), int(savgol_window_size) if savgol else 0
     skip, chunk = sw // 2, int(chunk_size)
     pad = W // 2 + skip + int(max_region) + int(max_gap) + 1
-    sizes = None if _is_alignment_file(input_file) else chrom_sizes_to_dict(chrom_sizes)
-    whole = interval_file is None
-    intervals = [] if whole else get_intervals(interval_file)
-    by_contig: dict[str, list[int]] = {}
-    for i, iv in enumerate(intervals):
-        by_contig.setdefault(iv[0], []).append(i)
-    if sizes is not None:
-        for c in by_contig:
-            if c not in sizes:
-                raise ValueError(f"{c} is not in chrom_sizes")
     args = dict(window_size=window_size, min_length=min_length, max_length=max_length, quality_threshold=quality_threshold,
                 median_window_size=W, savgol_window_size=savgol_window_size, savgol_poly_deg=savgol_poly_deg, savgol=bool(savgol),
                 max_gap=max_gap, min_region=min_region, short_max=short_max, max_region=max_region)
-    parts, stat_rows = [], {}
-    left = dict(by_contig)
-    eng = get_engine()
-    feed = ContigFeed(input_file, workers, names=None if whole else list(by_contig))
-    try:
-        for src, c in feed:
-            if whole:
-                if sizes is not None and c not in sizes:
-                    raise ValueError(f"{c} is not in chrom_sizes")
-                size = int(src.lengths[c]) if sizes is None else int(sizes[c])
-                idx = [len(intervals)]
-                intervals.append((c, 0, size, "."))
-                core = np.arange(0, max(size, 1), chunk, dtype=np.int64)
-                core_end = np.minimum(core + chunk, size)
-                calls, stats = eng.wps_peaks(src.key(c), np.maximum(core - pad, 0), np.minimum(core_end + pad, size), size, **args)
-                calls = calls[(calls["start"] >= core[calls["run"]]) & (calls["start"] < core_end[calls["run"]])]
-                which = np.full(len(calls), idx[0], np.int64)
-                stat_rows[idx[0]] = stats.sum(axis=0)
-                stat_rows[idx[0]][5] = len(calls)
-            else:
-                idx = left.pop(c, None)
-                if idx is None:
-                    continue
-                size = int(src.lengths[c]) if sizes is None else int(sizes[c])
-                calls, stats = eng.wps_peaks(src.key(c), [intervals[i][1] for i in idx], [intervals[i][2] for i in idx], size, **args)
-                which = np.asarray(idx, np.int64)[calls["run"]]
-                stat_rows.update(zip(idx, stats))
-            part = np.zeros(len(calls), WPS_PEAK_DTYPE)
-            part["interval"] = which
-            for name in WPS_PEAK_DTYPE.names[1:]:
-                part[name] = calls[name]
-            parts.append(part)
-            if verbose:
-                sys.stderr.write(f"frag_wps_peaks: {c}: {len(idx)} intervals, {len(part)} calls\n")
-        src = feed.finish()
-    except BaseException:
-        feed.close()
-        raise
-    for c in left:  # contigs the file does not hold: the ValueError of frag.coverage
-        src.require(c)
-    calls = np.concatenate(parts) if parts else np.zeros(0, WPS_PEAK_DTYPE)
-    calls = calls[np.argsort(calls["interval"], kind="stable")]  # (an interval's calls are in start order already)
-    n = len(intervals)
-    stats = np.array([stat_rows[i] for i in range(n)], np.int64).reshape(n, 6)
-    lens = np.array([max(iv[2] - iv[1], 0) for iv in intervals], np.int64)
-    callable_ = np.where(lens >= W + max(sw, 1), lens - W - 2 * skip, 0)
-    bounds = np.searchsorted(calls["interval"], np.arange(n + 1))
-    spacing = np.array([_median_spacing(calls["start"][a:b], calls["stop"][a:b]) for a, b in zip(bounds[:-1], bounds[1:])], np.float64)
-    res = WpsPeaks(intervals, calls, stats, callable_, spacing)
-    if output_file is not None:
-        writers.write_wps_peaks_rows(os.fspath(output_file), res)
-    if summary_file is not None:
-        writers.write_wps_peaks_summary(os.fspath(summary_file), res)
-    if verbose:
-        sys.stderr.write(f"frag_wps_peaks: {n} intervals, {len(calls)} calls in {time.time() - t0:.3f} s\n")
-    return res
+
+    def one_contig(eng, key, size, spans, whole):
+        if whole:  # padded chunks; a call stays with the chunk that holds its start
+            core = np.arange(0, max(size, 1), chunk, dtype=np.int64)
+            core_end = np.minimum(core + chunk, size)
+            calls, stats = eng.wps_peaks(key, np.maximum(core - pad, 0), np.minimum(core_end + pad, size), size, **args)
+            calls = calls[(calls["start"] >= core[calls["run"]]) & (calls["start"] < core_end[calls["run"]])]
+            stats = stats.sum(axis=0, keepdims=True)
+            stats[0, 5] = len(calls)
+            part = _to_interval_records(WPS_PEAK_DTYPE, calls, interval=0)
+        else:
+            calls, stats = eng.wps_peaks(key, [a for a, _ in spans], [b for _, b in spans], size, **args)
+            part = _to_interval_records(WPS_PEAK_DTYPE, calls)
+        return (part,), stats, f"{len(part)} calls"
+
+    def finish(intervals, records, stats):
+        calls, n = records[0], len(intervals)
+        lens = np.array([max(iv[2] - iv[1], 0) for iv in intervals], np.int64)
+        callable_ = np.where(lens >= W + max(sw, 1), lens - W - 2 * skip, 0)
+        bounds = np.searchsorted(calls["interval"], np.arange(n + 1))
+        spacing = np.array([_median_spacing(calls["start"][a:b], calls["stop"][a:b]) for a, b in zip(bounds[:-1], bounds[1:])], np.float64)
+        res = WpsPeaks(intervals, calls, stats, callable_, spacing)
+        if output_file is not None:
+            writers.write_wps_peaks_rows(os.fspath(output_file), res)
+        if summary_file is not None:
+            writers.write_wps_peaks_summary(os.fspath(summary_file), res)
+        return res, f", {len(calls)} calls"
+    return _over_regions("frag_wps_peaks", input_file, interval_file, chrom_sizes, workers, verbose, (WPS_PEAK_DTYPE,), (6, np.int64),
+                         one_contig, finish)
 
 
 class PreferredEnds(NamedTuple):
@@ -1398,26 +1432,18 @@ def preferred_end_thresholds(alpha: float = 0.01, n: int = 256) -> np.ndarray:
 
 def _check_preferred_ends_args(input_file, chrom_sizes, output_file, summary_file, half_window, alpha, min_count, min_length,
                                max_length, chunk_size):
-    if output_file is not None and not str(output_file).endswith((".bed", ".bed.gz")):
-        raise ValueError("output_file should have .bed or .bed.gz as suffix")
-    if summary_file is not None and not str(summary_file).endswith((".tsv", ".tsv.gz")):
-        raise ValueError("summary_file should have .tsv or .tsv.gz as suffix")
+    _check_suffix(output_file, "output_file", "bed")
+    _check_suffix(summary_file, "summary_file", "tsv")
     if not 1 <= int(half_window) <= PREFENDS_MAX_HALF:
         raise ValueError(f"invalid half_window ({half_window}): 1 .. {PREFENDS_MAX_HALF}")
     if not 0.0 < float(alpha) < 1.0:
         raise ValueError(f"invalid alpha ({alpha}): it should lie inside (0, 1)")
     if int(min_count) < 1:
         raise ValueError(f"invalid min_count ({min_count}): at least 1")
-    if min_length is not None and int(min_length) < 0:
-        raise ValueError(f"invalid min_length ({min_length}): it should not be negative")
-    if max_length is not None and int(max_length) < 0:
-        raise ValueError(f"invalid max_length ({max_length}): it should not be negative")
-    if min_length is not None and max_length is not None and int(min_length) > int(max_length):
-        raise ValueError(f"min_length ({min_length}) exceeds max_length ({max_length})")
+    _check_length_bounds(min_length, max_length)
     if int(chunk_size) < 1:
         raise ValueError(f"invalid chunk_size ({chunk_size}): at least 1")
-    if chrom_sizes is None and not _is_alignment_file(input_file):
-        raise ValueError("chrom_sizes must be specified for BED/Fragment files")
+    _check_chrom_sizes_given(input_file, chrom_sizes)
 
 
 def frag_preferred_ends(input_file, interval_file=None, chrom_sizes=None, output_file=None, summary_file=None,
@@ -1439,82 +1465,41 @@ def frag_preferred_ends(input_file, interval_file=None, chrom_sizes=None, output
     input lacks raises ``ValueError``, as in ``frag.coverage``.  ``output_file`` (``.bed`` / ``.bed.gz``):
     ``writers.write_preferred_end_rows``; ``summary_file`` (``.tsv`` / ``.tsv.gz``): ``writers.write_preferred_end_summary``."""
     import os
-    import sys
-    import time
 
     from . import writers
-    from .source import ContigFeed
     _check_preferred_ends_args(input_file, chrom_sizes, output_file, summary_file, half_window, alpha, min_count, min_length,
                                max_length, chunk_size)
-    t0 = time.time()
     chunk = int(chunk_size)
-    sizes = None if _is_alignment_file(input_file) else chrom_sizes_to_dict(chrom_sizes)
-    whole = interval_file is None
-    intervals = [] if whole else get_intervals(interval_file)
-    by_contig: dict[str, list[int]] = {}
-    for i, iv in enumerate(intervals):
-        by_contig.setdefault(iv[0], []).append(i)
-    if sizes is not None:
-        for c in by_contig:
-            if c not in sizes:
-                raise ValueError(f"{c} is not in chrom_sizes")
     args = dict(half=int(half_window), mode="split" if split else "combined", min_count=int(min_count),
                 thresholds=preferred_end_thresholds(alpha), min_length=min_length, max_length=max_length,
                 quality_threshold=quality_threshold)
-    parts, stat_rows = [], {}
-    left = dict(by_contig)
-    eng = get_engine()
-    feed = ContigFeed(input_file, workers, names=None if whole else list(by_contig))
-    try:
-        for src, c in feed:
-            if whole:
-                if sizes is not None and c not in sizes:
-                    raise ValueError(f"{c} is not in chrom_sizes")
-                size = int(src.lengths[c]) if sizes is None else int(sizes[c])
-                idx = [len(intervals)]
-                intervals.append((c, 0, size, "."))
-                cut = np.arange(0, max(size, 1), chunk, dtype=np.int64)
-                calls, stats = eng.preferred_ends(src.key(c), cut, np.minimum(cut + chunk, size), size, **args)
-                which = np.full(len(calls), idx[0], np.int64)  # (chunks follow one another: the calls are in position order)
-                stat_rows[idx[0]] = stats.sum(axis=0)
-            else:
-                idx = left.pop(c, None)
-                if idx is None:
-                    continue
-                size = int(src.lengths[c]) if sizes is None else int(sizes[c])
-                a = np.clip(np.array([intervals[i][1] for i in idx], np.int64), 0, size)
-                b = np.clip(np.array([intervals[i][2] for i in idx], np.int64), a, size)
-                calls, stats = eng.preferred_ends(src.key(c), a, b, size, **args)
-                which = np.asarray(idx, np.int64)[calls["run"]]
-                stat_rows.update(zip(idx, stats))
-            part = np.zeros(len(calls), PREFERRED_END_DTYPE)
-            part["interval"] = which
-            for name in PREFERRED_END_DTYPE.names[1:]:
-                part[name] = calls[name]
-            parts.append(part)
-            if verbose:
-                sys.stderr.write(f"frag_preferred_ends: {c}: {len(idx)} intervals, {len(part)} calls\n")
-        src = feed.finish()
-    except BaseException:
-        feed.close()
-        raise
-    for c in left:  # contigs the file does not hold: the ValueError of frag.coverage
-        src.require(c)
-    calls = np.concatenate(parts) if parts else np.zeros(0, PREFERRED_END_DTYPE)
-    calls = calls[np.argsort(calls["interval"], kind="stable")]  # (an interval's calls are in (pos, kind) order already)
-    n = len(intervals)
-    stats = np.array([stat_rows[i] for i in range(n)], np.int64).reshape(n, 6)
-    on_calls = np.bincount(calls["interval"], weights=calls["count"], minlength=n)[:n] if n else np.zeros(0)
-    ends = (stats[:, 0] + stats[:, 1]).astype(np.float64)
-    share = np.divide(on_calls, ends, out=np.full(n, np.nan), where=ends > 0)
-    res = PreferredEnds(intervals, calls, stats, share)
-    if output_file is not None:
-        writers.write_preferred_end_rows(os.fspath(output_file), res)
-    if summary_file is not None:
-        writers.write_preferred_end_summary(os.fspath(summary_file), res)
-    if verbose:
-        sys.stderr.write(f"frag_preferred_ends: {n} intervals, {len(calls)} calls in {time.time() - t0:.3f} s\n")
-    return res
+
+    def one_contig(eng, key, size, spans, whole):
+        if whole:  # chunks without overlap, one after the other: the calls are in position order
+            cut = np.arange(0, max(size, 1), chunk, dtype=np.int64)
+            calls, stats = eng.preferred_ends(key, cut, np.minimum(cut + chunk, size), size, **args)
+            stats = stats.sum(axis=0, keepdims=True)
+            part = _to_interval_records(PREFERRED_END_DTYPE, calls, interval=0)
+        else:
+            a = np.clip(np.array([a for a, _ in spans], np.int64), 0, size)
+            b = np.clip(np.array([b for _, b in spans], np.int64), a, size)
+            calls, stats = eng.preferred_ends(key, a, b, size, **args)
+            part = _to_interval_records(PREFERRED_END_DTYPE, calls)
+        return (part,), stats, f"{len(part)} calls"
+
+    def finish(intervals, records, stats):
+        calls, n = records[0], len(intervals)
+        on_calls = np.bincount(calls["interval"], weights=calls["count"], minlength=n)[:n] if n else np.zeros(0)
+        ends = (stats[:, 0] + stats[:, 1]).astype(np.float64)
+        share = np.divide(on_calls, ends, out=np.full(n, np.nan), where=ends > 0)
+        res = PreferredEnds(intervals, calls, stats, share)
+        if output_file is not None:
+            writers.write_preferred_end_rows(os.fspath(output_file), res)
+        if summary_file is not None:
+            writers.write_preferred_end_summary(os.fspath(summary_file), res)
+        return res, f", {len(calls)} calls"
+    return _over_regions("frag_preferred_ends", input_file, interval_file, chrom_sizes, workers, verbose, (PREFERRED_END_DTYPE,),
+                         (6, np.int64), one_contig, finish)
 
 
 class IfsHotspots(NamedTuple):
@@ -1573,11 +1558,9 @@ def ifs_thresholds(alpha: float = 1e-5, n: int = 256) -> np.ndarray:
 
 def _check_hotspots_args(input_file, chrom_sizes, output_file, windows_file, summary_file, step, window, background, alpha,
                          mean_length, min_count, join, min_windows, min_length, max_length):
-    for f, what in ((output_file, "output_file"), (windows_file, "windows_file")):
-        if f is not None and not str(f).endswith((".bed", ".bed.gz")):
-            raise ValueError(f"{what} should have .bed or .bed.gz as suffix")
-    if summary_file is not None and not str(summary_file).endswith((".tsv", ".tsv.gz")):
-        raise ValueError("summary_file should have .tsv or .tsv.gz as suffix")
+    _check_suffix(output_file, "output_file", "bed")
+    _check_suffix(windows_file, "windows_file", "bed")
+    _check_suffix(summary_file, "summary_file", "tsv")
     step, window = int(step), int(window)
     if not 1 <= step <= 65535:
         raise ValueError(f"invalid step ({step}): 1 .. 65535")
@@ -1609,14 +1592,8 @@ def _check_hotspots_args(input_file, chrom_sizes, output_file, windows_file, sum
         raise ValueError(f"invalid join ({join}): 1 .. {IFS_MAX_JOIN}")
     if int(min_windows) < 1:
         raise ValueError(f"invalid min_windows ({min_windows}): at least 1")
-    if min_length is not None and int(min_length) < 0:
-        raise ValueError(f"invalid min_length ({min_length}): it should not be negative")
-    if max_length is not None and int(max_length) < 0:
-        raise ValueError(f"invalid max_length ({max_length}): it should not be negative")
-    if min_length is not None and max_length is not None and int(min_length) > int(max_length):
-        raise ValueError(f"min_length ({min_length}) exceeds max_length ({max_length})")
-    if chrom_sizes is None and not _is_alignment_file(input_file):
-        raise ValueError("chrom_sizes must be specified for BED/Fragment files")
+    _check_length_bounds(min_length, max_length)
+    _check_chrom_sizes_given(input_file, chrom_sizes)
     return m, h[0], (h[1] if len(h) == 2 else 0)
 
 
@@ -1644,101 +1621,48 @@ def frag_hotspots(input_file, interval_file=None, chrom_sizes=None, output_file=
     ``writers.write_hotspot_rows``; ``windows_file``: ``writers.write_hotspot_windows``; ``summary_file`` (``.tsv`` /
     ``.tsv.gz``): ``writers.write_hotspot_summary``."""
     import os
-    import sys
-    import time
 
     from . import writers
-    from .source import ContigFeed
     m, h1, h2 = _check_hotspots_args(input_file, chrom_sizes, output_file, windows_file, summary_file, step, window, background,
                                      alpha, mean_length, min_count, join, min_windows, min_length, max_length)
-    t0 = time.time()
     step = int(step)
     join = max(m + 200 // step, 1) if join is None else int(join)
-    sizes = None if _is_alignment_file(input_file) else chrom_sizes_to_dict(chrom_sizes)
-    whole = interval_file is None
-    intervals = [] if whole else get_intervals(interval_file)
-    by_contig: dict[str, list[int]] = {}
-    for i, iv in enumerate(intervals):
-        by_contig.setdefault(iv[0], []).append(i)
-    if sizes is not None:
-        for c in by_contig:
-            if c not in sizes:
-                raise ValueError(f"{c} is not in chrom_sizes")
     filt = dict(min_length=min_length, max_length=max_length, quality_threshold=quality_threshold)
     thr = ifs_thresholds(alpha)
-    hot_parts, win_parts, stat_rows, mean_rows, glob_rows = [], [], {}, {}, {}
-    left = dict(by_contig)
-    eng = get_engine()
-    feed = ContigFeed(input_file, workers, names=None if whole else list(by_contig))
-    try:
-        for src, c in feed:
-            if whole:
-                if sizes is not None and c not in sizes:
-                    raise ValueError(f"{c} is not in chrom_sizes")
-                idx = [len(intervals)]
-            else:
-                idx = left.pop(c, None)
-                if idx is None:
-                    continue
-            size = int(src.lengths[c]) if sizes is None else int(sizes[c])
-            if whole:
-                intervals.append((c, 0, size, "."))
-            a = np.clip(np.array([intervals[i][1] for i in idx], np.int64), 0, size)
-            b = np.clip(np.array([intervals[i][2] for i in idx], np.int64), a, size)
-            L, gm = mean_length, 0
-            if L is None or use_global:
-                N, S = eng.ifs_totals(src.key(c), size, **filt)
-                if L is None:
-                    L = min(max((2 * S + N) // (2 * N), 1), 65535) if N else 1
-                L = int(L)
-                n_bins = -(-size // step)
-                if use_global and n_bins:
-                    gm = (N * L + S) * m * 1024 // (n_bins * L)
+
+    def one_contig(eng, key, size, spans, whole):
+        a = np.clip(np.array([a for a, _ in spans], np.int64), 0, size)
+        b = np.clip(np.array([b for _, b in spans], np.int64), a, size)
+        L, gm = mean_length, 0
+        if L is None or use_global:
+            N, S = eng.ifs_totals(key, size, **filt)
+            if L is None:
+                L = min(max((2 * S + N) // (2 * N), 1), 65535) if N else 1
             L = int(L)
-            win, hot, stats = eng.ifs_hotspots(src.key(c), a, b, size, step=step, m=m, mean_length=L, h1=h1, h2=h2,
-                                               min_count=int(min_count), thresholds=thr, global_mean=gm, join=join,
-                                               min_windows=int(min_windows), **filt)
-            which = np.asarray(idx, np.int64)
-            hp = np.zeros(len(hot), HOTSPOT_DTYPE)
-            hp["interval"] = which[hot["run"]]
-            for name in HOTSPOT_DTYPE.names[1:]:
-                hp[name] = hot[name]
-            wp = np.zeros(len(win), IFS_WINDOW_DTYPE)
-            wp["interval"] = which[win["run"]]
-            wp["start"] = win["pos"]
-            wp["stop"] = np.minimum(win["pos"] + m * step, size)
-            for name in IFS_WINDOW_DTYPE.names[3:]:
-                wp[name] = win[name]
-            hot_parts.append(hp)
-            win_parts.append(wp)
-            stat_rows.update(zip(idx, stats))
-            mean_rows.update((i, L) for i in idx)
-            glob_rows.update((i, gm) for i in idx)
-            if verbose:
-                sys.stderr.write(f"frag_hotspots: {c}: {len(idx)} intervals, L = {L}, {len(wp)} called windows, {len(hp)} hotspots\n")
-        src = feed.finish()
-    except BaseException:
-        feed.close()
-        raise
-    for c in left:  # contigs the file does not hold: the ValueError of frag.coverage
-        src.require(c)
-    hotspots = np.concatenate(hot_parts) if hot_parts else np.zeros(0, HOTSPOT_DTYPE)
-    hotspots = hotspots[np.argsort(hotspots["interval"], kind="stable")]  # (an interval's records are in start order already)
-    windows = np.concatenate(win_parts) if win_parts else np.zeros(0, IFS_WINDOW_DTYPE)
-    windows = windows[np.argsort(windows["interval"], kind="stable")]
-    n = len(intervals)
-    stats = np.array([stat_rows[i] for i in range(n)], np.int64).reshape(n, 6)
-    res = IfsHotspots(intervals, hotspots, windows, stats, np.array([mean_rows[i] for i in range(n)], np.int64),
-                      np.array([glob_rows[i] for i in range(n)], np.int64), step, m)
-    if output_file is not None:
-        writers.write_hotspot_rows(os.fspath(output_file), res)
-    if windows_file is not None:
-        writers.write_hotspot_windows(os.fspath(windows_file), res)
-    if summary_file is not None:
-        writers.write_hotspot_summary(os.fspath(summary_file), res)
-    if verbose:
-        sys.stderr.write(f"frag_hotspots: {n} intervals, {len(hotspots)} hotspots in {time.time() - t0:.3f} s\n")
-    return res
+            n_bins = -(-size // step)
+            if use_global and n_bins:
+                gm = (N * L + S) * m * 1024 // (n_bins * L)
+        L = int(L)
+        win, hot, stats = eng.ifs_hotspots(key, a, b, size, step=step, m=m, mean_length=L, h1=h1, h2=h2, min_count=int(min_count),
+                                           thresholds=thr, global_mean=gm, join=join, min_windows=int(min_windows), **filt)
+        hp = _to_interval_records(HOTSPOT_DTYPE, hot)
+        wp = _to_interval_records(IFS_WINDOW_DTYPE, win, start=win["pos"], stop=np.minimum(win["pos"] + m * step, size))
+        rows = np.column_stack([stats, np.full(len(stats), L, np.int64), np.full(len(stats), gm, np.int64)])
+        return (hp, wp), rows, f"L = {L}, {len(wp)} called windows, {len(hp)} hotspots"
+
+    def finish(intervals, records, rows):
+        hotspots, windows = records
+        stats, mean_rows, glob_rows = (np.ascontiguousarray(a) for a in (rows[:, :6], rows[:, 6], rows[:, 7]))
+        res = IfsHotspots(intervals, hotspots, windows, stats, mean_rows, glob_rows, step, m)
+        if output_file is not None:
+            writers.write_hotspot_rows(os.fspath(output_file), res)
+        if windows_file is not None:
+            writers.write_hotspot_windows(os.fspath(windows_file), res)
+        if summary_file is not None:
+            writers.write_hotspot_summary(os.fspath(summary_file), res)
+        return res, f", {len(hotspots)} hotspots"
+    return _over_regions("frag_hotspots", input_file, interval_file, chrom_sizes, workers, verbose, (HOTSPOT_DTYPE, IFS_WINDOW_DTYPE),
+                         (8, np.int64), one_contig, finish)
 
 
 def agg_bw(input_file, interval_file, output_file, median_window_size: int = 1, mean: bool = False,

@@ -253,7 +253,7 @@ def test_intervals(engine):
 
 
 def test_more_tiles_than_a_batch_and_a_growing_scratch(engine):
-    """The call walks its tiles in batches of ``BATCH`` (kPrefBatchTiles): ``BATCH + 5`` intervals of one base are as many
+    """The call walks its tiles in batches of ``BATCH`` (kCallBatchTiles): ``BATCH + 5`` intervals of one base are as many
     tiles, so the calls come home in two pieces and the counters of both reach their rows.  Then a context of its own, whose
     scratch is no larger than the plan of a batch: three copies of the whole contig at depth 200 give more calls than the
     plan's block has room for, so the scratch has to grow between the passes (where an idle block of an earlier context is
@@ -273,6 +273,31 @@ def test_more_tiles_than_a_batch_and_a_growing_scratch(engine):
         with Contig(own, *cols) as c:
             calls, stats = c.both([0, 0, 0], [size, size, size], size, **every)
             assert len(calls) * 32 > 1 << 20 and np.array_equal(stats[0], stats[2])
+
+
+def test_a_window_crosses_the_batch_boundary(engine):
+    """One interval of more tiles than a batch holds: the positions on either side of the last tile bound of the first batch
+    are tested against windows that read the ends on the far side of it, and the calls come home in two pieces."""
+    from finaletoolkit_amd import _lib as L
+    T, BATCH = tile(), L.PREFENDS_BATCH_TILES
+    edge = BATCH * T
+    size = edge + T + 9
+    frags = [((77, 240), 2), ((edge - 300, edge - 140), 2), ((edge - 3, edge + 160), 2), ((edge, edge + 167), 3),
+             ((edge + 2, edge + 150), 1), ((size - 160, size), 2)]
+    called = [77, 239, edge - 300, edge - 141, edge - 3, edge, edge + 159, edge + 166, size - 160, size - 1]
+    kw = dict(half=500, thresholds=flat_table(1))
+    with Contig(engine, *columns(*[(np.full(n, a), np.full(n, b)) for (a, b), n in frags])) as c:
+        calls, stats = c.both([0], [size], size, mode="combined", min_count=2, **kw)
+        assert calls["pos"].tolist() == called and calls["kind"].tolist() == [2] * 10
+        assert calls["total"][2:8].tolist() == [16] * 6 and calls["n_w"][2:8].tolist() == [1001] * 6
+        assert stats.tolist() == [[12, 12, 10, 0, 10, 0]]
+        calls, stats = c.both([0], [size], size, mode="combined", min_count=3, **kw)  # the first batch brings no call home
+        assert calls.tolist() == [(0, edge, 2, 3, 16, 1001), (0, edge + 166, 2, 3, 16, 1001)]
+        assert stats.tolist() == [[12, 12, 2, 0, 2, 0]]
+        calls, stats = c.both([0], [size], size, mode="split", min_count=2, **kw)
+        assert calls["pos"].tolist() == called and calls["kind"].tolist() == [0, 1, 0, 1, 0, 0, 1, 1, 0, 1]
+        assert calls["total"][2:8].tolist() == [8] * 6
+        assert stats.tolist() == [[12, 12, 5, 5, 5, 5]]
 
 
 # ---- 5. the refusals of the C call ----------------------------------------------------------------------------------------
