@@ -43,6 +43,9 @@ IFS_MAX_WINDOW_BINS = 64  # FTK_IFS_MAX_WINDOW_BINS
 IFS_MAX_REACH = 1024  # FTK_IFS_MAX_REACH
 IFS_MAX_THR = 4096  # FTK_IFS_MAX_THR
 IFS_MAX_JOIN = 1024  # FTK_IFS_MAX_JOIN
+CONTEXT_MAX_HALF = 128  # FTK_CONTEXT_MAX_HALF
+CONTEXT_MAX_CLASSES = 8  # FTK_CONTEXT_MAX_CLASSES
+CONTEXT_ANCHOR = {"ends": 0, "centre": 1}  # FTK_CONTEXT_ENDS, FTK_CONTEXT_CENTRE
 HOTSPOTS_TILE = 4096  # kCallTile: windows per workgroup of the hotspot passes
 HOTSPOTS_BATCH_TILES = 4096  # kCallBatchTiles: tiles the call plans, counts and writes at a time
 SPECTRUM_TILE = 16 << 10  # kSpectrumLdsSamples: a run of up to this many samples is folded out of LDS, a longer one from memory
@@ -85,6 +88,7 @@ EXPORTS = [
     "ftk_track_peaks", "ftk_wps_peaks",
     "ftk_preferred_ends",
     "ftk_ifs_hotspots", "ftk_ifs_track", "ftk_ifs_totals",
+    "ftk_end_context", "ftk_ref_context", "ftk_end_context_lds_classes",
 ]
 
 
@@ -373,6 +377,9 @@ def load() -> C.CDLL:
                                      + [C.POINTER(vp)] * 8 + [C.POINTER(i64)] + [C.POINTER(vp)] * 9 + [C.POINTER(i64), vp])
     lib.ftk_ifs_track.argtypes = [vp, C.c_int, vp, vp, i64, vp, i64, i32, i32, i32, i32, i32, i32, vp, vp]
     lib.ftk_ifs_totals.argtypes = [vp, C.c_int, i64, i32, i32, i32, C.POINTER(i64), C.POINTER(i64)]
+    lib.ftk_end_context.argtypes = [vp, C.c_int, C.c_int, i32, vp, i32, i32, i32, vp, vp]
+    lib.ftk_ref_context.argtypes = [vp, C.c_int, i64, i64, vp]
+    lib.ftk_end_context_lds_classes.argtypes = [i32]
     lib.ftk_comm_unique_id.argtypes = [C.c_char_p]
     lib.ftk_comm_create.argtypes = [vp, C.c_int, C.c_int, C.c_char_p, C.POINTER(vp)]
     lib.ftk_comm_size.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]

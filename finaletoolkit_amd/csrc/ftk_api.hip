@@ -1440,3 +1440,4 @@ static int wps_params(ftk_ctx* ctx, const ContigData& c, int64_t chrom_size, int
 #include "ftk_api_peaks.inc"
 #include "ftk_api_prefends.inc"
 #include "ftk_api_hotspots.inc"
+#include "ftk_api_endcontext.inc"

@@ -813,6 +813,42 @@ class Engine:
                                               int(stride), L.ptr(table)))
         return table
 
+    # -- end context: base and base-pair profiles around fragment ends (csrc/ftk_endcontext.hip) ----
+    def end_context_lds_classes(self, half_width: int) -> int:
+        """Length classes one workgroup of the end-context kernel keeps in LDS at ``half_width``
+        (``ftk_end_context_lds_classes``); a call with more classes spreads them over further rows of its grid."""
+        return int(self.lib.ftk_end_context_lds_classes(int(half_width)))
+
+    def end_context(self, name: str, rid: int, half_width: int, length_edges, quality_threshold=30, anchor="ends", out=None):
+        """``(table, n_kept)`` of resident contig ``name`` against reference image ``rid`` (``ftk_end_context``; the rule
+        is in ``include/ftk.h``, "end context"): ``table[c, k, o + half_width, 5 * x + y]`` = kept fragments of length
+        class ``c`` (``length_edges[c] <= L < length_edges[c + 1]``) whose reading of kind ``k`` (0: the U end on the +
+        strand, 1: the D end on the - strand; ``anchor="centre"``: the same readings around the fragment's centre) has
+        base ``x`` at offset ``o`` and base ``y`` at ``o + 1`` (A C G T N = 0 .. 4), int64 of shape
+        ``(n_classes, 2, 2 * half_width, 25)``; ``n_kept[c]``: the kept fragments of class ``c``, int64.  ``out``: an
+        int64 host array or device tensor of that many elements to write the table into (returned as passed)."""
+        if anchor not in L.CONTEXT_ANCHOR:
+            raise ValueError(f"invalid anchor ({anchor!r}): 'ends' or 'centre'")
+        edges = np.asarray(length_edges, dtype=np.int64).ravel()
+        if len(edges) < 2 or edges.min() < 1 or edges.max() > 1 << 30:
+            raise ValueError("length_edges: at least two values within [1, 2**30]")
+        edges32 = np.ascontiguousarray(edges, dtype=np.int32)
+        n_classes = len(edges) - 1
+        shape = (n_classes, 2, 2 * max(int(half_width), 0), 25)
+        table = np.empty(shape, np.int64) if out is None else out
+        n_kept = np.empty(n_classes, np.int64)
+        self._check(self.lib.ftk_end_context(self.ctx, self.contig_id(name), int(rid), int(half_width), L.ptr(edges32), n_classes,
+                                             int(quality_threshold), L.CONTEXT_ANCHOR[anchor], L.ptr(table), L.ptr(n_kept)))
+        return table, n_kept
+
+    def ref_context(self, rid: int, pos_lo: int, pos_hi: int) -> np.ndarray:
+        """The background of ``end_context`` (``ftk_ref_context``): int64 ``[25]``, cell ``5 * x + y`` = positions ``p`` of
+        ``[pos_lo, pos_hi)`` inside the contig with base ``x`` at ``p`` and base ``y`` at ``p + 1`` (A C G T N = 0 .. 4; the
+        base behind the contig's end is N)."""
+        out = np.empty(25, np.int64)
+        self._check(self.lib.ftk_ref_context(self.ctx, int(rid), int(pos_lo), int(pos_hi), L.ptr(out)))
+        return out
+
     # -- per-fragment weights and their sums per window (csrc/ftk_weights.hip) ----------
     def set_weights(self, name: str, w):
         """Attach one weight per fragment to resident contig ``name`` (``ftk_frags_set_weights``): uint32 in units of

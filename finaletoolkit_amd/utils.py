@@ -17,7 +17,7 @@ from .exceptions import InvalidInputError
 from .source import get_engine, open_source
 
 __all__ = ["chrom_sizes_to_list", "chrom_sizes_to_dict", "get_intervals", "overlaps", "frags_in_region", "frag_generator",
-           "frag_array", "frag_export", "frag_filter", "frag_gc_coverage", "frag_site_profile", "frag_vplot", "VPlot", "frag_ocf", "OCF", "frag_wps_spectrum", "WpsSpectrum", "frag_wps_peaks", "WpsPeaks", "frag_preferred_ends", "PreferredEnds", "preferred_end_thresholds", "frag_hotspots", "IfsHotspots", "ifs_thresholds", "read_sites", "gc_weights", "read_gc_bias_table", "read_region_mask", "agg_bw", "gen_kmers", "reverse_complement", "validate_compatible_contigs", "valid_interval",
+           "frag_array", "frag_export", "frag_filter", "frag_gc_coverage", "frag_site_profile", "frag_vplot", "VPlot", "frag_ocf", "OCF", "frag_wps_spectrum", "WpsSpectrum", "frag_wps_peaks", "WpsPeaks", "frag_preferred_ends", "PreferredEnds", "preferred_end_thresholds", "frag_hotspots", "IfsHotspots", "ifs_thresholds", "frag_end_context", "EndContext", "read_sites", "gc_weights", "read_gc_bias_table", "read_region_mask", "agg_bw", "gen_kmers", "reverse_complement", "validate_compatible_contigs", "valid_interval",
            "_none_eq", "_none_geq", "_none_leq"]
 
 FragTuple = Tuple[str, int, int, int, bool]
@@ -1663,6 +1663,147 @@ def frag_hotspots(input_file, interval_file=None, chrom_sizes=None, output_file=
         return res, f", {len(hotspots)} hotspots"
     return _over_regions("frag_hotspots", input_file, interval_file, chrom_sizes, workers, verbose, (HOTSPOT_DTYPE, IFS_WINDOW_DTYPE),
                          (8, np.int64), one_contig, finish)
+
+
+class EndContext(NamedTuple):
+    """Result of ``frag_end_context``: base and base-pair counts at every offset of a window around the fragment ends (or
+    centres), per length class and per kind of reading.  Bases are ``A C G T N`` = 0 .. 4."""
+    table: np.ndarray        # int64 (n_classes, 2, 2 * half_width, 25): cell 5 * x + y = base x at offset o, base y at o + 1
+    n_kept: np.ndarray       # int64 per class: the kept fragments; every row table[c, k, j] sums to n_kept[c]
+    background: np.ndarray   # int64 [25]: cell 5 * x + y = reference positions p with base x at p and base y at p + 1
+    half_width: int          # W: offsets run over [-W, W), row j = o + W; o >= 0 lies inside the fragment
+    length_edges: tuple      # class c holds the lengths length_edges[c] <= L < length_edges[c + 1]
+    anchor: str              # "ends": kind 0 = U end on the + strand, kind 1 = D end on the - strand; "centre"
+    skipped_contigs: tuple   # contigs of the input the reference does not hold
+
+    @property
+    def mono(self) -> np.ndarray:
+        """int64 ``(n_classes, 2, 2 * half_width, 5)``: the base at each offset (the marginal over the second base)."""
+        return self.table.reshape(self.table.shape[:-1] + (5, 5)).sum(axis=-1)
+
+    @property
+    def dinuc(self) -> np.ndarray:
+        """int64 ``(n_classes, 2, 2 * half_width, 16)``: cell ``4 * x + y`` of the pairs with both bases defined, in the
+        order ``AA AC AG AT CA ... TT``."""
+        t = self.table.reshape(self.table.shape[:-1] + (5, 5))[..., :4, :4]
+        return np.ascontiguousarray(t).reshape(self.table.shape[:-1] + (16,))
+
+    def background_counts(self, k: int) -> np.ndarray:
+        """int64 ``(2, 4 ** k)``: per kind of reading, how often each motif of ``k`` defined bases is read on that kind's
+        strand of the reference - kind 0: the motif's count on the + strand; kind 1: the count of its reverse complement
+        on the + strand."""
+        bg = np.asarray(self.background, dtype=np.int64).reshape(5, 5)
+        if k == 1:
+            plus = bg.sum(axis=1)[:4]
+            return np.stack([plus, plus[::-1]])
+        if k == 2:
+            plus = bg[:4, :4]
+            return np.stack([plus.reshape(16), plus[::-1, ::-1].T.reshape(16)])
+        raise ValueError(f"invalid k ({k}): 1 or 2")
+
+    def frequency(self, k: int) -> np.ndarray:
+        """float64 ``(n_classes, 2, 2 * half_width, 4 ** k)``: ``count[m] / sum(count[m'] for the 4 ** k defined motifs
+        m')`` per row, ``count`` = ``mono[..., :4]`` (k = 1) or ``dinuc`` (k = 2); NaN where a row has no defined motif."""
+        if k not in (1, 2):
+            raise ValueError(f"invalid k ({k}): 1 or 2")
+        count = (self.mono[..., :4] if k == 1 else self.dinuc).astype(np.float64)
+        total = count.sum(axis=-1, keepdims=True)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return np.where(total > 0, count / total, np.nan)
+
+    def enrichment(self, k: int) -> np.ndarray:
+        """float64 ``(n_classes, 2, 2 * half_width, 4 ** k)``:
+        ``enrichment[c, kind, j, m] = frequency(k)[c, kind, j, m] / (B[kind, m] / B[kind].sum())`` with ``B =
+        background_counts(k)`` - the motif's frequency among the defined motifs of its row over its frequency among the
+        defined motifs of the reference read on the same strand (kind 1: the reverse complement's count on the + strand).
+        NaN where the row has no defined motif, the background has none, or ``B[kind, m] == 0``."""
+        freq = self.frequency(k)
+        b = self.background_counts(k).astype(np.float64)
+        tot = b.sum(axis=-1, keepdims=True)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            bf = np.where((tot > 0) & (b > 0), b / tot, np.nan)
+            return freq / bf[None, :, None, :]
+
+
+def _check_end_context_args(output_file, half_width, length_edges, anchor):
+    from . import _lib as L
+    from . import writers
+    if not 1 <= int(half_width) <= L.CONTEXT_MAX_HALF:
+        raise ValueError(f"invalid half_width ({half_width}): 1 .. {L.CONTEXT_MAX_HALF}")
+    edges = tuple(int(v) for v in length_edges)
+    if not 2 <= len(edges) <= L.CONTEXT_MAX_CLASSES + 1:
+        raise ValueError(f"invalid length_edges: 2 .. {L.CONTEXT_MAX_CLASSES + 1} values bound 1 .. {L.CONTEXT_MAX_CLASSES} classes")
+    if edges[0] < 1 or edges[-1] > 1 << 30 or any(b <= a for a, b in zip(edges, edges[1:])):
+        raise ValueError(f"invalid length_edges {edges}: strictly ascending within [1, 2**30]")
+    if anchor not in L.CONTEXT_ANCHOR:
+        raise ValueError(f"invalid anchor ({anchor!r}): 'ends' or 'centre'")
+    if output_file is not None and not str(output_file).endswith(writers.END_CONTEXT_SUFFIXES):
+        raise ValueError("output_file should have .tsv or .tsv.gz as suffix")
+    return edges
+
+
+def frag_end_context(input_file, reference_file, output_file=None, contig=None, quality_threshold: int = 30, half_width: int = 32,
+                     length_edges=(1, 150, 221, 1001), anchor: str = "ends", workers=None, verbose=False) -> EndContext:
+    """Nucleotide and dinucleotide profiles around the fragment ends of ``input_file`` against ``reference_file``
+    (``.2bit`` or FASTA), per fragment length class: the first figure of a cfDNA cleavage analysis and the first QC plot
+    of library-prep end bias.  Counted on the GPU in one pass per contig as the input is decoded.
+
+    A fragment ``[s, e)`` of length ``L`` with ``mapq >= quality_threshold`` and ``length_edges[0] <= L <
+    length_edges[-1]`` belongs to the class ``c`` with ``length_edges[c] <= L < length_edges[c + 1]`` (at most 8 classes)
+    and gives two readings over the offsets ``o`` of ``[-half_width, half_width]``: kind 0 ``= base(s + o)``, the U end read
+    5'->3' on the + strand, and kind 1 ``= complement(base(e - 1 - o))``, the D end read 5'->3' on the - strand.  ``o >= 0``
+    lies inside the fragment, ``o < 0`` in front of it.  ``anchor="centre"`` takes the same readings around ``s + L // 2`` and
+    ``e - 1 - L // 2`` instead.  ``table[c, kind, o + half_width, 5 * x + y]`` counts the readings with base ``x`` at ``o``
+    and ``y`` at ``o + 1`` (``A C G T N`` = 0 .. 4; N: outside the contig, a 2bit N block, or a FASTA byte other than
+    ACGTacgt).  ``background[5 * x + y]`` counts the reference positions of the contigs used in the same way.
+
+    Contigs of the input that the reference lacks are skipped with one ``UserWarning`` and listed in ``skipped_contigs``.
+    Returns an ``EndContext``: see its ``mono``, ``dinuc``, ``frequency(k)`` and ``enrichment(k)``.  ``output_file`` (``.tsv``
+    / ``.tsv.gz``): ``writers.write_end_context_rows``."""
+    import os
+    import sys
+    import time
+    import warnings
+
+    from . import writers
+    from .reference import ReferenceGenome
+    from .source import ContigFeed
+    edges = _check_end_context_args(output_file, half_width, length_edges, anchor)
+    w = int(half_width)
+    t0 = time.time()
+    eng = get_engine()
+    feed = ContigFeed(input_file, workers, names=None if contig is None else [str(contig)])
+    table = np.zeros((len(edges) - 1, 2, 2 * w, 25), np.int64)
+    n_kept = np.zeros(len(edges) - 1, np.int64)
+    background = np.zeros(25, np.int64)
+    missing = []
+    try:
+        with ReferenceGenome(reference_file) as ref:
+            for src, c in feed:
+                if c not in ref.chroms:
+                    missing.append(c)
+                    continue
+                rid = ref.device_image(eng, c, with_layout=True)
+                t, k = eng.end_context(src.key(c), rid, w, edges, quality_threshold, anchor)
+                table += t
+                n_kept += k
+                background += eng.ref_context(rid, 0, ref.chroms[c])
+                if verbose:
+                    sys.stderr.write(f"frag_end_context: {c}: {int(k.sum())} fragments\n")
+            src = feed.finish()
+    except BaseException:
+        feed.close()
+        raise
+    if contig is not None and str(contig) not in feed.seen:
+        src.require(str(contig))  # not in the file: the ValueError of every other command
+    if missing:
+        warnings.warn("frag_end_context: contigs not in the reference were skipped: " + ", ".join(missing), UserWarning)
+    res = EndContext(table, n_kept, background, w, edges, str(anchor), tuple(missing))
+    if output_file is not None:
+        writers.write_end_context_rows(os.fspath(output_file), res)
+    if verbose:
+        sys.stderr.write(f"frag_end_context: {int(n_kept.sum())} fragments in {time.time() - t0:.3f} s\n")
+    return res
 
 
 def agg_bw(input_file, interval_file, output_file, median_window_size: int = 1, mean: bool = False,

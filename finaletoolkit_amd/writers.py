@@ -512,3 +512,41 @@ def write_hotspot_summary(output_file: str, res) -> None:
         rows.append("\t".join([str(c), str(a), str(b), str(name), str(int(L)), "nan" if gm == 0 else format(int(gm) / 1024.0, ".6g")]
                               + [str(int(x)) for x in stats]) + "\n")
     _emit(output_file, "".join(rows), (".tsv",), (".tsv.gz",), message)
+
+
+END_CONTEXT_SUFFIXES = (".tsv", ".tsv.gz")
+END_CONTEXT_HEADER = "length_lo\tlength_hi\tend\toffset\tmotif\tcount\tfrequency\tenrichment\n"
+END_CONTEXT_MOTIFS = tuple("ACGTN") + tuple(a + b for a in "ACGT" for b in "ACGT")
+
+
+def end_context_text(res) -> str:
+    """The rows of a ``utils.EndContext``: the header ``length_lo length_hi end offset motif count frequency enrichment``,
+    then, per length class ``[length_lo, length_hi)``, per end (``U`` / ``D``; ``+`` / ``-`` when the anchor is the
+    centre) and per offset, the motifs ``A C G T N`` and ``AA AC ... TT`` that have a count or a background count (N: the
+    reference's N positions).  ``frequency`` and ``enrichment`` are ``repr(float)`` of ``res.frequency(k)`` and
+    ``res.enrichment(k)``, ``nan`` where they are undefined and for N."""
+    w = int(res.half_width)
+    mono, dinuc = res.mono, res.dinuc
+    count = np.concatenate([mono, dinuc], axis=-1)
+    nan = np.full(mono.shape[:-1] + (1,), np.nan)
+    freq = np.concatenate([res.frequency(1), nan, res.frequency(2)], axis=-1)
+    enr = np.concatenate([res.enrichment(1), nan, res.enrichment(2)], axis=-1)
+    bg_n = int(np.asarray(res.background).reshape(5, 5)[4].sum())
+    bg = np.concatenate([res.background_counts(1), np.full((2, 1), bg_n, np.int64), res.background_counts(2)], axis=-1)
+    ends = "UD" if res.anchor == "ends" else "+-"
+    rows = [END_CONTEXT_HEADER]
+    for c in range(count.shape[0]):
+        for k in range(2):
+            head = f"{int(res.length_edges[c])}\t{int(res.length_edges[c + 1])}\t{ends[k]}\t"
+            for j in range(2 * w):
+                rows += [f"{head}{j - w}\t{END_CONTEXT_MOTIFS[m]}\t{int(count[c, k, j, m])}\t{float(freq[c, k, j, m])!r}\t{float(enr[c, k, j, m])!r}\n"
+                         for m in np.flatnonzero((count[c, k, j] > 0) | (bg[k] > 0))]
+    return "".join(rows)
+
+
+def write_end_context_rows(output_file: str, res) -> None:
+    """``end_context_text`` to ``output_file``: ``.tsv`` as text, ``.tsv.gz`` as gzip."""
+    message = "output_file should have .tsv or .tsv.gz as suffix"
+    if not output_file.endswith(END_CONTEXT_SUFFIXES):
+        raise ValueError(message)
+    _emit(output_file, end_context_text(res), (".tsv",), (".tsv.gz",), message)

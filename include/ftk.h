@@ -1054,6 +1054,52 @@ int ftk_ifs_track(ftk_ctx* ctx, int contig_id, const int64_t* iv_start, const in
 int ftk_ifs_totals(ftk_ctx* ctx, int contig_id, int64_t chrom_size, int32_t min_len, int32_t max_len, int32_t mapq_min,
                    int64_t* n_frags, int64_t* len_sum);
 
+/* ---- end context: nucleotide and dinucleotide profiles around fragment ends (csrc/ftk_endcontext.hip) --------
+ * The figure cfDNA cleavage papers start from: the frequency of every base and base pair at each position of a window
+ * around the fragment ends (or centres), in front of and inside the fragment, per fragment length class.
+ *
+ * Bases.  base(q) of a reference image that has its layout (ftk_ref_set_layout) is A = 0, C = 1, G = 2, T = 3 (either
+ * case; the ACGT order of gen_kmers), and 4, written N, when q < 0, q >= chrom_len, or the base IS N by the rule of the
+ * GC section above (a base of a 2bit N block; a FASTA byte other than ACGTacgt).  comp(x) = 3 - x for x < 4, comp(4) = 4.
+ *
+ * Which fragments count.  len_edges holds n_classes + 1 strictly ascending values, 1 <= len_edges[0] and
+ * len_edges[n_classes] <= 2^30 (a HOST array).  A fragment [s, e) with L = e - s is kept when mapq >= mapq_min and
+ * len_edges[0] <= L < len_edges[n_classes]; its class c is the one with len_edges[c] <= L < len_edges[c + 1].  There is
+ * no other length bound: only the neighbourhood of the anchors is read.
+ *
+ * Readings.  Every kept fragment gives two oriented readings, for o in [-W, W], W = half_width:
+ *    kind 0:  r0(o) = base(a0 + o)
+ *    kind 1:  r1(o) = comp(base(a1 - o))
+ *    FTK_CONTEXT_ENDS     a0 = s,            a1 = e - 1              the U end read 5'->3' on the + strand, the D end
+ *                                                                    read 5'->3' on the - strand
+ *    FTK_CONTEXT_CENTRE   a0 = s + (L >> 1), a1 = e - 1 - (L >> 1)   the same readings around the fragment's centre
+ * In both modes o >= 0 lies inside the fragment and o < 0 in front of it; for kind 1 this is the orientation
+ * ftk_motif_counts uses for its reverse k-mer.  Offsets may run past the fragment's other end (L < W): that is reference
+ * sequence and is counted.
+ *
+ * The table.  out[c][k][o + W][5 rk(o) + rk(o + 1)] += 1 for every o of [-W, W): int64 of shape [n_classes][2][2 W][25].
+ * The mononucleotide profile is the marginal over the second base, the dinucleotide profile the 16 cells with both bases
+ * below 4.  n_kept_out[c] = kept fragments of class c, so every row out[c][k][j] sums to n_kept_out[c].
+ *   ftk_end_context   the table and n_kept_out[n_classes] of a resident contig; outputs host or device, every cell
+ *                     written by the call; an empty contig gives zeros.
+ *   ftk_ref_context   the background: out25[5 a + b] = positions p of [pos_lo, pos_hi) within [0, chrom_len) with
+ *                     base(p) = a and base(p + 1) = b.  The tables of two halves of a range sum to the table of the
+ *                     range; pos_hi > chrom_len is allowed.
+ *   ftk_end_context_lds_classes   classes one workgroup keeps in LDS at that width (the further classes of a call go to
+ *                     further rows of the grid); 0 for a width outside [1, FTK_CONTEXT_MAX_HALF].
+ * FTK_ERR_INVALID: a NULL pointer, a reference without layout, chrom_len >= 2^30, half_width outside
+ * [1, FTK_CONTEXT_MAX_HALF], n_classes outside [1, FTK_CONTEXT_MAX_CLASSES], edges not strictly ascending or outside
+ * their bounds, an unknown anchor, pos_lo < 0, pos_hi < pos_lo; FTK_ERR_NO_CONTIG: an unknown contig or reference.  A
+ * failing call writes nothing. */
+#define FTK_CONTEXT_MAX_HALF 128
+#define FTK_CONTEXT_MAX_CLASSES 8
+#define FTK_CONTEXT_ENDS 0
+#define FTK_CONTEXT_CENTRE 1
+int ftk_end_context(ftk_ctx* ctx, int contig_id, int ref_id, int32_t half_width, const int32_t* len_edges /* host */,
+                    int32_t n_classes, int32_t mapq_min, int32_t anchor, int64_t* out, int64_t* n_kept_out);
+int ftk_ref_context(ftk_ctx* ctx, int ref_id, int64_t pos_lo, int64_t pos_hi, int64_t* out25);
+int ftk_end_context_lds_classes(int32_t half_width);
+
 /* ---- multi-GPU (SURVEY 8-e, 8-b's export list) -------------------------------------------------
  * One process and one ftk_ctx per GPU.  Contigs / genome runs are dealt to the ranks by the host and every window,
  * bin and base depends on its own contig's fragments only, so the data path has no collective.  What remains are the

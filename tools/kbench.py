@@ -16,7 +16,10 @@ KBENCH=prefends: preferred ends of the whole contig at h = 500 and h = 2048, com
 ftk_cleavage of the same region (the same tile skeleton), with the call's byte floor.
 KBENCH=hotspots: IFS hotspots of the whole contig at the defaults (20-base step, 200-base windows, 5 kb / 10 kb backgrounds,
 alpha = 1e-5) - the whole call, the totals reduction, the per-window track into device arrays - beside preferred ends combined
-at h = 500 on the same contig, with the call's byte floor."""
+at h = 500 on the same contig, with the call's byte floor.
+KBENCH=endcontext: the end-context table at W = 32 with the default length classes against the 2bit image of KBENCH=gcbias, in both
+LDS arrangements (lanes are offsets / lanes are fragments), beside ftk_frag_gc_table on the same contig and image and beside the
+route there was before: 64 calls of ftk_motif_counts, one per offset; and the background, ftk_ref_context of the whole image."""
 import os
 import sys
 
@@ -724,3 +727,40 @@ if "motif" in which:
     c, nf, er = eng.motif_counts("c", rid2, mws, mwe, 4, 0, -4, True, False, 0, False, 30)
     print("motif total", int(c.sum()), "fragments", int(nf.sum()))
 print("wps checksum", int(out[:5_000_000].sum().item()), "cov", int(cov.sum().item()))
+if "endcontext" in which:
+    # End context at W = 32, classes (1, 150, 221, 1001), against the 2bit image of KBENCH=gcbias: the whole call (table zeroed,
+    # kernel, 77 KB copied to the host).  The work is LDS updates, not bytes: 2 kinds x 2 W offsets per kept fragment, one
+    # returnless 32-bit LDS add each.  The estimate it is held against: a 64-lane LDS add takes 4 LDS cycles of a CU (the rate
+    # of a 32-bit LDS write), so 16 updates per clock and CU at 2.4 GHz.  The byte figure printed is the columns + the image.
+    rng = np.random.default_rng(7)
+    packed = rng.integers(0, 256, (size + 3) // 4, dtype=np.uint8)
+    ride = eng.ref_upload(("kb", "gcbias2bit"), packed, 1)
+    eng.ref_set_layout(ride, size, 0, 0, [10_000_000], [10_050_000])
+    img = (size + 3) // 4
+    W, EDGES = 32, (1, 150, 221, 1001)
+    n_cu = torch.cuda.get_device_properties(0).multi_processor_count
+    lds_rate = 16 * n_cu * 2.4e9
+
+    def context(arrange):
+        os.environ["FTK_CONTEXT_ARRANGE"] = arrange
+        return eng.end_context("c", ride, W, EDGES, 30, "ends")
+
+    def motif_route():
+        for o in range(-W, W):
+            eng.motif_counts("c", ride, [0], [size], 2, o, -o - 2, True, False, 0, False, 30)
+
+    tables = {a: context(a) for a in ("0", "1")}
+    assert np.array_equal(tables["0"][0], tables["1"][0]) and np.array_equal(tables["0"][1], tables["1"][1])
+    table, kept = tables["0"]
+    updates = 2 * 2 * W * int(kept.sum())
+    print(f"endcontext: {n} fragments, {int(kept.sum())} kept, {updates} LDS updates, image {img} B, {n_cu} CUs: "
+          f"{updates / lds_rate * 1e6:.1f} us at the estimated LDS rate", flush=True)
+    for _ in range(2):  # twice: the spread between the two passes is the noise
+        timeit(lambda: context("0"), "end context, lanes=offsets", 9 * n + img)
+        timeit(lambda: context("1"), "end context, lanes=frags", 9 * n + img)
+        timeit(lambda: eng.frag_gc_table("c", ride, 100, 220, 30), "observed GC table 100-220", 9 * n + img)
+        timeit(motif_route, "64 x motif_counts (k=2)", 64 * 9 * n)
+        timeit(lambda: eng.ref_context(ride, 0, size), "ref context (background)", img)
+    del os.environ["FTK_CONTEXT_ARRANGE"]
+    print("endcontext checksum", int(table.sum()), int(table[..., 20:].sum()), int(eng.ref_context(ride, 0, size).sum()),
+          "(share of the LDS estimate = the us above / the measured us)")
