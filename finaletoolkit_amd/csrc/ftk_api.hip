@@ -107,6 +107,10 @@ int reserve_scratch(ftk_ctx* ctx, size_t bytes) {
 // the device address each variable gets (the user's own array when that is on the device), the copies finish() issues.
 // place() writes through the addresses the declarations named: those variables (and the structs that hold them) must
 // not be copied or moved between their declaration and reserve() / place().
+// One 64-bit output of a call: `cells` cells at `user` (host or device; NULL or no cells: not asked for), reached on the
+// device through *dev, which stays NULL when it was not asked for.
+struct CellsOut { int64_t** dev; int64_t* user; size_t cells; };
+
 class Scratch {
   public:
     explicit Scratch(ftk_ctx* ctx, size_t prefix = 0) : ctx_(ctx), bytes_(prefix) {}
@@ -128,6 +132,15 @@ class Scratch {
     size_t bytes() const { return bytes_; }
     // once per call, before any of the declared variables is read
     int reserve() { const int rc = reserve_scratch(ctx_, bytes_); return rc ? rc : place(); }
+    // the table and site calls' step: these outputs declared (behind the call's other buffers), reserve(), those asked for zeroed
+    int reserve_zeroed(std::initializer_list<CellsOut> outs) {
+        for (const CellsOut& o : outs)
+            if (o.user && o.cells) out(o.dev, o.user, o.cells);
+        if (const int rc = reserve()) return rc;
+        for (const CellsOut& o : outs)
+            if (*o.dev) HIPCHK(ctx_, hipMemsetAsync(*o.dev, 0, o.cells * 8, ctx_->stream));
+        return FTK_OK;
+    }
     // (on its own: for buffers inside the prefix that another Scratch's reserve() made room for)
     int place() {
         if (n_ > kMaxBufs) return fail(ctx_, FTK_ERR_INVALID, "more than %d scratch buffers in one call", kMaxBufs);
@@ -163,6 +176,16 @@ class Scratch {
     Buf bufs_[kMaxBufs];
     int n_ = 0;
 };
+
+// The tail of a table call (the GC tables, the GC weights, the end-context tables): `outs` get their place beside what the
+// call has declared on `s` and are zeroed, launch() enqueues the work and returns an error code, the outputs go home.
+template <class Launch>
+int run_table_call(ftk_ctx* ctx, Scratch& s, std::initializer_list<CellsOut> outs, Launch&& launch, bool must_sync = false) {
+    int rc = s.reserve_zeroed(outs);
+    if (rc || (rc = launch())) return rc;
+    HIPCHK(ctx, hipGetLastError());
+    return s.finish(must_sync);
+}
 
 struct SyncOnExit {  // pageable staging of this frame may be in flight on any way out
     ftk_ctx* ctx;

@@ -47,37 +47,27 @@ int ftk_end_context(ftk_ctx* ctx, int contig_id, int ref_id, int32_t half_width,
     HIPCHK(ctx, hipSetDevice(ctx->device));
     int64_t *d_out = nullptr, *d_kept = nullptr;
     Scratch s(ctx);
-    s.out(&d_out, out, cells);
-    s.out(&d_kept, n_kept_out, (size_t)n_classes);
-    if ((rc = s.reserve())) return rc;
-    HIPCHK(ctx, hipMemsetAsync(d_out, 0, cells * 8, ctx->stream));
-    HIPCHK(ctx, hipMemsetAsync(d_kept, 0, (size_t)n_classes * 8, ctx->stream));
-    launch_end_context(ctx->stream, ctx->n_cu, c->v, im, p, end_context_arrangement(), (unsigned long long*)d_out,
-                       (unsigned long long*)d_kept);
-    HIPCHK(ctx, hipGetLastError());
-    return s.finish();
+    return run_table_call(ctx, s, {{&d_out, out, cells}, {&d_kept, n_kept_out, (size_t)n_classes}}, [&] {
+        launch_end_context(ctx->stream, ctx->n_cu, c->v, im, p, end_context_arrangement(), (unsigned long long*)d_out,
+                           (unsigned long long*)d_kept);
+        return FTK_OK;
+    });
 }
 
 int ftk_ref_context(ftk_ctx* ctx, int ref_id, int64_t pos_lo, int64_t pos_hi, int64_t* out25) {
     if (!ctx) return fail(nullptr, FTK_ERR_INVALID, "ctx is NULL");
     if (!out25) return fail(ctx, FTK_ERR_INVALID, "out25 is NULL");
     RefView im;
-    const int rc0 = open_gc_view(ctx, ref_id, &im);
-    if (rc0) return rc0;
-    if (pos_lo < 0 || pos_hi < pos_lo) return fail(ctx, FTK_ERR_INVALID, "positions [%lld, %lld) are not a range", (long long)pos_lo, (long long)pos_hi);
+    int64_t hi;
+    int rc = open_gc_view(ctx, ref_id, &im);
+    if (rc || (rc = check_ref_range(ctx, im, pos_lo, pos_hi, &hi))) return rc;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     int64_t* d_out = nullptr;
     Scratch s(ctx);
-    s.out(&d_out, out25, (size_t)kCtxCellsPerRow);
-    int rc = s.reserve();
-    if (rc) return rc;
-    HIPCHK(ctx, hipMemsetAsync(d_out, 0, kCtxCellsPerRow * 8, ctx->stream));
-    const int64_t hi = std::min<int64_t>(pos_hi, im.chrom_len);
-    if (pos_lo < hi) {
-        launch_ref_context(ctx->stream, ctx->n_cu, im, (int)pos_lo, (int)hi, (unsigned long long*)d_out);
-        HIPCHK(ctx, hipGetLastError());
-    }
-    return s.finish();
+    return run_table_call(ctx, s, {{&d_out, out25, (size_t)kCtxCellsPerRow}}, [&] {
+        if (pos_lo < hi) launch_ref_context(ctx->stream, ctx->n_cu, im, (int)pos_lo, (int)hi, (unsigned long long*)d_out);
+        return FTK_OK;
+    });
 }
 
 }  // extern "C"

@@ -19,6 +19,14 @@ int check_gc_lengths(ftk_ctx* ctx, int32_t len_lo, int32_t len_hi) {
     return FTK_OK;
 }
 
+// A reference call's positions [pos_lo, pos_hi) must be a range; *hi: its end clamped to the contig's (nothing is defined
+// at or behind the contig's end), so the call launches when pos_lo < *hi.
+int check_ref_range(ftk_ctx* ctx, const RefView& im, int64_t pos_lo, int64_t pos_hi, int64_t* hi) {
+    *hi = std::min<int64_t>(pos_hi, im.chrom_len);
+    if (pos_lo >= 0 && pos_hi >= pos_lo) return FTK_OK;
+    return fail(ctx, FTK_ERR_INVALID, "positions [%lld, %lld) are not a range", (long long)pos_lo, (long long)pos_hi);
+}
+
 size_t gc_table_cells(int32_t len_lo, int32_t len_hi) { return (size_t)(len_hi - len_lo + 1) * (size_t)(len_hi + 1); }
 
 }  // namespace
@@ -41,11 +49,11 @@ int ftk_frag_gc(ftk_ctx* ctx, int contig_id, int ref_id, int32_t min_len, int32_
     HIPCHK(ctx, hipSetDevice(ctx->device));
     int16_t* d_out = nullptr;
     Scratch s(ctx);
-    s.out(&d_out, gc_out, (size_t)c->n);
-    if ((rc = s.reserve())) return rc;
-    launch_frag_gc(ctx->stream, ctx->n_cu, c->v, im, p, d_out, nullptr, nullptr);
-    HIPCHK(ctx, hipGetLastError());
-    return s.finish();
+    s.out(&d_out, gc_out, (size_t)c->n);  // (every row is written: nothing to zero)
+    return run_table_call(ctx, s, {}, [&] {
+        launch_frag_gc(ctx->stream, ctx->n_cu, c->v, im, p, d_out, nullptr, nullptr);
+        return FTK_OK;
+    });
 }
 
 int ftk_frag_gc_table(ftk_ctx* ctx, int contig_id, int ref_id, int32_t len_lo, int32_t len_hi, int32_t mapq_min,
@@ -56,19 +64,14 @@ int ftk_frag_gc_table(ftk_ctx* ctx, int contig_id, int ref_id, int32_t len_lo, i
     RefView im;
     int rc = get_contig(ctx, contig_id, &c);
     if (rc || (rc = open_gc_view(ctx, ref_id, &im)) || (rc = check_gc_lengths(ctx, len_lo, len_hi))) return rc;
-    const size_t cells = gc_table_cells(len_lo, len_hi);
     HIPCHK(ctx, hipSetDevice(ctx->device));
     int64_t *d_table = nullptr, *d_skipped = nullptr;
     Scratch s(ctx);
-    s.out(&d_table, table_out, cells);
-    s.out(&d_skipped, n_skipped, 1);
-    if ((rc = s.reserve())) return rc;
-    HIPCHK(ctx, hipMemsetAsync(d_table, 0, cells * 8, ctx->stream));
-    HIPCHK(ctx, hipMemsetAsync(d_skipped, 0, 8, ctx->stream));
-    FragGcParams p{len_lo, len_hi, mapq_min, len_lo, len_hi, len_lo};
-    launch_frag_gc(ctx->stream, ctx->n_cu, c->v, im, p, nullptr, (unsigned long long*)d_table, (unsigned long long*)d_skipped);
-    HIPCHK(ctx, hipGetLastError());
-    return s.finish();
+    return run_table_call(ctx, s, {{&d_table, table_out, gc_table_cells(len_lo, len_hi)}, {&d_skipped, n_skipped, 1}}, [&] {
+        FragGcParams p{len_lo, len_hi, mapq_min, len_lo, len_hi, len_lo};
+        launch_frag_gc(ctx->stream, ctx->n_cu, c->v, im, p, nullptr, (unsigned long long*)d_table, (unsigned long long*)d_skipped);
+        return FTK_OK;
+    });
 }
 
 int ftk_ref_gc_table(ftk_ctx* ctx, int ref_id, int64_t pos_lo, int64_t pos_hi, int32_t len_lo, int32_t len_hi, int64_t stride,
@@ -79,23 +82,18 @@ int ftk_ref_gc_table(ftk_ctx* ctx, int ref_id, int64_t pos_lo, int64_t pos_hi, i
     int rc = open_gc_view(ctx, ref_id, &im);
     if (rc || (rc = check_gc_lengths(ctx, len_lo, len_hi))) return rc;
     if (stride < 1) return fail(ctx, FTK_ERR_INVALID, "stride %lld is below 1", (long long)stride);
-    if (pos_lo < 0 || pos_hi < pos_lo) return fail(ctx, FTK_ERR_INVALID, "positions [%lld, %lld) are not a range", (long long)pos_lo, (long long)pos_hi);
-    const size_t cells = gc_table_cells(len_lo, len_hi);
+    int64_t hi;
+    if ((rc = check_ref_range(ctx, im, pos_lo, pos_hi, &hi))) return rc;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     int64_t* d_table = nullptr;
     Scratch s(ctx);
-    s.out(&d_table, table_out, cells);
-    if ((rc = s.reserve())) return rc;
-    HIPCHK(ctx, hipMemsetAsync(d_table, 0, cells * 8, ctx->stream));
-    // a window that starts at or behind the contig's end is undefined; of the multiples of a stride of 2^30 or more only
-    // position 0 lies below the coordinate bound
-    const int64_t hi = std::min<int64_t>(pos_hi, im.chrom_len);
-    if (pos_lo < hi) {
-        launch_ref_gc_table(ctx->stream, ctx->n_cu, im, (int)pos_lo, (int)hi, len_lo, len_hi, std::min<int64_t>(stride, 1LL << 30),
-                            (unsigned long long*)d_table);
-        HIPCHK(ctx, hipGetLastError());
-    }
-    return s.finish();
+    return run_table_call(ctx, s, {{&d_table, table_out, gc_table_cells(len_lo, len_hi)}}, [&] {
+        // (of the multiples of a stride of 2^30 or more only position 0 lies below the coordinate bound)
+        if (pos_lo < hi)
+            launch_ref_gc_table(ctx->stream, ctx->n_cu, im, (int)pos_lo, (int)hi, len_lo, len_hi, std::min<int64_t>(stride, 1LL << 30),
+                                (unsigned long long*)d_table);
+        return FTK_OK;
+    });
 }
 
 }  // extern "C"

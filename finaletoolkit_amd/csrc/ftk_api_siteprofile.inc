@@ -73,7 +73,7 @@ struct SitePlan {
         }
         run_off.push_back((int32_t)n_sites);
     }
-    // (behind the call's outputs; the plan must not move between this and Scratch::reserve)
+    // (in front of the call's outputs; the plan must not move between this and Scratch::reserve)
     void declare(Scratch& s) {
         if (!n_runs()) return;
         s.tmp(&d_words, words.size());
@@ -91,27 +91,15 @@ struct SitePlan {
     }
 };
 
-// One output of a site call: `cells` 64-bit cells at `user` (host or device; NULL or no cells: not asked for), reached
-// on the device through *dev.
-struct SiteOut {
-    int64_t** dev;
-    int64_t* user;
-    size_t cells;
-};
-
 // The tail every site call ends with: the outputs and the plan get their place in the scratch, the outputs are zeroed,
 // the plan goes up, and launch(r0, part) is called for runs [r0, r0 + part) - at most kSiteMaxRunsPerLaunch workgroups
 // per launch, a run being groups_per_run of them, so that a grid of any workgroup size stays below 2^32 threads.
 template <class Launch>
-int run_site_call(ftk_ctx* ctx, SitePlan& plan, std::initializer_list<SiteOut> outs, size_t groups_per_run, Launch&& launch) {
+int run_site_call(ftk_ctx* ctx, SitePlan& plan, std::initializer_list<CellsOut> outs, size_t groups_per_run, Launch&& launch) {
     Scratch s(ctx);
-    for (const SiteOut& o : outs)
-        if (o.user && o.cells) s.out(o.dev, o.user, o.cells);
     plan.declare(s);
     int rc;
-    if ((rc = s.reserve())) return rc;
-    for (const SiteOut& o : outs)
-        if (*o.dev) HIPCHK(ctx, hipMemsetAsync(*o.dev, 0, o.cells * 8, ctx->stream));
+    if ((rc = s.reserve_zeroed(outs))) return rc;
     // From here on the stream may be reading the plan's vectors (pageable staging of this call): every way out, an
     // error's included, waits for the stream first.
     auto enqueue = [&]() -> int {

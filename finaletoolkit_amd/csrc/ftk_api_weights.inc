@@ -75,16 +75,15 @@ int ftk_frags_set_gc_weights(ftk_ctx* ctx, int contig_id, int ref_id, int32_t le
     int64_t* d_zero = nullptr;
     Scratch s(ctx);
     s.tmp(&d_packed, cells);
-    s.out(&d_zero, n_zero_out, 1);
-    if ((rc = s.reserve()) || (rc = ensure_weights(ctx, c))) return rc;
-    HIPCHK(ctx, hipMemsetAsync(d_zero, 0, 8, ctx->stream));
-    if (c->n > 0) {
-        HIPCHK(ctx, hipMemcpyAsync(d_packed, packed.data(), cells * 4, hipMemcpyHostToDevice, ctx->stream));
-        GcWeightParams p{len_lo, len_hi, mapq_min, 0, 0};
-        launch_frag_gc_weights(ctx->stream, ctx->n_cu, c->v, im, p, d_packed, c->weights, (unsigned long long*)d_zero);
-        HIPCHK(ctx, hipGetLastError());
-    }
-    return s.finish(true);  // (`packed` is pageable staging of this call)
+    return run_table_call(ctx, s, {{&d_zero, n_zero_out, 1}}, [&]() -> int {
+        if (const int e = ensure_weights(ctx, c)) return e;
+        if (c->n > 0) {
+            HIPCHK(ctx, hipMemcpyAsync(d_packed, packed.data(), cells * 4, hipMemcpyHostToDevice, ctx->stream));
+            GcWeightParams p{len_lo, len_hi, mapq_min, 0, 0};
+            launch_frag_gc_weights(ctx->stream, ctx->n_cu, c->v, im, p, d_packed, c->weights, (unsigned long long*)d_zero);
+        }
+        return FTK_OK;
+    }, true);  // (`packed` is pageable staging of this call)
 }
 
 int ftk_weighted_window_sums(ftk_ctx* ctx, int contig_id, const int32_t* w_start, const int32_t* w_end, int64_t n_win,

@@ -1,6 +1,6 @@
 // Nucleotide and dinucleotide profiles around fragment ends (ftk_end_context) and their background (ftk_ref_context):
 // the rule is in include/ftk.h under "end context".  base(q) = A 0, C 1, G 2, T 3 or N 4 of a reference image resident in
-// HBM; every kept fragment gives two oriented readings r0(o) = base(a0 + o), r1(o) = comp(base(a1 - o)) and adds one to
+// HBM (ref_base, ftk_device.h); every kept fragment gives two oriented readings r0(o) = base(a0 + o), r1(o) = comp(base(a1 - o)) and adds one to
 // out[class][kind][o + W][5 r(o) + r(o + 1)] for every o of [-W, W).
 //
 // Both kernels keep the classes of one row of the grid in a workgroup's LDS block of 32-bit cells (a workgroup sees fewer
@@ -26,7 +26,7 @@
 //
 // A window is CLEAN when the image is 2bit and its 2W + 1 bases lie inside the contig and outside every N block (one binary
 // search per end): both bases of a pair then come out of two adjacent bytes.  Every other window - FASTA text included -
-// reads base by base through ctx_base.
+// reads base by base through ref_base.
 #include <algorithm>
 #include <cstdlib>
 
@@ -38,21 +38,6 @@ namespace ftk {
 namespace {
 
 constexpr int kCtxWaves = kCtxThreads / 64;
-
-// A 0, C 1, G 2, T 3 of a 2bit code (T 0, C 1, A 2, G 3)
-__device__ __forceinline__ int acgt_of_2bit(uint32_t c) { return (int)((0x87u >> (2 * c)) & 3u); }
-
-// base(q) of the rule, for any q
-__device__ __forceinline__ int ctx_base(const RefView& im, int q) {
-    if (q < 0 || q >= im.chrom_len) return 4;
-    if (im.kind == FTK_REF_2BIT) {
-        if (im.n_nblk && ref_has_n(im, q, q + 1)) return 4;
-        return acgt_of_2bit(twobit_code(im.img[q >> 2], q));
-    }
-    int col;
-    const int ch = im.img[ref_text_offset(im, q, col)] & 0xDF;  // fold case
-    return ch == 'A' ? 0 : ch == 'C' ? 1 : ch == 'G' ? 2 : ch == 'T' ? 3 : 4;
-}
 
 __device__ __forceinline__ int ctx_comp(int x) { return x < 4 ? 3 - x : 4; }
 
@@ -71,8 +56,8 @@ __device__ __forceinline__ int ctx_cell(const RefView& im, int q, int kind, bool
         const int x = acgt_of_2bit(pr >> 2), y = acgt_of_2bit(pr & 3u);
         return kind ? 5 * (3 - y) + (3 - x) : 5 * x + y;
     }
-    if (!kind) return 5 * ctx_base(im, q) + ctx_base(im, q + 1);
-    return 5 * ctx_comp(ctx_base(im, q)) + ctx_comp(ctx_base(im, q - 1));
+    if (!kind) return 5 * ref_base(im, q) + ref_base(im, q + 1);
+    return 5 * ctx_comp(ref_base(im, q)) + ctx_comp(ref_base(im, q - 1));
 }
 
 // the class of fragment i among the row's classes [c0, c0 + nc), or -1; its anchors
@@ -195,9 +180,9 @@ __global__ __launch_bounds__(kCtxRefThreads) void ref_context_kernel(RefView im,
         const int lo = (int)(pos_lo + r * kCtxRefRun), hi = min(lo + kCtxRefRun, pos_hi);
         // bases lo .. hi are read (hi <= chrom_len: base(chrom_len) is N)
         const bool clean = im.kind == FTK_REF_2BIT && hi + 1 <= im.chrom_len && !(im.n_nblk && ref_has_n(im, lo, hi + 1));
-        int cur = clean ? acgt_of_2bit(twobit_code(im.img[lo >> 2], lo)) : ctx_base(im, lo);
+        int cur = clean ? acgt_of_2bit(twobit_code(im.img[lo >> 2], lo)) : ref_base(im, lo);
         for (int q = lo; q < hi; ++q) {
-            const int nxt = clean ? acgt_of_2bit(twobit_code(im.img[(q + 1) >> 2], q + 1)) : ctx_base(im, q + 1);
+            const int nxt = clean ? acgt_of_2bit(twobit_code(im.img[(q + 1) >> 2], q + 1)) : ref_base(im, q + 1);
             ++cnt[(5 * cur + nxt) * kCtxRefThreads + tid];
             cur = nxt;
         }

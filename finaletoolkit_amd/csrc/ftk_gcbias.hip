@@ -58,7 +58,7 @@ __global__ __launch_bounds__(kGcFragThreads) void frag_gc_kernel(ContigView cv, 
         const int a = cv.start[i], b = cv.end[i], L = b - a;
         int g = -1;
         if ((int)cv.mapq[i] >= p.mapq_min && L >= p.min_len && L <= p.max_len) {
-            if (a >= 0 && b <= im.chrom_len) g = im.kind == FTK_REF_2BIT ? span_gc_2bit(im, a, b) : span_gc_text(im, a, b);
+            g = span_gc(im, a, b);
             if (table) {
                 if (g < 0) atomicAdd(&skipped_s, 1u);
                 else if (L <= p.lds_hi) atomicAdd(&gc_cells[tri(L) - tri0 + g], 1u);
@@ -69,18 +69,12 @@ __global__ __launch_bounds__(kGcFragThreads) void frag_gc_kernel(ContigView cv, 
     }
     if (!table) return;
     __syncthreads();
-    const int lane = tid & 63, wv = tid >> 6;
-    for (int L = p.len_lo + wv; L <= p.lds_hi; L += kGcFragThreads / 64) {
-        const int base = tri(L) - tri0;
-        for (int g = lane; g <= L; g += 64) {
-            const uint32_t v = gc_cells[base + g];
-            if (v) atomicAdd(&table[(long long)(L - p.len_lo) * pitch + g], (unsigned long long)v);
-        }
-    }
+    flush_packed_rows<kGcFragThreads>(gc_cells, p.len_lo, p.lds_hi, p.len_lo, pitch, table);
     if (tid == 0 && skipped_s) atomicAdd(n_skipped, (unsigned long long)skipped_s);
 }
 
 // is-GC (bit 0) / is-N or outside the contig (bit 16) of position q >= 0
+// (not stated over ref_base: once per base and tile, that made ref_gc_table_kernel 1103 -> 1364 instructions long)
 __device__ __forceinline__ uint32_t base_flags(const RefView& im, int q) {
     if (q >= im.chrom_len) return 0x10000u;
     if (im.kind == FTK_REF_2BIT) {
@@ -139,14 +133,7 @@ __global__ __launch_bounds__(kGcRefThreads) void ref_gc_table_kernel(RefView im,
         }
     }
     __syncthreads();
-    const int pitch = len_hi + 1;
-    for (int l = L0 + wv; l <= L1; l += kGcRefThreads / 64) {
-        const int base = tri(l) - tri0;
-        for (int g = lane; g <= l; g += 64) {
-            const uint32_t v = cells[base + g];
-            if (v) atomicAdd(&table[(long long)(l - len_lo) * pitch + g], (unsigned long long)v);
-        }
-    }
+    flush_packed_rows<kGcRefThreads>(cells, L0, L1, len_lo, len_hi + 1, table);
 }
 
 }  // namespace
@@ -161,10 +148,8 @@ void launch_frag_gc(hipStream_t s, int n_cu, const ContigView& cv, const RefView
         n_cells = (int)(gc_tri(p.lds_hi + 1) - gc_tri(p.len_lo));
     }
     const size_t lds = (size_t)n_cells * 4;
-    const long long blocks = ((long long)cv.n + kGcFragThreads - 1) / kGcFragThreads;
-    const long long resident = (long long)n_cu * (2 * lds <= (size_t)(152 << 10) ? 2 : 1);  // workgroups a CU's LDS and 32 wave slots hold
-    hipLaunchKernelGGL(frag_gc_kernel, dim3((unsigned)std::min(blocks, resident)), dim3(kGcFragThreads), lds, s, cv, im, p, n_cells,
-                       gc_out, table, n_skipped);
+    hipLaunchKernelGGL(frag_gc_kernel, dim3(frag_pass_grid(n_cu, cv.n, kGcFragThreads, lds)), dim3(kGcFragThreads), lds, s, cv, im, p,
+                       n_cells, gc_out, table, n_skipped);
 }
 
 void launch_ref_gc_table(hipStream_t s, int n_cu, const RefView& im, int pos_lo, int pos_hi, int len_lo, int len_hi,

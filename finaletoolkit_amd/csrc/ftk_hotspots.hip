@@ -166,8 +166,8 @@ __global__ __launch_bounds__(256) void ifs_totals_kernel(ContigView cv, IfsParam
         ++cnt;
         sum += (unsigned)len;
     }
-    cnt = wave_sum_u64x(cnt);
-    sum = wave_sum_u64x(sum);
+    cnt = wave_sum_u64(cnt);
+    sum = wave_sum_u64(sum);
     if (lane == 0) red[wv][0] = cnt, red[wv][1] = sum;
     __syncthreads();
     if (tid < 2) partial[2 * blockIdx.x + tid] = red[0][tid] + red[1][tid] + red[2][tid] + red[3][tid];

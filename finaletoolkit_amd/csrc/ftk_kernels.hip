@@ -359,8 +359,7 @@ __device__ __forceinline__ int kmer_code(const MotifParams& M, int lo, bool revc
         // longer than the image), the sixteen 2-bit groups translated at once, the k-mer cut out with a shift and a mask
         typedef uint32_t __attribute__((aligned(1))) u32u;
         const uint32_t be = __builtin_bswap32(*reinterpret_cast<const u32u*>(M.img + (lo >> 2)));  // first base on top
-        const uint32_t v1 = (be >> 1) & 0x55555555u, v0 = be & 0x55555555u;    // T=00 C=01 A=10 G=11
-        const uint32_t acgt = ((~(v1 ^ v0) & 0x55555555u) << 1) | (~v1 & 0x55555555u);  // -> A=00 C=01 G=10 T=11
+        const uint32_t acgt = acgt_of_2bit_word(be);
         const uint32_t mask = (1u << (2 * M.k)) - 1u;
         uint32_t x = (acgt >> (32 - 2 * ((lo & 3) + M.k))) & mask;  // base 0 most significant
         if (revcomp) {  // base j complemented at bits 2j: the 2-bit groups in reverse order, each XOR 3
@@ -373,13 +372,8 @@ __device__ __forceinline__ int kmer_code(const MotifParams& M, int lo, bool revc
     int code = 0, col;
     long long off = ref_text_offset(M, lo, col);
     for (int j = 0; j < M.k; ++j) {
-        const int ch = M.img[off] & 0xDF;
-        int base;
-        if (ch == 'A') base = 0;
-        else if (ch == 'C') base = 1;
-        else if (ch == 'G') base = 2;
-        else if (ch == 'T') base = 3;
-        else return -1;
+        const int base = text_base(M.img[off]);
+        if (base == 4) return -1;
         code = revcomp ? (code | ((3 - base) << (2 * j))) : (code * 4 + base);
         ref_text_next(M, off, col);
     }
@@ -446,8 +440,7 @@ __device__ __forceinline__ int kmer_from_word(uint32_t w, int p, int k, bool rev
 }
 // bin b of a T C A G ordered histogram -> its place in A C G T order (digit by digit: T=00 C=01 A=10 G=11 -> 11 01 00 10)
 __device__ __forceinline__ int motif_bin(int b, int n_bins) {
-    const uint32_t v1 = ((uint32_t)b >> 1) & 0x55555555u, v0 = (uint32_t)b & 0x55555555u;
-    return (int)((((~(v1 ^ v0) & 0x55555555u) << 1) | (~v1 & 0x55555555u)) & (uint32_t)(n_bins - 1));
+    return (int)(acgt_of_2bit_word((uint32_t)b) & (uint32_t)(n_bins - 1));
 }
 
 // What one window-feature launch computes (any combination, ONE pass over the fragments):
@@ -1978,12 +1971,6 @@ __global__ void add_i64_kernel(const int64_t* a, const int64_t* b, int64_t* out,
 //   stdev  = sqrt(sum(c (v - mean)^2) / n), population; summed lane-wise and then across the wave (the reference sums
 //            in dict insertion order: equal to ~1e-16 relative, the tests allow 1e-9)
 // ---------------------------------------------------------------------------
-__device__ __forceinline__ long long wave_sum_ll(long long v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
-    return v;
-}
-
 __global__ __launch_bounds__(256) void window_stats_kernel(const uint32_t* __restrict__ hist, int n_win, int n_bins,
                                                            int len_lo, int short_cut, double* __restrict__ out) {
     const int w = blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -2003,9 +1990,9 @@ __global__ __launch_bounds__(256) void window_stats_kernel(const uint32_t* __res
             last = b;
         }
     }
-    tot = wave_sum_ll(tot);
-    sum = wave_sum_ll(sum);
-    n_short = wave_sum_ll(n_short);
+    tot = wave_sum_u64(tot);
+    sum = wave_sum_u64(sum);
+    n_short = wave_sum_u64(n_short);
 #pragma unroll
     for (int d = 32; d >= 1; d >>= 1) {
         first = min(first, __shfl_xor(first, d, 64));

@@ -109,7 +109,7 @@ __global__ __launch_bounds__(kSiteThreads) void site_ends_kernel(ContigView cv, 
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 const unsigned long long n = wave_sum_u32(wc[j]);
-                const unsigned long long w = WEIGHTED ? wave_sum_u64x(ws[j]) : n * FTK_WEIGHT_ONE;
+                const unsigned long long w = WEIGHTED ? wave_sum_u64(ws[j]) : n * FTK_WEIGHT_ONE;
                 if (lane == 0 && ((j & 1) ? do_d : do_u)) {
                     site_sum[row + j] = w;
                     if (site_cnt) site_cnt[row + j] = n;

@@ -43,8 +43,7 @@ __global__ __launch_bounds__(kGcWeightThreads) void frag_gc_weight_kernel(Contig
         const int a = cv.start[i], b = cv.end[i], L = b - a;
         uint32_t w = 0;
         if ((int)cv.mapq[i] >= p.mapq_min && L >= p.len_lo && L <= p.len_hi) {
-            int g = -1;
-            if (a >= 0 && b <= im.chrom_len) g = im.kind == FTK_REF_2BIT ? span_gc_2bit(im, a, b) : span_gc_text(im, a, b);
+            const int g = span_gc(im, a, b);
             if (g >= 0) {  // (g <= L: the cell lies inside row L)
                 const int cell = tri(L) - tri0 + g;
                 w = p.in_lds ? w_cells[cell] : packed[cell];
@@ -58,7 +57,8 @@ __global__ __launch_bounds__(kGcWeightThreads) void frag_gc_weight_kernel(Contig
     if (tid == 0 && zero_s) atomicAdd(n_zero, (unsigned long long)zero_s);
 }
 
-__device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v) {
+// (not ftk_device.h's wave_sum_u64: on __shfl_xor the kernel below came out 12 instructions longer and slower at times)
+__device__ __forceinline__ unsigned long long wave_sum_down_u64(unsigned long long v) {
 #pragma unroll
     for (int d = 32; d; d >>= 1) v += __shfl_down(v, d, 64);
     return v;  // lane 0 holds the sum
@@ -101,8 +101,8 @@ __global__ __launch_bounds__(kWwThreads) void weighted_window_kernel(ContigView 
             cnt += (unsigned long long)(ok & (wt != 0));
         }
     }
-    sum = wave_sum_u64(sum);
-    cnt = wave_sum_u64(cnt);
+    sum = wave_sum_down_u64(sum);
+    cnt = wave_sum_down_u64(cnt);
     if (lane == 0) { red[0][wv] = sum; red[1][wv] = cnt; }
     __syncthreads();
     if (tid < 2) {
@@ -122,10 +122,8 @@ void launch_frag_gc_weights(hipStream_t s, int n_cu, const ContigView& cv, const
     p.n_cells = (int)gc_weight_cells(p.len_lo, p.len_hi);
     p.in_lds = p.n_cells <= kGcWeightLdsCells;
     const size_t lds = p.in_lds ? (size_t)p.n_cells * 4 : 0;
-    const long long blocks = ((long long)cv.n + kGcWeightThreads - 1) / kGcWeightThreads;
-    const long long resident = (long long)n_cu * (2 * lds <= (size_t)(152 << 10) ? 2 : 1);  // workgroups a CU's LDS and 32 wave slots hold
-    hipLaunchKernelGGL(frag_gc_weight_kernel, dim3((unsigned)std::min(blocks, resident)), dim3(kGcWeightThreads), lds, s, cv, im, p,
-                       packed, w_out, n_zero);
+    hipLaunchKernelGGL(frag_gc_weight_kernel, dim3(frag_pass_grid(n_cu, cv.n, kGcWeightThreads, lds)), dim3(kGcWeightThreads), lds, s,
+                       cv, im, p, packed, w_out, n_zero);
 }
 
 int weighted_window_slices(int n_cu, long long n_win, long long n_frag) {

@@ -133,11 +133,12 @@ def _coverage_one_process(clock, input_file, interval_file, min_length, max_leng
     clock.lap("read_intervals")
     if feed is None:
         feed = ContigFeed(input_file, workers, names=list(by_contig))
+    feed.required = by_contig  # contigs the file does not hold: the error the reference's fetch raises (ValueError)
     starts = np.array([iv[1] for iv in intervals], dtype=np.int64)
     stops = np.array([iv[2] for iv in intervals], dtype=np.int64)
     counts = np.zeros(len(intervals), np.int64)
     total, left = 0, dict(by_contig)
-    try:
+    with feed:
         for src, c in feed:
             clock.lap("decode_wait")
             key = src.key(c)
@@ -151,12 +152,6 @@ def _coverage_one_process(clock, input_file, interval_file, min_length, max_leng
                 counts[order] = eng.window_counts(key, starts[order].astype(np.int32), stops[order].astype(np.int32),
                                                   quality_threshold, min_length, max_length, intersect_policy)
             clock.lap("count_kernels")
-        src = feed.finish()
-    except BaseException:
-        feed.close()
-        raise
-    for c in left:  # contigs the file does not hold: the error the reference's fetch raises (ValueError)
-        src.require(c)
     return counts, total, intervals
 
 

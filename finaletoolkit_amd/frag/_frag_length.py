@@ -374,19 +374,16 @@ def frag_length_intervals(input_file, interval_file: str, output_file: str | Non
         sys.setswitchinterval(min(switch, 2e-4))
         rows_thread.start()
         try:
-            for src, c in feed:
-                clock.lap("decode_wait")
-                idx = by_contig.pop(c, None)
-                if idx is not None:
-                    idx = np.asarray(idx, dtype=np.int64)
-                    order = idx[np.argsort(iv_starts[idx], kind="stable")]
-                    block = unit_stats(src.key(c), order)
-                    clock.lap("histograms_and_statistics")
-                    todo.put((order, block))
-            src = feed.finish()
-        except BaseException:
-            feed.close()
-            raise
+            with feed:
+                for src, c in feed:
+                    clock.lap("decode_wait")
+                    idx = by_contig.pop(c, None)
+                    if idx is not None:
+                        idx = np.asarray(idx, dtype=np.int64)
+                        order = idx[np.argsort(iv_starts[idx], kind="stable")]
+                        block = unit_stats(src.key(c), order)
+                        clock.lap("histograms_and_statistics")
+                        todo.put((order, block))
         finally:
             todo.put(None)
             rows_thread.join()
@@ -394,8 +391,9 @@ def frag_length_intervals(input_file, interval_file: str, output_file: str | Non
         if failed:
             raise failed[0]
         clock.lap("result_rows_tail")
+        # (not the feed's ``require``: a failure of the row thread comes first, and the rows below need the walk anyway)
         for c, idx in by_contig.items():  # contigs the file does not hold: the error the reference's fetch raises (ValueError)
-            src.require(c)
+            feed.src.require(c)
             # a header contig without a usable read (never fed): every interval's row is all -1 (:202-238)
             _result_rows(results, intervals, np.asarray(idx, dtype=np.int64), np.zeros((len(idx), 7)), lines)
     else:

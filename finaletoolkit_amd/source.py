@@ -646,9 +646,14 @@ class ContigFeed:
     as each contig becomes resident - while the decoder is already in the next one - instead of after ``open_source``
     has decoded the whole file.  Iterate for ``(src, contig)`` in the order the contigs become resident; ``finish()``
     drains what is left and returns the source.  ``names``: the contigs the caller can want (``None``: all) - a lazily
-    indexed file is then read through its index for those alone."""
+    indexed file is then read through its index for those alone.
 
-    def __init__(self, input_file, workers=None, names=None, warn_bed6: bool = True):
+    As a context manager: ``with ContigFeed(...) as feed: for src, c in feed: ...``.  An exception in the body closes the
+    feed and goes on; a clean exit calls ``finish()`` - ``feed.src`` is the source from then on - and then
+    ``src.require(name)`` for every name of ``require`` (any iterable, kept as ``feed.required`` and read at the exit: a
+    dict the body empties as it goes will do, and it may be set before the exit) that is not in ``seen``: the ``ValueError`` of a contig the file does not hold."""
+
+    def __init__(self, input_file, workers=None, names=None, warn_bed6: bool = True, require=()):
         # (the decoder may run a whole genome's contigs ahead of a consumer that is busy with one contig's rows: the
         #  finished tables wait in HBM, 10 B per fragment)
         self._early = EarlyContigs(input_file, workers, True, warn_bed6, names=names, queued=32)
@@ -656,6 +661,24 @@ class ContigFeed:
         self.src: Optional[FragSource] = None
         self.seen: list = []
         self._input, self._workers, self._warn = input_file, workers, warn_bed6
+        self.required = require
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, exc_type, exc, tb):
+        if exc_type is not None:
+            self.close()
+            return False
+        try:
+            self.finish()
+        except BaseException:
+            self.close()
+            raise
+        for name in list(self.required):
+            if name not in self.seen:
+                self.src.require(name)
+        return False
 
     def __iter__(self):
         if self._it is None:

@@ -224,6 +224,12 @@ def _check_export_args(input_file, output_file, layout) -> str:
     return output_file
 
 
+def _one_or_all(contig) -> dict:
+    """The ``ContigFeed`` arguments of a command that takes ``contig=None`` (every contig of the file) or one name, which
+    the file must then hold: the ``ValueError`` of every other command otherwise."""
+    return {} if contig is None else dict(names=[str(contig)], require=[str(contig)])
+
+
 def _export(label, input_file, output_file, contig, quality_threshold, min_length, max_length, layout, workers, verbose,
             whitelist=None, blacklist=None, intersect_policy="midpoint") -> dict:
     """The body of ``frag_export`` and ``frag_filter`` (arguments checked by the caller): every contig of the feed goes
@@ -236,10 +242,9 @@ def _export(label, input_file, output_file, contig, quality_threshold, min_lengt
     from .source import ContigFeed
     t0 = time.time()
     eng = get_engine()
-    feed = ContigFeed(input_file, workers, names=None if contig is None else [str(contig)])
     none = (np.zeros(0, np.int32), np.zeros(0, np.int32))
     written, index, first = {}, [], True
-    try:
+    with ContigFeed(input_file, workers, **_one_or_all(contig)) as feed:
         for src, c in feed:
             mask = None
             if whitelist is not None or blacklist is not None:
@@ -254,12 +259,6 @@ def _export(label, input_file, output_file, contig, quality_threshold, min_lengt
             if verbose:
                 sys.stderr.write(f"{label}: {c}: {res['rows']} rows, {res['text_bytes']} bytes of text -> "
                                  f"{res['end_off'] - res['first_off']} bytes\n")
-        src = feed.finish()
-    except BaseException:
-        feed.close()
-        raise
-    if contig is not None and str(contig) not in written:
-        src.require(str(contig))  # not in the file: the ValueError of every other command
     with open(output_file, "ab" if not first else "wb") as fh:
         fh.write(bgzf._EOF)
     bgzf.write_tabix(output_file + ".tbi", index)
@@ -353,7 +352,6 @@ def frag_depth_track(input_file, output_file, contig=None, quality_threshold: in
     level = writers.GZIP_LEVEL if zipped else 0
     t0 = time.time()
     eng = get_engine()
-    feed = ContigFeed(input_file, workers, names=None if contig is None else [str(contig)])
     out = dict(n_runs=0, n_fragments=0, bases_covered=0, max_depth=0)
     state = dict(first=True, next=0)
     pending = {}  # include_zero: rows of contigs that became resident ahead of an earlier contig of the file
@@ -374,7 +372,7 @@ def frag_depth_track(input_file, output_file, contig=None, quality_threshold: in
                 emit(text)
             state["next"] += 1
 
-    try:
+    with ContigFeed(input_file, workers, **_one_or_all(contig)) as feed:
         for src, c in feed:
             key = src.key(c)
             length = src.lengths.get(c)
@@ -395,13 +393,7 @@ def frag_depth_track(input_file, output_file, contig=None, quality_threshold: in
             out["max_depth"] = max(out["max_depth"], int(rd.max()) if len(rd) else 0)
             if verbose:
                 sys.stderr.write(f"frag_depth_track: {c}: {kept} fragments, {len(rs)} runs\n")
-        src = feed.finish()
-        flush(src, True)
-    except BaseException:
-        feed.close()
-        raise
-    if contig is not None and str(contig) not in feed.seen:
-        src.require(str(contig))  # not in the file: the ValueError of every other command
+        flush(feed.finish(), True)
     if state["first"]:
         writers.write_text(output_file, b"", level)
     if verbose:
@@ -455,6 +447,31 @@ def _check_gc_bias_args(output_file, min_length, max_length, stride, expected):
     return shape, expected
 
 
+def _over_reference_contigs(label, input_file, reference_file, contig, workers, verbose, one_contig) -> tuple:
+    """The walk ``frag_gc_bias`` and ``frag_end_context`` share: every contig of the input (``contig``: that one alone,
+    which the file must hold) that ``reference_file`` holds too, handed to ``one_contig(engine, key, image id, name,
+    size) -> note`` as it becomes resident, its reference image resident with its layout; ``note`` ends the contig's
+    verbose line.  Contigs the reference lacks are skipped with one ``UserWarning`` and returned."""
+    import sys
+    import warnings
+
+    from .reference import ReferenceGenome
+    from .source import ContigFeed
+    eng = get_engine()
+    missing = []
+    with ContigFeed(input_file, workers, **_one_or_all(contig)) as feed, ReferenceGenome(reference_file) as ref:
+        for src, c in feed:
+            if c not in ref.chroms:
+                missing.append(c)
+                continue
+            note = one_contig(eng, src.key(c), ref.device_image(eng, c, with_layout=True), c, ref.chroms[c])
+            if verbose:
+                sys.stderr.write(f"{label}: {c}: {note}\n")
+    if missing:
+        warnings.warn(f"{label}: contigs not in the reference were skipped: " + ", ".join(missing), UserWarning)
+    return tuple(missing)
+
+
 def frag_gc_bias(input_file, reference_file, output_file=None, contig=None, min_length: int = 100, max_length: int = 220,
                  quality_threshold: int = 30, stride: int = 1, expected=None, workers=None, verbose=False) -> GCBias:
     """Fragment length x GC bias of ``input_file`` against ``reference_file`` (``.2bit`` or FASTA), the measurement of
@@ -480,44 +497,25 @@ def frag_gc_bias(input_file, reference_file, output_file=None, contig=None, min_
     import os
     import sys
     import time
-    import warnings
 
     from . import writers
-    from .reference import ReferenceGenome
-    from .source import ContigFeed
     shape, given = _check_gc_bias_args(output_file, min_length, max_length, stride, expected)
     lo, hi, stride = int(min_length), int(max_length), int(stride)
     t0 = time.time()
-    eng = get_engine()
-    feed = ContigFeed(input_file, workers, names=None if contig is None else [str(contig)])
     observed = np.zeros(shape, np.int64)
-    exp_sum = np.zeros(shape, np.int64)
-    n_skipped, missing = 0, []
-    try:
-        with ReferenceGenome(reference_file) as ref:
-            for src, c in feed:
-                if c not in ref.chroms:
-                    missing.append(c)
-                    continue
-                rid = ref.device_image(eng, c, with_layout=True)
-                table, skipped = eng.frag_gc_table(src.key(c), rid, lo, hi, quality_threshold)
-                observed += table
-                n_skipped += skipped
-                if given is None:
-                    exp_sum += eng.ref_gc_table(rid, 0, ref.chroms[c], lo, hi, stride)
-                if verbose:
-                    sys.stderr.write(f"frag_gc_bias: {c}: {int(table.sum())} fragments, {skipped} skipped\n")
-            src = feed.finish()
-    except BaseException:
-        feed.close()
-        raise
-    if contig is not None and str(contig) not in feed.seen:
-        src.require(str(contig))  # not in the file: the ValueError of every other command
-    if missing:
-        warnings.warn("frag_gc_bias: contigs not in the reference were skipped: " + ", ".join(missing), UserWarning)
-    if given is not None:
-        exp_sum = given
-    res = GCBias(lo, hi, observed, exp_sum, gc_bias_ratio(observed, exp_sum), int(observed.sum()), int(n_skipped), tuple(missing))
+    exp_sum = np.zeros(shape, np.int64) if given is None else given
+    n_skipped = 0
+
+    def one_contig(eng, key, rid, name, size):
+        nonlocal n_skipped
+        table, skipped = eng.frag_gc_table(key, rid, lo, hi, quality_threshold)
+        observed[...] += table
+        n_skipped += skipped
+        if given is None:
+            exp_sum[...] += eng.ref_gc_table(rid, 0, size, lo, hi, stride)
+        return f"{int(table.sum())} fragments, {skipped} skipped"
+    missing = _over_reference_contigs("frag_gc_bias", input_file, reference_file, contig, workers, verbose, one_contig)
+    res = GCBias(lo, hi, observed, exp_sum, gc_bias_ratio(observed, exp_sum), int(observed.sum()), int(n_skipped), missing)
     if output_file is not None:
         writers.write_gc_bias_table(os.fspath(output_file), lo, res.observed, res.expected, res.bias)
     if verbose:
@@ -525,13 +523,17 @@ def frag_gc_bias(input_file, reference_file, output_file=None, contig=None, min_
     return res
 
 
+def _check_min_bias(min_bias):
+    if not float(min_bias) >= 2.0 ** -15:
+        raise ValueError(f"invalid min_bias ({min_bias}): at least 2**-15")
+
+
 def gc_weights(bias, min_bias: float = 0.05) -> np.ndarray:
     """The weight table of a bias table (a ``GCBias`` or a float array): uint32 in units of 2^-16, ``floor(65536 / bias +
     0.5)`` per cell, 0 where the bias is NaN or below ``min_bias`` (a cell with hardly any observed fragments would
     otherwise give each of them a huge weight).  ``min_bias`` is at least 2^-15, which keeps every weight within 2^31
     units."""
-    if not float(min_bias) >= 2.0 ** -15:
-        raise ValueError(f"invalid min_bias ({min_bias}): at least 2**-15")
+    _check_min_bias(min_bias)
     b = np.asarray(bias.bias if isinstance(bias, GCBias) else bias, dtype=np.float64)
     out = np.zeros(b.shape, np.uint32)
     ok = ~np.isnan(b) & (b >= float(min_bias))
@@ -567,6 +569,20 @@ def read_gc_bias_table(path, min_length: int, max_length: int) -> GCBias:
     return GCBias(lo, hi, observed, expected, bias, int(observed.sum()), 0, ())
 
 
+def _weight_table(input_file, reference_file, bias, lo, hi, quality_threshold, stride, min_bias, workers, verbose) -> np.ndarray:
+    """``gc_weights`` of what a command was given as ``bias`` for the lengths ``[lo, hi]``: a ``GCBias``, the path of its TSV
+    (``read_gc_bias_table``), or ``None`` - then ``frag_gc_bias`` of the input runs first with the same lengths, MAPQ cut
+    and ``stride``, its warning about contigs the reference lacks left to the command, which reports them itself."""
+    import warnings
+    if bias is None:
+        with warnings.catch_warnings():
+            warnings.filterwarnings("ignore", message="frag_gc_bias: contigs not in the reference", category=UserWarning)
+            bias = frag_gc_bias(input_file, reference_file, None, None, lo, hi, quality_threshold, stride, None, workers, verbose)
+    elif not isinstance(bias, GCBias):
+        bias = read_gc_bias_table(bias, lo, hi)
+    return gc_weights(bias, min_bias)
+
+
 class GCCoverage(NamedTuple):
     """Result of ``frag_gc_coverage``, one entry per interval of the interval file, in its order."""
     intervals: list           # (contig, start, stop, name)
@@ -583,8 +599,7 @@ _GC_COVERAGE_SUFFIXES = (".bed", ".bed.gz")
 def _check_gc_coverage_args(output_file, bias, min_length, max_length, intersect_policy, min_bias, stride):
     _check_gc_bias_args(None, min_length, max_length, stride, None)
     _check_policy(intersect_policy)
-    if not float(min_bias) >= 2.0 ** -15:
-        raise ValueError(f"invalid min_bias ({min_bias}): at least 2**-15")
+    _check_min_bias(min_bias)
     if output_file is not None and not str(output_file).endswith(_GC_COVERAGE_SUFFIXES):
         raise ValueError("output_file should have .bed or .bed.gz as suffix")
     if isinstance(bias, GCBias) and (bias.min_length, bias.max_length) != (int(min_length), int(max_length)):
@@ -633,13 +648,7 @@ def frag_gc_coverage(input_file, reference_file, interval_file, output_file=None
     _check_gc_coverage_args(output_file, bias, min_length, max_length, intersect_policy, min_bias, stride)
     lo, hi = int(min_length), int(max_length)
     t0 = time.time()
-    if bias is None:
-        with warnings.catch_warnings():  # (contigs the reference lacks are reported once, below)
-            warnings.filterwarnings("ignore", message="frag_gc_bias: contigs not in the reference", category=UserWarning)
-            bias = frag_gc_bias(input_file, reference_file, None, None, lo, hi, quality_threshold, stride, None, workers, verbose)
-    elif not isinstance(bias, GCBias):
-        bias = read_gc_bias_table(bias, lo, hi)
-    table = gc_weights(bias, min_bias)
+    table = _weight_table(input_file, reference_file, bias, lo, hi, quality_threshold, stride, min_bias, workers, verbose)
     intervals = get_intervals(interval_file)
     by_contig: dict[str, list[int]] = {}
     for i, iv in enumerate(intervals):
@@ -652,35 +661,28 @@ def frag_gc_coverage(input_file, reference_file, interval_file, output_file=None
     no_reference = np.zeros(len(intervals), bool)
     n_zero, missing, left = 0, [], dict(by_contig)
     eng = get_engine()
-    feed = ContigFeed(input_file, workers, names=list(by_contig))
-    try:
-        with ReferenceGenome(reference_file) as ref:
-            for src, c in feed:
-                idx = left.pop(c, None)
-                if idx is None:
-                    continue
-                key = src.key(c)
-                idx = np.asarray(idx, dtype=np.int64)
-                order = idx[np.argsort(starts[idx], kind="stable")]
-                ws, we = starts[order].astype(np.int32), stops[order].astype(np.int32)
-                args = (quality_threshold, lo, hi, intersect_policy)
-                count[order] = eng.window_counts(key, ws, we, *args)
-                if c not in ref.chroms:
-                    missing.append(c)
-                    no_reference[order] = True
-                    continue
-                rid = ref.device_image(eng, c, with_layout=True)
-                zeros = eng.set_gc_weights(key, rid, lo, hi, table, quality_threshold)
-                units[order], n_weighted[order] = eng.weighted_window_sums(key, ws, we, *args)
-                n_zero += zeros
-                if verbose:
-                    sys.stderr.write(f"frag_gc_coverage: {c}: {len(order)} intervals, {zeros} fragments of weight 0\n")
-            src = feed.finish()
-    except BaseException:
-        feed.close()
-        raise
-    for c in left:  # contigs the file does not hold: the ValueError of frag.coverage
-        src.require(c)
+    # (require: contigs the file does not hold get the ValueError of frag.coverage)
+    with ContigFeed(input_file, workers, names=list(by_contig), require=left) as feed, ReferenceGenome(reference_file) as ref:
+        for src, c in feed:
+            idx = left.pop(c, None)
+            if idx is None:
+                continue
+            key = src.key(c)
+            idx = np.asarray(idx, dtype=np.int64)
+            order = idx[np.argsort(starts[idx], kind="stable")]
+            ws, we = starts[order].astype(np.int32), stops[order].astype(np.int32)
+            args = (quality_threshold, lo, hi, intersect_policy)
+            count[order] = eng.window_counts(key, ws, we, *args)
+            if c not in ref.chroms:
+                missing.append(c)
+                no_reference[order] = True
+                continue
+            rid = ref.device_image(eng, c, with_layout=True)
+            zeros = eng.set_gc_weights(key, rid, lo, hi, table, quality_threshold)
+            units[order], n_weighted[order] = eng.weighted_window_sums(key, ws, we, *args)
+            n_zero += zeros
+            if verbose:
+                sys.stderr.write(f"frag_gc_coverage: {c}: {len(order)} intervals, {zeros} fragments of weight 0\n")
     if missing:
         warnings.warn("frag_gc_coverage: contigs not in the reference were not corrected: " + ", ".join(missing), UserWarning)
     corrected = units / float(L.WEIGHT_ONE)
@@ -822,14 +824,8 @@ def _sites_over_contigs(what, one_contig, cell_shape, input_file, site_file, ref
             raise ValueError(f"{n_groups} groups of {' x '.join(str(n) for n in cell_shape)} cells: at most {max_cells} cells in all")
     table = None
     if reference_file is not None:
-        lo, hi = int(min_length), int(max_length)
-        if bias is None:
-            with warnings.catch_warnings():  # (contigs the reference lacks are reported once, below)
-                warnings.filterwarnings("ignore", message="frag_gc_bias: contigs not in the reference", category=UserWarning)
-                bias = frag_gc_bias(input_file, reference_file, None, None, lo, hi, quality_threshold, stride, None, workers, verbose)
-        elif not isinstance(bias, GCBias):
-            bias = read_gc_bias_table(bias, lo, hi)
-        table = gc_weights(bias, min_bias)
+        table = _weight_table(input_file, reference_file, bias, int(min_length), int(max_length), quality_threshold, stride,
+                              min_bias, workers, verbose)
     names: dict[str, int] = {}
     if by_name:
         for s in sites:
@@ -849,33 +845,28 @@ def _sites_over_contigs(what, one_contig, cell_shape, input_file, site_file, ref
 
         from .reference import ReferenceGenome
         eng = get_engine()
-        feed = ContigFeed(input_file, workers, names=list(by_contig))
-        try:
-            with (ReferenceGenome(reference_file) if table is not None else nullcontext()) as ref:
-                for src, c in feed:
-                    idx = left.pop(c, None)
-                    if idx is None:
-                        continue
-                    if ref is not None and c not in ref.chroms:
-                        no_reference.append(c)
-                        continue
-                    key = src.key(c)
-                    idx = np.asarray(idx, dtype=np.int64)
-                    if ref is not None:
-                        rid = ref.device_image(eng, c, with_layout=True)
-                        eng.set_gc_weights(key, rid, int(min_length), int(max_length), table, quality_threshold)
-                    sums, counts, *rest = one_contig(eng, key, centre[idx], flip[idx], group[idx], len(groups), ref is not None)
-                    if per_site is not None:
-                        per_site(idx, *rest)
-                    units += sums
-                    count += counts
-                    n_sites += np.bincount(group[idx], minlength=len(groups))
-                    if verbose:
-                        sys.stderr.write(f"{what}: {c}: {len(idx)} sites, {int(counts.sum())} {'midpoints' if per_site is None else 'ends'}\n")
-                feed.finish()
-        except BaseException:
-            feed.close()
-            raise
+        with ContigFeed(input_file, workers, names=list(by_contig)) as feed, \
+                (ReferenceGenome(reference_file) if table is not None else nullcontext()) as ref:
+            for src, c in feed:
+                idx = left.pop(c, None)
+                if idx is None:
+                    continue
+                if ref is not None and c not in ref.chroms:
+                    no_reference.append(c)
+                    continue
+                key = src.key(c)
+                idx = np.asarray(idx, dtype=np.int64)
+                if ref is not None:
+                    rid = ref.device_image(eng, c, with_layout=True)
+                    eng.set_gc_weights(key, rid, int(min_length), int(max_length), table, quality_threshold)
+                sums, counts, *rest = one_contig(eng, key, centre[idx], flip[idx], group[idx], len(groups), ref is not None)
+                if per_site is not None:
+                    per_site(idx, *rest)
+                units += sums
+                count += counts
+                n_sites += np.bincount(group[idx], minlength=len(groups))
+                if verbose:
+                    sys.stderr.write(f"{what}: {c}: {len(idx)} sites, {int(counts.sum())} {'midpoints' if per_site is None else 'ends'}\n")
     if left:
         warnings.warn(f"{what}: contigs not in the input were skipped: " + ", ".join(left), UserWarning)
     if no_reference:
@@ -1152,8 +1143,8 @@ def _over_regions(label, input_file, interval_file, chrom_sizes, workers, verbos
     parts, rows = [[] for _ in dtypes], {}
     left = dict(by_contig)
     eng = get_engine()
-    feed = ContigFeed(input_file, workers, names=None if whole else list(by_contig))
-    try:
+    # (require: contigs the file does not hold get the ValueError of frag.coverage)
+    with ContigFeed(input_file, workers, names=None if whole else list(by_contig), require=left) as feed:
         for src, c in feed:
             if whole:
                 if sizes is not None and c not in sizes:
@@ -1174,12 +1165,6 @@ def _over_regions(label, input_file, interval_file, chrom_sizes, workers, verbos
             rows.update(zip(idx, c_rows))
             if verbose:
                 sys.stderr.write(f"{label}: {c}: {len(idx)} intervals, {note}\n")
-        src = feed.finish()
-    except BaseException:
-        feed.close()
-        raise
-    for c in left:  # contigs the file does not hold: the ValueError of frag.coverage
-        src.require(c)
     records = []
     for part, dt in zip(parts, dtypes):  # (an interval's records are in order already)
         rec = np.concatenate(part) if part else np.zeros(0, dt)
@@ -1763,42 +1748,23 @@ def frag_end_context(input_file, reference_file, output_file=None, contig=None, 
     import os
     import sys
     import time
-    import warnings
 
     from . import writers
-    from .reference import ReferenceGenome
-    from .source import ContigFeed
     edges = _check_end_context_args(output_file, half_width, length_edges, anchor)
     w = int(half_width)
     t0 = time.time()
-    eng = get_engine()
-    feed = ContigFeed(input_file, workers, names=None if contig is None else [str(contig)])
     table = np.zeros((len(edges) - 1, 2, 2 * w, 25), np.int64)
     n_kept = np.zeros(len(edges) - 1, np.int64)
     background = np.zeros(25, np.int64)
-    missing = []
-    try:
-        with ReferenceGenome(reference_file) as ref:
-            for src, c in feed:
-                if c not in ref.chroms:
-                    missing.append(c)
-                    continue
-                rid = ref.device_image(eng, c, with_layout=True)
-                t, k = eng.end_context(src.key(c), rid, w, edges, quality_threshold, anchor)
-                table += t
-                n_kept += k
-                background += eng.ref_context(rid, 0, ref.chroms[c])
-                if verbose:
-                    sys.stderr.write(f"frag_end_context: {c}: {int(k.sum())} fragments\n")
-            src = feed.finish()
-    except BaseException:
-        feed.close()
-        raise
-    if contig is not None and str(contig) not in feed.seen:
-        src.require(str(contig))  # not in the file: the ValueError of every other command
-    if missing:
-        warnings.warn("frag_end_context: contigs not in the reference were skipped: " + ", ".join(missing), UserWarning)
-    res = EndContext(table, n_kept, background, w, edges, str(anchor), tuple(missing))
+
+    def one_contig(eng, key, rid, name, size):
+        t, k = eng.end_context(key, rid, w, edges, quality_threshold, anchor)
+        table[...] += t
+        n_kept[...] += k
+        background[...] += eng.ref_context(rid, 0, size)
+        return f"{int(k.sum())} fragments"
+    missing = _over_reference_contigs("frag_end_context", input_file, reference_file, contig, workers, verbose, one_contig)
+    res = EndContext(table, n_kept, background, w, edges, str(anchor), missing)
     if output_file is not None:
         writers.write_end_context_rows(os.fspath(output_file), res)
     if verbose:

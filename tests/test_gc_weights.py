@@ -72,6 +72,25 @@ def test_read_gc_bias_table_round_trip(tmp_path, suffix):
     assert wider.observed.shape == (6, 10) and np.array_equal(wider.observed[1:4, :8], res.observed)
 
 
+@pytest.mark.parametrize("min_bias", [0.05, 0.2, 2.0 ** -15])
+def test_weight_table_of_a_bias_and_of_its_file(tmp_path, min_bias):
+    """``utils._weight_table``: a ``GCBias`` comes back as ``gc_weights`` of it, the path of its TSV gives the same array,
+    and ``min_bias`` is checked with ``gc_weights``' words.  (``bias=None`` runs ``frag_gc_bias``: the GPU tests.)"""
+    from finaletoolkit_amd import utils, writers
+    res = table_with_odd_cells()
+    want = utils.gc_weights(res, min_bias)
+    args = (5, 7, 30, 1, min_bias, None, False)
+    got = utils._weight_table("no input is read", "nor a reference", res, *args)
+    assert got.dtype == np.uint32 and np.array_equal(got, want) and want.any()
+    out = str(tmp_path / "bias.tsv")
+    writers.write_gc_bias_table(out, res.min_length, res.observed, res.expected, res.bias)
+    assert np.array_equal(utils._weight_table("no input is read", "nor a reference", out, *args), want)
+    for bias in (res, out):
+        with pytest.raises(ValueError) as e:
+            utils._weight_table("no input is read", "nor a reference", bias, 5, 7, 30, 1, 2.0 ** -16, None, False)
+        assert str(e.value) == "invalid min_bias (1.52587890625e-05): at least 2**-15"
+
+
 def test_signature():
     from finaletoolkit_amd import utils
     sig = inspect.signature(utils.frag_gc_coverage)

@@ -255,6 +255,47 @@ def test_sources_opened_from_text_files_use_the_device_rows(tmp_path):
     source.close_all()
 
 
+def test_contig_feed_as_a_context_manager(tmp_path):
+    """``with ContigFeed(...) as feed``: the contigs in file order and ``feed.src`` set after a clean exit; a name of
+    ``require`` the file lacks raises ``src.require``'s ``ValueError`` at the exit; an exception of the body comes out as
+    itself, whatever ``require`` says; the feed's decoder thread has ended every time."""
+    import threading
+
+    from finaletoolkit_amd import source
+    rng = np.random.default_rng(23)
+    contigs = []
+    for k, name in enumerate(("cB", "cA", "cC")):  # (file order, not name order)
+        s = np.sort(rng.integers(0, 500_000, 200 + 17 * k)).astype(np.int32)
+        contigs.append((name, s, (s + rng.integers(40, 400, len(s))).astype(np.int32), rng.integers(0, 61, len(s)).astype(np.uint8),
+                        rng.integers(0, 2, len(s)).astype(np.uint8)))
+    p = str(tmp_path / "three.frag.gz")
+    bgzf.write_frag_gz(p, contigs, level=1)
+
+    def decoding():
+        return [t for t in threading.enumerate() if t.name == "ftk-early-decode"]
+
+    source.close_all()
+    eng = source.get_engine()
+    order = []
+    with source.ContigFeed(p) as feed:
+        for src, c in feed:
+            order.append((c, eng.info(src.key(c))[0]))
+    assert order == [(c[0], len(c[1])) for c in contigs] and feed.seen == ["cB", "cA", "cC"]
+    assert feed.src is src and not decoding()
+    with pytest.raises(ValueError) as want:
+        feed.src.require("cZ")
+    with pytest.raises(ValueError) as got:
+        with source.ContigFeed(p, require=["cA", "cZ"]) as feed:
+            seen = [c for _, c in feed]
+    assert str(got.value) == str(want.value) and seen == ["cB", "cA", "cC"] and not decoding()
+    with pytest.raises(RuntimeError, match="from the body"):
+        with source.ContigFeed(p, require=["cZ"]) as feed:
+            for _ in feed:
+                raise RuntimeError("from the body")
+    assert not decoding()
+    source.close_all()
+
+
 def test_device_stream_errors_and_early_close(tmp_path):
     """Closing a device-mode stream before it is drained, a truncated file and an unsorted file: clean errors,
     no hang, and the next stream works (the buffer sets and device blocks go back to their pools)."""

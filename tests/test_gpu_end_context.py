@@ -249,6 +249,40 @@ def test_ref_context(engine, world, name):
         assert whole[N].sum() == sum(b - a for a, b in H.LAYOUT[name][1])
 
 
+def test_the_gc_kernels_and_the_context_kernels_read_the_same_bases(engine, tmp_path):
+    """One sequence of 1 003 bases (a multiple of neither 4 nor 16) with an N run inside, N in the last three bases and a
+    lower-case stretch, as 2bit, as FASTA with 60-base lines and as FASTA whose lines are 2 bytes wider than their bases:
+    over every range, the 1 x 2 expected GC table (A + T positions, G + C positions) equals numpy's count of the sequence
+    and the count read off ``ref_context`` by summing its cells over the second base."""
+    from finaletoolkit_amd.reference import ReferenceGenome
+    rng = np.random.default_rng(1003)
+    b = np.frombuffer(b"ACGT", np.uint8)[rng.integers(0, 4, 1003)].copy()
+    b[411:463] = ord("N")
+    b[995:1003] = np.frombuffer(b"GATCANGN", np.uint8)  # (both kinds of base among the last six)
+    b[590:700] |= 0x20  # lower case
+    b[440:450] |= 0x20  # (n inside the N run)
+    seq = b.tobytes().decode()
+    assert len(seq) == 1003 and len(seq) % 4 and len(seq) % 16 and set(seq) >= set("ACGTNacgtn")
+    paths = {"2bit": str(tmp_path / "r.2bit"), "fa60": str(tmp_path / "r60.fa"), "crlf": str(tmp_path / "rcrlf.fa")}
+    write_2bit(paths["2bit"], {"r": seq})
+    write_fasta(paths["fa60"], {"r": seq}, width=60)
+    with open(paths["crlf"], "wb") as fh:
+        fh.write(b">r\r\n" + b"".join(seq[i:i + 70].encode() + b"\r\n" for i in range(0, 1003, 70)))
+    with open(paths["crlf"] + ".fai", "w") as fh:
+        fh.write("r\t1003\t4\t70\t72\n")
+    up = b & 0xDF
+    at, gc = (up == ord("A")) | (up == ord("T")), (up == ord("G")) | (up == ord("C"))
+    for image, path in paths.items():
+        with ReferenceGenome(path) as ref:
+            rid = ref.device_image(engine, "r", with_layout=True)
+            for lo, hi in ((0, 1003), (1, 999), (997, 2000)):
+                want = [int(at[lo:hi].sum()), int(gc[lo:hi].sum())]
+                assert want[0] > 0 and want[1] > 0 and sum(want) < min(hi, 1003) - lo  # both kinds, and an N, in every range
+                cells = engine.ref_context(rid, lo, hi).reshape(5, 5).sum(axis=1)
+                assert [int(cells[0] + cells[3]), int(cells[1] + cells[2])] == want, (image, lo, hi, cells)
+                assert engine.ref_gc_table(rid, lo, hi, 1, 1, 1)[0, :2].tolist() == want, (image, lo, hi)
+
+
 # ---- 4. the top coordinates --------------------------------------------------------------------------------------------
 def test_top_coordinates(engine):
     from finaletoolkit_amd import _lib as L

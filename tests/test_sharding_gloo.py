@@ -187,6 +187,13 @@ def _product_worker(rank, world, port, d, q):
         def close(self):
             pass
 
+        def __enter__(self):
+            return self
+
+        def __exit__(self, exc_type, exc, tb):
+            for c in () if exc_type else self.required:  # (set by the command before the exit)
+                src.has(c) or src.require(c)
+
     Cv.ContigFeed = Feed
     Df.resident_contigs = lambda path, names, *a, **k: ((src, c) for c in names if src.has(c))
     Df.region_contig = lambda path, c, lo, hi, *a, **k: (src, src.require(c))  # (the whole contig: a superset of the region)
