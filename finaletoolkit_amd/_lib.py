@@ -59,7 +59,7 @@ MAX_TELOMERES = 8
 EXPORTS = [
     "ftk_version", "ftk_device_count", "ftk_ctx_create", "ftk_ctx_destroy", "ftk_last_error",
     "ftk_ctx_set_stream", "ftk_ctx_sync", "ftk_timer_start", "ftk_timer_stop", "ftk_event_record",
-    "ftk_event_elapsed_ms",
+    "ftk_event_elapsed_ms", "ftk_ctx_scratch_fill",
     "ftk_frags_from_host", "ftk_frags_from_device", "ftk_frags_set_read1", "ftk_frags_set_order", "ftk_frags_load_fraggz", "ftk_frags_load_bam", "ftk_frags_name",
     "ftk_frags_info", "ftk_frags_packed", "ftk_frags_release",
     "ftk_fragfile_decode", "ftk_bam_decode", "ftk_host_alloc", "ftk_host_alloc_pageable", "ftk_host_free", "ftk_cache_trim", "ftk_wps_async", "ftk_result_wait", "ftk_fragfile_index_contigs", "ftk_fragstream_open", "ftk_fragstream_open_device", "ftk_fragstream_open_region", "ftk_fragtable_is_device", "ftk_fragtable_ready_event", "ftk_fragtable_columns_to_host", "ftk_fragtable_read1_to_host", "ftk_fragstream_next", "ftk_fragstream_n_refs",
@@ -258,6 +258,7 @@ def load() -> C.CDLL:
     lib.ftk_ctx_destroy.restype = None
     lib.ftk_ctx_set_stream.argtypes = [vp, vp]
     lib.ftk_ctx_sync.argtypes = [vp]
+    lib.ftk_ctx_scratch_fill.argtypes = [vp, C.c_int, pi64]
     lib.ftk_timer_start.argtypes = [vp]
     lib.ftk_timer_stop.argtypes = [vp, C.POINTER(C.c_float)]
     lib.ftk_event_record.argtypes = [vp, C.c_int]

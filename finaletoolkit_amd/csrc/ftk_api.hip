@@ -741,6 +741,19 @@ int ftk_ctx_sync(ftk_ctx* ctx) {
     return FTK_OK;
 }
 
+// Diagnostics: the scratch block as it stands, filled with one byte value (tests: a call's result must not depend on what
+// the block held).  One memset on the ctx stream, behind whatever still reads the block; nothing is allocated or moved.
+int ftk_ctx_scratch_fill(ftk_ctx* ctx, int byte, int64_t* bytes_out) {
+    if (!ctx) return fail(nullptr, FTK_ERR_INVALID, "ctx is NULL");
+    if (byte < -1 || byte > 255) return fail(ctx, FTK_ERR_INVALID, "byte must be -1 (no fill) or in [0, 255], not %d", byte);
+    if (byte >= 0 && ctx->scratch && ctx->scratch_bytes) {
+        HIPCHK(ctx, hipSetDevice(ctx->device));
+        HIPCHK(ctx, hipMemsetAsync(ctx->scratch, byte, ctx->scratch_bytes, ctx->stream));
+    }
+    if (bytes_out) *bytes_out = (int64_t)ctx->scratch_bytes;
+    return FTK_OK;
+}
+
 int ftk_timer_start(ftk_ctx* ctx) {
     if (!ctx) return fail(nullptr, FTK_ERR_INVALID, "ctx is NULL");
     HIPCHK(ctx, hipEventRecord(ctx->ev_start, ctx->stream));

@@ -165,6 +165,14 @@ class Engine:
         self._check(self.lib.ftk_ctx_sync(self.ctx))
         self._pending.clear()
 
+    def scratch_fill(self, byte: Optional[int] = None) -> int:
+        """Diagnostics (``ftk_ctx_scratch_fill``): fill the context's scratch block as it stands with ``byte`` (0 .. 255;
+        ``None``: fill nothing) on the context's stream and return the block's size in bytes.  No result of any call may
+        depend on what the block held."""
+        n = C.c_int64()
+        self._check(self.lib.ftk_ctx_scratch_fill(self.ctx, -1 if byte is None else int(byte), C.byref(n)))
+        return int(n.value)
+
     def timer_start(self):
         self._check(self.lib.ftk_timer_start(self.ctx))
 

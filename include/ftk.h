@@ -96,6 +96,15 @@ const char* ftk_last_error(ftk_ctx* ctx);
  * NULL restores the ctx's own stream. */
 int ftk_ctx_set_stream(ftk_ctx* ctx, void* hip_stream);
 int ftk_ctx_sync(ftk_ctx* ctx);
+
+/* ---- diagnostics ----
+ * Every call carves its temporaries, and the device stand-ins of host outputs, out of one scratch block per ctx that is
+ * never cleared between calls; a call may assume nothing about what the block holds.  ftk_ctx_scratch_fill makes that
+ * testable: byte in [0, 255] enqueues one memset of the whole block as it stands on the ctx stream, byte == -1 fills
+ * nothing; either way *bytes_out (if not NULL) receives the block's size.  Any other byte: FTK_ERR_INVALID.  Nothing is
+ * allocated, the block never moves, and no other memory of the ctx (contigs, reference images, weights, the asynchronous
+ * result buffers) is touched. */
+int ftk_ctx_scratch_fill(ftk_ctx* ctx, int byte, int64_t* bytes_out);
 /* HIP-event stopwatch on the ctx stream (used by bench.py for per-kernel
  * durations).  ftk_timer_stop waits for the stop event. */
 int ftk_timer_start(ftk_ctx* ctx);

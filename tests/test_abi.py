@@ -50,6 +50,18 @@ def test_header_symbols_all_exported():
     assert lib.ftk_version().startswith(b"ftk-hip")
 
 
+def test_scratch_fill_refuses_a_null_context():
+    """ftk_ctx_scratch_fill (diagnostics) checks its context before anything else: NULL is FTK_ERR_INVALID for a fill, for
+    the size query and for a byte out of range alike, and *bytes_out is left alone."""
+    lib = L.load()
+    for byte in (0, 0xFF, -1, 256):
+        n = C.c_int64(-7)
+        assert lib.ftk_ctx_scratch_fill(None, byte, C.byref(n)) == L.FTK_ERR_INVALID
+        assert n.value == -7
+        assert b"ctx is NULL" in lib.ftk_last_error(None)
+    assert lib.ftk_ctx_scratch_fill(None, 0, None) == L.FTK_ERR_INVALID
+
+
 def test_no_gpu_is_a_loud_failure_not_a_fallback():
     import torch
     if torch.cuda.is_available():
