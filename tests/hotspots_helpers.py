@@ -202,3 +202,61 @@ def planted_fragments():
     keep = ~(near & drop)
     start, length = start[keep], length[keep]
     return chrom_size, centres, (start, start + length, np.full(len(start), 60, np.int64))
+
+
+# ---- what the GPU tests share: a resident contig held against the restatement, and fragments built by hand ----------------
+def assert_same(got, want, what=None):
+    assert np.array_equal(got[2], want[2]), (what, got[2].tolist(), want[2].tolist())
+    assert got[0].dtype == WINDOW_DTYPE and same_records(got[0], want[0]), (what, "windows", len(got[0]), len(want[0]))
+    assert got[1].dtype == HOTSPOT_DTYPE and same_records(got[1], want[1]), (what, "hotspots", got[1].tolist()[:5], want[1].tolist()[:5])
+
+
+class Contig:
+    """A contig of the engine's for the length of a ``with`` block."""
+
+    def __init__(self, engine, start, end, mapq, read1=False, name="ifs:case"):
+        order = np.argsort(np.asarray(start), kind="stable")
+        self.cols = tuple(np.asarray(c)[order] for c in (start, end, mapq))
+        self.engine, self.name, self.read1 = engine, name, read1
+
+    def __enter__(self):
+        s, e, q = self.cols
+        strand = np.zeros(len(s), np.uint8)
+        if self.read1:  # forward fragments: read1 is the first 50 bases
+            self.engine.load_contig(self.name, s, e, q, strand, s, np.minimum(s + 50, e))
+        else:
+            self.engine.load_contig(self.name, s, e, q, strand)
+        return self
+
+    def __exit__(self, *exc):
+        self.engine.release(self.name)
+
+    def both(self, starts, stops, size, what=None, tracks=None, **kw):
+        """The engine's hotspots, held against the restatement's."""
+        starts, stops = np.asarray(starts, np.int64), np.asarray(stops, np.int64)
+        got = self.engine.ifs_hotspots(self.name, starts, stops, size, **kw)
+        assert_same(got, ifs_hotspots_ref(*self.cols, starts, stops, size, tracks=tracks, **kw), what)
+        return got
+
+    def track(self, starts, stops, size, what=None, **kw):
+        """The engine's per-window track, on the host and on the device, held against the restatement's."""
+        starts, stops = np.asarray(starts, np.int64), np.asarray(stops, np.int64)
+        n, ifs, offs = self.engine.ifs_track(self.name, starts, stops, size, **kw)
+        want = ifs_track_ref(*self.cols, starts, stops, size, **kw)
+        assert n.dtype == np.int32 and ifs.dtype == np.int64 and np.array_equal(offs, want[2]), (what, offs, want[2])
+        assert np.array_equal(n, want[0]) and np.array_equal(ifs, want[1]), what
+        dn, di, _ = self.engine.ifs_track(self.name, starts, stops, size, device=True, **kw)
+        assert np.array_equal(dn.cpu().numpy(), want[0]) and np.array_equal(di.cpu().numpy(), want[1]), what
+        return n, ifs, offs
+
+
+def columns(*pairs):
+    s = np.concatenate([np.atleast_1d(np.asarray(a, np.int64)) for a, _ in pairs])
+    e = np.concatenate([np.atleast_1d(np.asarray(b, np.int64)) for _, b in pairs])
+    return s, e, np.full(len(s), 60, np.int64)
+
+
+def at(mids, length=10, copies=1):
+    """Fragments of ``length`` (even) bases with their midpoints on ``mids``."""
+    m = np.repeat(np.asarray(mids, np.int64), copies)
+    return m - length // 2, m + length // 2
