@@ -54,7 +54,8 @@ _FLAT_BY_MODULE = {
               "frag_depth", "frag_depth_track", "frag_gc_bias", "frag_gc_coverage", "gc_weights", "read_gc_bias_table",
               "frag_site_profile", "read_sites", "frag_vplot", "VPlot", "frag_wps_spectrum", "WpsSpectrum", "frag_ocf", "OCF",
               "frag_wps_peaks", "WpsPeaks", "frag_preferred_ends", "PreferredEnds", "preferred_end_thresholds",
-              "frag_hotspots", "IfsHotspots", "ifs_thresholds", "frag_end_context", "EndContext"),
+              "frag_hotspots", "IfsHotspots", "ifs_thresholds", "frag_end_context", "EndContext",
+              "frag_cofragmentation", "CoFragmentation", "ks_neglog10_p"),
     "genome": ("GenomeGaps", "ContigGaps", "ucsc_hg19_gap_bed", "b37_gap_bed", "ucsc_hg38_gap_bed"),
     "io": ("Fragment", "AlignmentWrapper"),
 }

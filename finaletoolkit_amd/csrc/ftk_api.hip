@@ -1477,3 +1477,4 @@ static int wps_params(ftk_ctx* ctx, const ContigData& c, int64_t chrom_size, int
 #include "ftk_api_prefends.inc"
 #include "ftk_api_hotspots.inc"
 #include "ftk_api_endcontext.inc"
+#include "ftk_api_cofrag.inc"

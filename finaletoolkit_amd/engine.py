@@ -857,6 +857,53 @@ class Engine:
         self._check(self.lib.ftk_ref_context(self.ctx, int(rid), int(pos_lo), int(pos_hi), L.ptr(out)))
         return out
 
+    # -- co-fragmentation: pairwise KS numerators of length histograms (csrc/ftk_cofrag.hip) ----
+    def hist_ks_shape(self):
+        """``(T, chunk)`` of the tiled pair kernel (``ftk_hist_ks_shape``): the edge of the pair tile one workgroup
+        computes and the lengths it stages per LDS chunk."""
+        t, c = C.c_int32(), C.c_int32()
+        self._check(self.lib.ftk_hist_ks_shape(C.byref(t), C.byref(c)))
+        return int(t.value), int(c.value)
+
+    def hist_ks(self, hist, out=None, at=True):
+        """``(K, at, n)`` of the histogram rows ``hist`` (``ftk_hist_ks``; the rule is in ``include/ftk.h``,
+        "co-fragmentation"): ``hist`` is a uint32 host array or device tensor of shape ``(N, n_bins)``;
+        ``K[i, j] = max over l of |C(i, l) n(j) - C(j, l) n(i)|`` (int64, ``N x N``, symmetric: the two-sample KS statistic
+        is ``K / (n(i) n(j))``), ``at[i, j]`` the smallest ``l`` that attains it (int32; ``None`` with ``at=False``) and
+        ``n`` the row sums (int64), each of which must be below 2**31.  ``out``: an int64 host array or device tensor of
+        ``N * N`` elements to write K into (returned as passed); ``at`` may likewise be an int32 array or tensor."""
+        if isinstance(hist, np.ndarray) or not hasattr(hist, "data_ptr"):
+            hist = np.ascontiguousarray(hist, dtype=np.uint32)
+        if len(hist.shape) != 2:
+            raise ValueError("hist: rows of cells, shape (N, n_bins)")
+        n_rows, n_bins = int(hist.shape[0]), int(hist.shape[1])
+        k = np.empty((n_rows, n_rows), np.int64) if out is None else out
+        if at is True:
+            at = np.empty((n_rows, n_rows), np.int32)
+        elif at is False:
+            at = None
+        n = np.empty(n_rows, np.int64)
+        self._check(self.lib.ftk_hist_ks(self.ctx, L.ptr(hist), n_rows, n_bins, L.ptr(k), L.ptr(at), L.ptr(n)))
+        return k, at, n
+
+    def cofrag(self, name: str, starts, stops, len_lo: int, n_bins: int, quality_threshold=30, min_length=None, max_length=None,
+               intersect_policy="midpoint", out=None, at=True):
+        """``(K, at, n, overflow)`` of the windows of resident contig ``name`` (``ftk_cofrag``): what ``hist_ks`` gives on
+        the rows of ``fraglen_hist`` with the same arguments, and that call's overflow column - the histograms are
+        built and compared on the device and never leave it.  ``out`` / ``at`` as in ``hist_ks``."""
+        ws, we = _win(starts, L.OPEN_LO), _win(stops, L.OPEN_HI)
+        f = self._filter(name, quality_threshold, min_length, max_length, intersect_policy)
+        n_win = len(ws)
+        k = np.empty((n_win, n_win), np.int64) if out is None else out
+        if at is True:
+            at = np.empty((n_win, n_win), np.int32)
+        elif at is False:
+            at = None
+        n, over = np.empty(n_win, np.int64), np.empty(n_win, np.int64)
+        self._check(self.lib.ftk_cofrag(self.ctx, self.contig_id(name), L.ptr(ws), L.ptr(we), n_win, C.byref(f), int(len_lo),
+                                        int(n_bins), L.ptr(k), L.ptr(at), L.ptr(n), L.ptr(over)))
+        return k, at, n, over
+
     # -- per-fragment weights and their sums per window (csrc/ftk_weights.hip) ----------
     def set_weights(self, name: str, w):
         """Attach one weight per fragment to resident contig ``name`` (``ftk_frags_set_weights``): uint32 in units of

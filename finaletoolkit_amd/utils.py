@@ -1772,6 +1772,174 @@ def frag_end_context(input_file, reference_file, output_file=None, contig=None, 
     return res
 
 
+class CoFragmentation(NamedTuple):
+    """Result of ``frag_cofragmentation`` for one contig: the pairwise Kolmogorov-Smirnov distances between the fragment
+    length distributions of its bins and the compartment track read off them.  ``N`` bins; the matrices are ``N x N``."""
+    contig: str
+    starts: np.ndarray      # int64 [N]: bin k is [starts[k], stops[k])
+    stops: np.ndarray       # int64 [N]
+    n: np.ndarray           # int64 [N]: fragments of the bin inside the length range
+    overflow: np.ndarray    # int64 [N]: fragments of the bin that passed the filter outside the histogram's range
+    K: np.ndarray           # int64: the KS numerator, max over lengths of |C(i, l) n(j) - C(j, l) n(i)|
+    at: np.ndarray          # int32: the smallest fragment LENGTH at which that maximum is attained (min_length where K = 0)
+    valid: np.ndarray       # bool [N]: n >= min_count
+    D: np.ndarray           # float64: the KS statistic K / (n(i) n(j)); NaN where either bin is not valid
+    z: np.ndarray           # float64: D sqrt(n(i) n(j) / (n(i) + n(j))); NaN likewise
+    neglog10_p: np.ndarray  # float64: ks_neglog10_p(z); NaN likewise
+    corr: np.ndarray        # float64: Pearson correlation of the rows of the chosen distance over the valid bins; NaN elsewhere
+    pc1: np.ndarray         # float64 [N]: unit eigenvector of corr's largest eigenvalue, largest component positive; NaN at invalid bins
+
+
+def ks_neglog10_p(z) -> np.ndarray:
+    """``-log10 Q(z)`` of the Kolmogorov distribution, ``Q(z) = 2 sum_{k >= 1} (-1)^(k - 1) exp(-2 k^2 z^2)`` summed over
+    ``k`` to 200 in float64: 0 for ``z < 0.04`` (where Q is 1 to the last bit); for ``z >= 1`` evaluated as
+    ``(2 z^2 - ln(2 (1 - e^(-6 z^2) + e^(-16 z^2) - ...))) / ln 10``, which stays finite where Q underflows.  NaN stays
+    NaN.  Any shape; returns float64 of that shape."""
+    z = np.asarray(z, dtype=np.float64)
+    flat = z.ravel()
+    out = np.zeros(flat.shape, np.float64)
+    out[np.isnan(flat)] = np.nan
+    hi = np.flatnonzero(flat >= 1.0)
+    if len(hi):
+        # (k = 20: exp(-2 * 399) is 0 in float64, as is every later term of the 200)
+        k = np.arange(1, 21, dtype=np.float64)
+        sign = np.where(k % 2 == 1, 1.0, -1.0)
+        for lo in range(0, len(hi), 1 << 16):
+            idx = hi[lo:lo + (1 << 16)]
+            z2 = flat[idx] ** 2
+            t = (sign * np.exp(-2.0 * (k * k - 1.0) * z2[:, None])).sum(axis=1)
+            out[idx] = (2.0 * z2 - np.log(2.0 * t)) / np.log(10.0)
+    mid = np.flatnonzero((flat >= 0.04) & (flat < 1.0))
+    if len(mid):
+        mid = mid[np.argsort(flat[mid], kind="stable")]
+        for lo in range(0, len(mid), 1 << 14):
+            idx = mid[lo:lo + (1 << 14)]
+            zz = flat[idx]
+            # the terms with 2 k^2 z^2 > 760 are exactly 0 in float64: leaving them out changes nothing
+            kmax = int(min(200, np.ceil(np.sqrt(380.0) / zz[0]) + 1))
+            k = np.arange(1, kmax + 1, dtype=np.float64)
+            sign = np.where(k % 2 == 1, 1.0, -1.0)
+            q = 2.0 * (sign * np.exp(-2.0 * (k * k) * (zz * zz)[:, None])).sum(axis=1)
+            out[idx] = -np.log10(np.clip(q, np.finfo(np.float64).tiny, 1.0))
+    return out.reshape(z.shape)
+
+
+def cofrag_bins(size: int, bin_size: int, contig: str = "the contig"):
+    """``(starts, stops)`` of the bins ``[k * bin_size, min((k + 1) * bin_size, size))`` of a contig of ``size`` bases, int64;
+    ``ValueError`` when there are more than 4096 (``FTK_COFRAG_MAX_BINS``)."""
+    from . import _lib as L
+    if int(bin_size) < 1:
+        raise ValueError("bin_size must be at least 1")
+    n_bins = -(-max(int(size), 0) // int(bin_size))
+    if n_bins > L.COFRAG_MAX_BINS:
+        raise ValueError(f"{contig}: {n_bins} bins of {int(bin_size)} bases; at most {L.COFRAG_MAX_BINS} bins per contig are "
+                         f"supported - use a larger bin_size")
+    starts = np.arange(n_bins, dtype=np.int64) * int(bin_size)
+    return starts, np.minimum(starts + int(bin_size), int(size))
+
+
+def cofrag_host_part(contig, starts, stops, n, overflow, K, at, len_lo: int, min_count: int = 1000, distance: str = "d") -> CoFragmentation:
+    """The host's arithmetic of ``frag_cofragmentation`` on what the device returned (``Engine.cofrag`` / ``hist_ks``):
+    the mask, ``D``, ``z``, ``neglog10_p``, the row correlation of the chosen distance and its first principal
+    component.  ``at`` comes in as an index ``l`` and leaves as the length ``len_lo + l``."""
+    if distance not in ("d", "z"):
+        raise ValueError(f"invalid distance ({distance!r}): 'd' or 'z'")
+    n = np.asarray(n, dtype=np.int64)
+    K = np.asarray(K, dtype=np.int64)
+    N = len(n)
+    valid = n >= max(int(min_count), 1)
+    pair = valid[:, None] & valid[None, :]
+    nf = n.astype(np.float64)
+    prod, tot = nf[:, None] * nf[None, :], nf[:, None] + nf[None, :]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        D = np.where(pair, K.astype(np.float64) / prod, np.nan)
+        z = np.where(pair, D * np.sqrt(prod / tot), np.nan)
+    p = np.full((N, N), np.nan)
+    iu = np.triu_indices(N)
+    p[iu] = ks_neglog10_p(z[iu])
+    p.T[iu] = p[iu]
+    corr = np.full((N, N), np.nan)
+    pc1 = np.full(N, np.nan)
+    v = np.flatnonzero(valid)
+    if len(v) >= 3:
+        m = (D if distance == "d" else z)[np.ix_(v, v)]
+        with np.errstate(divide="ignore", invalid="ignore"):
+            c = np.corrcoef(m)
+        corr[np.ix_(v, v)] = c
+        w, vec = np.linalg.eigh(np.nan_to_num(c))
+        e = vec[:, int(np.argmax(w))]
+        if e[int(np.argmax(np.abs(e)))] < 0:
+            e = -e
+        pc1[v] = e
+    return CoFragmentation(str(contig), np.asarray(starts, np.int64), np.asarray(stops, np.int64), n, np.asarray(overflow, np.int64),
+                           K, (np.asarray(at, np.int32) + np.int32(len_lo)).astype(np.int32), valid, D, z, p, corr, pc1)
+
+
+def frag_cofragmentation(input_file, bin_size: int = 500_000, contigs=None, chrom_sizes=None, min_length: int = 50,
+                         max_length: int = 1000, quality_threshold: int = 30, min_count: int = 1000, distance: str = "d",
+                         output_file=None, pairs_file=None, workers=None, verbose=False) -> list:
+    """The co-fragmentation map of Liu et al. 2019: every contig of ``input_file`` (or those of ``contigs``) is cut into
+    bins ``[k * bin_size, min((k + 1) * bin_size, chrom_size))``, the length distributions (``min_length .. max_length``, at
+    most 4096 lengths) of the fragments with their midpoint in each bin are compared pair by pair with the two-sample
+    Kolmogorov-Smirnov statistic, the rows of that distance matrix (``distance``: ``"d"`` the statistic, ``"z"`` scaled by
+    ``sqrt(n_i n_j / (n_i + n_j))``) are correlated over the bins with at least ``min_count`` fragments, and the first
+    principal component is the A/B-compartment track.  The histograms are built and compared on the GPU, contig by contig
+    as the input is decoded (``Engine.cofrag``; the rule is in ``include/ftk.h``, "co-fragmentation"): the integer matrix K
+    comes back, the float arithmetic on its N^2 values is the host's.  Needs no site list, reference or second sample.
+
+    Chromosome sizes: the BAM header, else the ``chrom_sizes`` file, else ``ValueError``.  A contig of more than 4096 bins
+    raises ``ValueError``.  Returns one ``CoFragmentation`` per contig, in the order the contigs are met.  ``output_file``
+    (``.tsv`` / ``.tsv.gz``): ``writers.write_cofrag_track``; ``pairs_file``: ``writers.write_cofrag_pairs``."""
+    import os
+    import sys
+    import time
+
+    from . import _lib as L
+    from . import writers
+    from .source import ContigFeed
+    _check_suffix(output_file, "output_file", "tsv")
+    _check_suffix(pairs_file, "pairs_file", "tsv")
+    if distance not in ("d", "z"):
+        raise ValueError(f"invalid distance ({distance!r}): 'd' or 'z'")
+    if int(bin_size) < 1:
+        raise ValueError("bin_size must be at least 1")
+    len_lo, n_len = int(min_length), int(max_length) - int(min_length) + 1
+    if len_lo < 0 or n_len < 1 or n_len > L.COFRAG_MAX_LEN_BINS:
+        raise ValueError(f"min_length .. max_length must hold 1 to {L.COFRAG_MAX_LEN_BINS} lengths from 0 up")
+    if not _is_alignment_file(input_file) and chrom_sizes is None:
+        raise ValueError("chrom_sizes is needed for an input without a header")
+    t0 = time.time()
+    sizes = None if _is_alignment_file(input_file) else chrom_sizes_to_dict(chrom_sizes)
+    names = None if contigs is None else list(contigs)
+    if sizes is not None and names is not None:
+        for c in names:
+            if c not in sizes:
+                raise ValueError(f"{c} is not in chrom_sizes")
+    results = []
+    eng = get_engine()
+    with ContigFeed(input_file, workers, names=names, require=() if names is None else names) as feed:
+        for src, c in feed:
+            if names is not None and c not in names:
+                continue
+            if sizes is not None and c not in sizes:
+                raise ValueError(f"{c} is not in chrom_sizes")
+            size = int(src.lengths[c]) if sizes is None else int(sizes[c])
+            starts, stops = cofrag_bins(size, bin_size, c)
+            if len(starts) == 0:
+                continue
+            K, at, n, over = eng.cofrag(src.key(c), starts, stops, len_lo, n_len, quality_threshold, len_lo, int(max_length))
+            results.append(cofrag_host_part(c, starts, stops, n, over, K, at, len_lo, min_count, distance))
+            if verbose:
+                sys.stderr.write(f"frag_cofragmentation: {c}: {len(starts)} bins, {int(results[-1].valid.sum())} valid\n")
+    if output_file is not None:
+        writers.write_cofrag_track(os.fspath(output_file), results)
+    if pairs_file is not None:
+        writers.write_cofrag_pairs(os.fspath(pairs_file), results)
+    if verbose:
+        sys.stderr.write(f"frag_cofragmentation: {len(results)} contigs in {time.time() - t0:.3f} s\n")
+    return results
+
+
 def agg_bw(input_file, interval_file, output_file, median_window_size: int = 1, mean: bool = False,
            verbose: bool = False) -> np.ndarray:
     """Aggregate a bigWig signal across strand-oriented intervals (reference: ``utils/_agg_bw.py:18-146``):

@@ -550,3 +550,43 @@ def write_end_context_rows(output_file: str, res) -> None:
     if not output_file.endswith(END_CONTEXT_SUFFIXES):
         raise ValueError(message)
     _emit(output_file, end_context_text(res), (".tsv",), (".tsv.gz",), message)
+
+
+COFRAG_TRACK_HEADER = "contig\tstart\tstop\tn_frags\toverflow\tvalid\tpc1\n"
+COFRAG_PAIRS_HEADER = "contig\tstart_i\tstart_j\tn_i\tn_j\tks_num\td\tat\tz\tneglog10_p\tcorr\n"
+
+
+def cofrag_track_text(results) -> str:
+    """The bins of ``utils.CoFragmentation`` results, contig by contig: the header ``contig start stop n_frags overflow
+    valid pc1``, ``valid`` as 0 / 1, ``pc1`` as ``repr(float)`` (``nan`` at a bin that is not valid)."""
+    rows = [COFRAG_TRACK_HEADER]
+    for r in results:
+        rows += [f"{r.contig}\t{int(a)}\t{int(b)}\t{int(n)}\t{int(o)}\t{int(v)}\t{float(p)!r}\n"
+                 for a, b, n, o, v, p in zip(r.starts, r.stops, r.n, r.overflow, r.valid, r.pc1)]
+    return "".join(rows)
+
+
+def cofrag_pairs_text(results) -> str:
+    """The bin pairs ``i < j`` of ``utils.CoFragmentation`` results, row-major: the header ``contig start_i start_j n_i n_j
+    ks_num d at z neglog10_p corr``; the floats as ``repr(float)``, ``nan`` where a bin of the pair is not valid."""
+    rows = [COFRAG_PAIRS_HEADER]
+    for r in results:
+        for i in range(len(r.n)):
+            rows += [f"{r.contig}\t{int(r.starts[i])}\t{int(r.starts[j])}\t{int(r.n[i])}\t{int(r.n[j])}\t{int(r.K[i, j])}\t"
+                     f"{float(r.D[i, j])!r}\t{int(r.at[i, j])}\t{float(r.z[i, j])!r}\t{float(r.neglog10_p[i, j])!r}\t"
+                     f"{float(r.corr[i, j])!r}\n" for j in range(i + 1, len(r.n))]
+    return "".join(rows)
+
+
+def write_cofrag_track(output_file: str, results) -> None:
+    """``cofrag_track_text`` to ``output_file``: ``.tsv`` as text, ``.tsv.gz`` as gzip."""
+    message = "output_file should have .tsv or .tsv.gz as suffix"
+    check_suffix(output_file, (".tsv", ".tsv.gz"), message)
+    _emit(output_file, cofrag_track_text(results), (".tsv",), (".tsv.gz",), message)
+
+
+def write_cofrag_pairs(pairs_file: str, results) -> None:
+    """``cofrag_pairs_text`` to ``pairs_file``: ``.tsv`` as text, ``.tsv.gz`` as gzip."""
+    message = "pairs_file should have .tsv or .tsv.gz as suffix"
+    check_suffix(pairs_file, (".tsv", ".tsv.gz"), message)
+    _emit(pairs_file, cofrag_pairs_text(results), (".tsv",), (".tsv.gz",), message)

@@ -1109,6 +1109,40 @@ int ftk_end_context(ftk_ctx* ctx, int contig_id, int ref_id, int32_t half_width,
 int ftk_ref_context(ftk_ctx* ctx, int ref_id, int64_t pos_lo, int64_t pos_hi, int64_t* out25);
 int ftk_end_context_lds_classes(int32_t half_width);
 
+/* ---- co-fragmentation: pairwise KS distances between fragment-length histograms (csrc/ftk_cofrag.hip) ---------
+ * The co-fragmentation map of Liu et al. 2019: a contig is cut into large bins, the fragment-length distributions of
+ * every pair of bins are compared with the two-sample Kolmogorov-Smirnov statistic, and the rows of that distance
+ * matrix are correlated (the host's part).  Everything the device returns is an integer.
+ *
+ *  1. Input: hist is N rows of n_bins uint32 cells, 1 <= N <= FTK_COFRAG_MAX_BINS, 1 <= n_bins <=
+ *     FTK_COFRAG_MAX_LEN_BINS.  n(i) is the sum of row i, C(i, l) the sum of its cells 0 .. l.  Every n(i) must be
+ *     < 2^31: a larger row sum is FTK_ERR_INVALID naming the first such row, found on the device before anything is
+ *     written.
+ *  2. Statistic: K(i, j) = max over l of |C(i, l) n(j) - C(j, l) n(i)|; the KS statistic is D = K / (n(i) n(j)).  Both
+ *     products are below 2^62 and their difference fits a signed 64-bit word: nothing overflows.  K(i, i) = 0.  A pair
+ *     with n(i) = 0 or n(j) = 0 has K = 0 by the formula; the caller masks it.  at(i, j) is the SMALLEST l at which the
+ *     maximum is attained, 0 when K = 0.
+ *  3. Outputs: k_out int64 [N][N], full and symmetric; at_out int32 [N][N], symmetric, NULL switches it off; n_out
+ *     int64 [N].  Each may be host or device memory.  The call writes every cell; a failing call writes nothing.
+ *
+ * ftk_hist_ks        the rule over any histogram rows (host or device).
+ * ftk_cofrag         exactly what ftk_hist_ks gives on the rows ftk_fraglen_hist returns for the same windows (1 <=
+ *                    n_win <= FTK_COFRAG_MAX_BINS), filter, len_lo and n_bins - lengths outside [len_lo, len_lo +
+ *                    n_bins) take no part - with overflow_out [n_win] (host or device) ftk_fraglen_hist's overflow
+ *                    column.  The rows are built in the scratch and never leave the device.
+ * ftk_hist_ks_shape  two constants of the tiled pair kernel: the edge T of the pair tile one workgroup computes and
+ *                    the lengths it stages per LDS chunk (tests place their shapes around them).
+ * FTK_COFRAG_ARRANGE=0 (read at every call) selects the thread-per-pair kernel instead of the tiled one; both give the
+ * same cells.  FTK_ERR_INVALID: a NULL argument, N or n_bins out of range, a row sum >= 2^31, a bad filter;
+ * FTK_ERR_NO_CONTIG: an unknown contig. */
+#define FTK_COFRAG_MAX_BINS 4096
+#define FTK_COFRAG_MAX_LEN_BINS 4096
+int ftk_hist_ks(ftk_ctx* ctx, const uint32_t* hist /* host or device */, int64_t n_rows, int32_t n_bins, int64_t* k_out,
+                int32_t* at_out /* NULL: off */, int64_t* n_out);
+int ftk_cofrag(ftk_ctx* ctx, int contig_id, const int32_t* w_start, const int32_t* w_end, int64_t n_win, const ftk_filter* f,
+               int32_t len_lo, int32_t n_bins, int64_t* k_out, int32_t* at_out, int64_t* n_out, int64_t* overflow_out);
+int ftk_hist_ks_shape(int32_t* tile_out, int32_t* chunk_out);
+
 /* ---- multi-GPU (SURVEY 8-e, 8-b's export list) -------------------------------------------------
  * One process and one ftk_ctx per GPU.  Contigs / genome runs are dealt to the ranks by the host and every window,
  * bin and base depends on its own contig's fragments only, so the data path has no collective.  What remains are the

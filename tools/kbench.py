@@ -19,7 +19,11 @@ alpha = 1e-5) - the whole call, the totals reduction, the per-window track into 
 at h = 500 on the same contig, with the call's byte floor.
 KBENCH=endcontext: the end-context table at W = 32 with the default length classes against the 2bit image of KBENCH=gcbias, in both
 LDS arrangements (lanes are offsets / lanes are fragments), beside ftk_frag_gc_table on the same contig and image and beside the
-route there was before: 64 calls of ftk_motif_counts, one per offset; and the background, ftk_ref_context of the whole image."""
+route there was before: 64 calls of ftk_motif_counts, one per offset; and the background, ftk_ref_context of the whole image.
+KBENCH=cofrag: the co-fragmentation map of the contig's first 2490 bins of 100 kb over lengths 0-1000 (run it on the chr1-sized
+contig: `tools/kbench.py 249250621`) - ftk_hist_ks alone on resident histogram rows in both arrangements of the pair kernel
+(a thread per pair / a workgroup per 64 x 64 tile), ftk_cofrag end to end, the histogram launch alone, and the numpy
+restatement on this host at N = 500 (KBENCH_COFRAG_CPU=0 leaves it out)."""
 import os
 import sys
 
@@ -764,3 +768,70 @@ if "endcontext" in which:
     del os.environ["FTK_CONTEXT_ARRANGE"]
     print("endcontext checksum", int(table.sum()), int(table[..., 20:].sum()), int(eng.ref_context(ride, 0, size).sum()),
           "(share of the LDS estimate = the us above / the measured us)")
+if "cofrag" in which:
+    # Co-fragmentation: N = 2490 bins of 100 kb (chr1 at that bin size), lengths 0 .. 1000.  The work is pair steps, not bytes:
+    # N (N + 1) / 2 pairs x n_bins lengths, each two 32 x 32 -> 64 multiplies, a 64-bit subtraction, an absolute value, a compare
+    # and three selects (13 vector instructions in the tiled kernel's inner loop, docs/experiments.md).  Outputs stay on the
+    # device except in the "host outputs" row, which adds the 74 MB of K and `at` on their way home.
+    import ctypes as C
+    import time
+    from finaletoolkit_amd import _lib as L
+    N, NB = min(2490, len(ws)), 1001
+    c_ws, c_we = np.ascontiguousarray(ws[:N]), np.ascontiguousarray(we[:N])
+    flt = L.make_filter(30, None, None, "midpoint")
+    d_hist = torch.zeros((N, NB), dtype=torch.int32, device=dev)
+    d_over = torch.zeros(N, dtype=torch.int64, device=dev)
+    d_k = torch.zeros((N, N), dtype=torch.int64, device=dev)
+    d_at = torch.zeros((N, N), dtype=torch.int32, device=dev)
+    d_n = torch.zeros(N, dtype=torch.int64, device=dev)
+
+    def hist_only():
+        eng._check(eng.lib.ftk_fraglen_hist(eng.ctx, eng.contig_id("c"), L.ptr(c_ws), L.ptr(c_we), N, C.byref(flt), 0, NB, L.ptr(d_hist),
+                                            L.ptr(d_over)))
+
+    def ks(arrange, at=True):
+        os.environ["FTK_COFRAG_ARRANGE"] = arrange
+        eng._check(eng.lib.ftk_hist_ks(eng.ctx, L.ptr(d_hist), N, NB, L.ptr(d_k), L.ptr(d_at) if at else None, L.ptr(d_n)))
+
+    def whole(arrange):
+        os.environ["FTK_COFRAG_ARRANGE"] = arrange
+        eng._check(eng.lib.ftk_cofrag(eng.ctx, eng.contig_id("c"), L.ptr(c_ws), L.ptr(c_we), N, C.byref(flt), 0, NB, L.ptr(d_k), L.ptr(d_at),
+                                      L.ptr(d_n), L.ptr(d_over)))
+
+    hist_only()
+    got = {}
+    for a in ("0", "1"):
+        ks(a)
+        torch.cuda.synchronize()
+        got[a] = (d_k.cpu().numpy().copy(), d_at.cpu().numpy().copy(), d_n.cpu().numpy().copy())
+    assert all(np.array_equal(x, y) for x, y in zip(got["0"], got["1"]))
+    whole("1")
+    torch.cuda.synchronize()
+    assert np.array_equal(d_k.cpu().numpy(), got["1"][0]) and np.array_equal(d_at.cpu().numpy(), got["1"][1])
+    steps = N * (N + 1) // 2 * NB
+    n_cu = torch.cuda.get_device_properties(0).multi_processor_count
+    print(f"cofrag: {N} bins x {NB} lengths, {steps} pair steps, {int(got['1'][2].sum())} fragments in range, {n_cu} CUs", flush=True)
+    nbytes = N * NB * 4 + N * N * 12
+    for _ in range(2):  # twice: the spread between the two passes is the noise
+        timeit(hist_only, "fraglen_hist 2490 x 1001", 10 * n)
+        timeit(lambda: ks("0"), "hist_ks, thread per pair", nbytes)
+        timeit(lambda: ks("1"), "hist_ks, 64 x 64 tiles", nbytes)
+        timeit(lambda: ks("1", at=False), "hist_ks, tiles, no at", nbytes - N * N * 4)
+        timeit(lambda: whole("0"), "cofrag, thread per pair", 10 * n + nbytes)
+        timeit(lambda: whole("1"), "cofrag, 64 x 64 tiles", 10 * n + nbytes)
+    os.environ["FTK_COFRAG_ARRANGE"] = "1"
+    h_hist = d_hist.cpu().numpy().view(np.uint32)
+    timeit(lambda: eng.hist_ks(h_hist), "hist_ks, host in and out", nbytes)
+    del os.environ["FTK_COFRAG_ARRANGE"]
+    if os.environ.get("KBENCH_COFRAG_CPU", "1") != "0":
+        from tests import cofrag_helpers
+        sub = h_hist[:500]
+        ts = []
+        for _ in range(3):
+            t0 = time.perf_counter()
+            ck = cofrag_helpers.ks_matrix(sub)
+            ts.append(time.perf_counter() - t0)
+        assert np.array_equal(ck[0], got["1"][0][:500, :500]) and np.array_equal(ck[1], got["1"][1][:500, :500])
+        print(f"numpy restatement on this host, N = 500 x {NB}: best of 3 {min(ts):.3f} s; SCALED by (N / 500)^2 to N = {N}: "
+              f"{min(ts) * (N / 500) ** 2:.1f} s", flush=True)
+    print("cofrag checksum", int(got["1"][0].sum() % (1 << 61)), int(got["1"][1].sum()), int(got["1"][2].sum()))
