@@ -446,8 +446,11 @@ int upload_common(ftk_ctx* ctx, int contig_id, const int32_t* start, const int32
     // leave the allocation
     size_t n_pad = ((size_t)n + 3) / 4 * 4 + 4;
     size_t b_i32 = align_up(n_pad * 4), b_u8 = align_up(n_pad);
-    // the packed (length, mapq) words sit behind the four columns: the stats kernel below writes them, padding included
-    size_t wide = 2 * b_i32 + 2 * b_u8, total = wide + align_up(n_pad * 2);
+    // the packed (length, mapq) words sit behind the four columns, the start deltas and their group bases (ftk_packed.h;
+    // whole groups, one past n_pad) behind them: the stats kernel below writes all three, padding included
+    size_t n_grp = n_pad / kDsGroup + 1;
+    size_t wide = 2 * b_i32 + 2 * b_u8, b_lq = align_up(n_pad * 2), b_ds = align_up(n_grp * kDsGroup);
+    size_t total = wide + b_lq + b_ds + align_up(n_grp * 4);
     HIPCHK(ctx, hipMalloc(&c.base, total));
     char* base = (char*)c.base;
     int32_t* d_start = (int32_t*)base;
@@ -455,6 +458,8 @@ int upload_common(ftk_ctx* ctx, int contig_id, const int32_t* start, const int32
     uint8_t* d_mapq = (uint8_t*)(base + 2 * b_i32);
     uint8_t* d_strand = (uint8_t*)(base + 2 * b_i32 + b_u8);
     uint16_t* d_lq = (uint16_t*)(base + wide);
+    uint8_t* d_ds = (uint8_t*)(base + wide + b_lq);
+    int32_t* d_gbase = (int32_t*)(base + wide + b_lq + b_ds);
     hipStream_t s = ctx->stream;
     hipError_t e = hipMemsetAsync(c.base, 0, wide, s);
     // padding fragments sit at 2^30, beyond every coordinate: no window test accepts them, so the
@@ -480,7 +485,7 @@ int upload_common(ftk_ctx* ctx, int contig_id, const int32_t* start, const int32
     if (!ctx->d_stats) e = hipMalloc(&ctx->d_stats, sizeof(FragStats));
     FragStats* d_st = (FragStats*)ctx->d_stats;
     if (e == hipSuccess) e = hipMemcpyAsync(d_st, &init, sizeof(init), hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) launch_stats(s, d_start, d_end, d_mapq, d_lq, (int)n, (int)n_pad, d_st);  // (n = 0: the padding words alone)
+    if (e == hipSuccess) launch_stats(s, d_start, d_end, d_mapq, d_lq, d_ds, d_gbase, (int)n, (int)n_pad, d_st);  // (n = 0: the padding words alone)
     if (e == hipSuccess) e = hipMemcpyAsync(&h_st, d_st, sizeof(h_st), hipMemcpyDeviceToHost, s);
     // the last start (the largest: the columns are sorted) for the position index below - on the ctx stream with the
     // summary: a synchronous hipMemcpy here waited for whatever transfer the device had in flight, 7-29 ms per contig
@@ -529,6 +534,8 @@ int upload_common(ftk_ctx* ctx, int contig_id, const int32_t* start, const int32
     // the packed column holds every fragment exactly when none is longer than kLqLenMax (0 <= len and 0 <= start were
     // checked above); otherwise it stays unused and every kernel reads end and mapq
     c.v.lq = c.max_len <= kLqLenMax ? d_lq : nullptr;
+    c.v.ds = c.v.lq ? d_ds : nullptr;  // sorted, 0 <= start < 2^30: every delta is what ftk_packed.h says
+    c.v.gbase = c.v.lq ? d_gbase : nullptr;
     c.v.lq_len_max = kLqLenMax;
     c.v.r1_start = nullptr;
     c.v.r1_end = nullptr;
@@ -921,6 +928,8 @@ int ftk_frags_set_read1(ftk_ctx* ctx, int contig_id, const int32_t* r1_start, co
     c->v.r1_start = c->r1;
     c->v.r1_end = (int32_t*)((char*)c->r1 + b);
     c->v.lq = nullptr;  // a contig with read1 columns keeps the wide kernels (their BAM forms have no packed variant)
+    c->v.ds = nullptr;
+    c->v.gbase = nullptr;
     static const bool r1_always = getenv("FTK_R1_ALWAYS") && atoi(getenv("FTK_R1_ALWAYS")) != 0;  // tests: both code paths
     c->v.r1_inside = (bad == 0 && !r1_always) ? 1 : 0;
     return FTK_OK;

@@ -21,6 +21,26 @@ __device__ __forceinline__ int wave_incl_scan_dpp(int x) {
     return x;
 }
 
+// inclusive prefix sum inside each row of 16 lanes (the first four steps above).  A lane only takes from lower lanes of
+// its row, so a row whose upper lanes are switched off still gives the lower ones their sums.
+__device__ __forceinline__ int row_incl_scan_dpp(int x) {
+    x += __builtin_amdgcn_update_dpp(0, x, 0x111, 0xf, 0xf, false);
+    x += __builtin_amdgcn_update_dpp(0, x, 0x112, 0xf, 0xf, false);
+    x += __builtin_amdgcn_update_dpp(0, x, 0x114, 0xf, 0xf, false);
+    x += __builtin_amdgcn_update_dpp(0, x, 0x118, 0xf, 0xf, false);
+    return x;
+}
+
+// Four consecutive starts from the delta columns (ContigView::ds / gbase, ftk_packed.h): the lane holds the deltas of
+// fragments i .. i + 3 in one dword (i a multiple of 4), the 16 lanes of its row hold one group of 64 in order, gb is the
+// group's base.  An in-lane prefix, a scan over the row, the base.  Not for a group whose base carries kGbaseWide.
+__device__ __forceinline__ int4 starts_from_deltas(unsigned dsw, int gb) {
+    const int p0 = (int)(dsw & 255u), p1 = p0 + (int)((dsw >> 8) & 255u), p2 = p1 + (int)((dsw >> 16) & 255u),
+              p3 = p2 + (int)(dsw >> 24);
+    const int before = gb + row_incl_scan_dpp(p3) - p3;  // the start of the fragment in front of the lane's four
+    return make_int4(before + p0, before + p1, before + p2, before + p3);
+}
+
 // the sum over the 64 lanes of a wave, in every lane
 __device__ __forceinline__ unsigned int wave_sum_u32(unsigned int v) {
 #pragma unroll

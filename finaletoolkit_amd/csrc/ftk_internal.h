@@ -24,16 +24,20 @@ constexpr int kPadCoord = 1 << 30;
 // Positions per WPS tile.
 constexpr int kWpsTile = 4096;
 
-// One contig's fragments, resident in HBM (start-sorted SoA, 10 B / fragment, + 2 B for the packed word).
+// One contig's fragments, resident in HBM (start-sorted SoA, 10 B / fragment, + 3.07 B for the packed columns).
 // lq: the packed (length, mapq) column, built with the load-time statistics (stats_kernel) and read INSTEAD of end and
-// mapq by the PACKED forms of the FAST feature blocks and the WPS tiles (6 B per fragment instead of 9).  Present only
+// mapq by the PACKED forms of the FAST feature blocks and the WPS tiles.  Present only
 // when every fragment has 0 <= len <= lq_len_max and start >= 0, and the contig has no read1 columns; else nullptr and
 // every kernel reads the wide columns.  The word and which calls may use it: ftk_packed.h (packed_call_ok).
+// ds, gbase: the start column as 1-byte deltas inside groups of 64 fragments, read by the same PACKED forms instead of
+// start (3 B per fragment instead of 9); built by the same pass, present exactly when lq is.
 struct ContigView {
     const int32_t* start;
     const int32_t* end;
     const uint8_t* mapq;
     const uint16_t* lq;       // packed (length, mapq) words, or nullptr
+    const uint8_t* ds;        // 1-byte start deltas and ...
+    const int32_t* gbase;     // ... one base per 64 fragments (ftk_packed.h); present exactly when lq is
     const uint8_t* strand;
     const int32_t* r1_start;  // BAM only (else nullptr)
     const int32_t* r1_end;

@@ -43,9 +43,10 @@ struct CleaveParams {
 };
 
 // lq (may be NULL): also writes the contig's packed (length, mapq) column (ContigView::lq), n_pad words of it (the ones
-// behind the n fragments are cleared)
-void launch_stats(hipStream_t s, const int32_t* start, const int32_t* end, const uint8_t* mapq, uint16_t* lq, int n,
-                  int n_pad, FragStats* st);
+// behind the n fragments are cleared), and with it the start deltas ds and their group bases gbase (ContigView::ds,
+// ContigView::gbase; ftk_packed.h): n_pad / 64 + 1 whole groups of them
+void launch_stats(hipStream_t s, const int32_t* start, const int32_t* end, const uint8_t* mapq, uint16_t* lq, uint8_t* ds,
+                  int32_t* gbase, int n, int n_pad, FragStats* st);
 // Calls that read the packed column instead of end / mapq so far in this process (a debug counter: tests tell the two
 // paths apart with it).
 long long packed_launches();

@@ -60,17 +60,28 @@ __device__ __forceinline__ int last_at_or_below(int n, Pred&& at_or_below) {
 constexpr int kStatsThreads = 256;
 __global__ __launch_bounds__(kStatsThreads) void stats_kernel(const int32_t* start, const int32_t* end,
                                                               const uint8_t* __restrict__ mapq,
-                                                              uint16_t* __restrict__ lq, int n, int n_pad,
+                                                              uint16_t* __restrict__ lq, uint8_t* __restrict__ ds,
+                                                              int32_t* __restrict__ gbase, int n, int n_pad, int n_all,
                                                               FragStats* st) {
     __shared__ int red[5][kStatsThreads / 64];
     int unsorted = 0, max_len = INT32_MIN, min_len = INT32_MAX, max_end = INT32_MIN, min_start = INT32_MAX;
-    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n_pad; i += gridDim.x * blockDim.x) {
+    // n_all: n without the packed columns; with them a multiple of 64, so a wave is one group of the delta columns
+    // (ftk_packed.h) in every pass of the loop and all of its lanes reach the ballot
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n_all; i += gridDim.x * blockDim.x) {
+        const int s = i < n ? start[i] : kPadCoord;
+        const int prev = i == 0 ? s : i <= n ? start[i - 1] : kPadCoord;
+        if (lq) {
+            const unsigned dlt = (i & (kDsGroup - 1)) ? (unsigned)s - (unsigned)prev : 0u;
+            ds[i] = (uint8_t)dlt;
+            const bool wide = __ballot(dlt > 255u) != 0;
+            if ((i & (kDsGroup - 1)) == 0) gbase[i / kDsGroup] = (int32_t)((unsigned)s | (wide ? kGbaseWide : 0u));
+        }
         if (i >= n) {
-            lq[i] = 0;
+            if (i < n_pad) lq[i] = 0;
             continue;
         }
-        int s = start[i], e = end[i];
-        if (i > 0 && start[i - 1] > s) unsorted = 1;
+        const int e = end[i];
+        if (prev > s) unsorted = 1;
         int len = e - s;
         if (lq) lq[i] = (uint16_t)(min(max(len, 0), kLqLenSat) << kLqBits | min((int)mapq[i], kLqMapqSat));
         max_len = max(max_len, len);
@@ -1087,9 +1098,13 @@ __device__ __forceinline__ void fast_group(const ContigView& cv, const FeatParam
     for (int j = 0; j < 4; ++j) fast_element<CHK, HIST, DF, BL, GAPS>(P, fs[j], fe[j], x[j], o0, o1, h, a);
 }
 
-// Four fragments in flight: their starts, ends and mapqs (36 B, three loads), or - PACKED - their starts and their four
-// packed (length, mapq) words (24 B, two loads; ContigView::lq).  get() hands out what fast_group takes either way:
-// end = start + (lq >> kLqBits), mapq = lq & kLqMapqSat (saturated: packed_call_ok admits no threshold above it).
+// Four fragments in flight: their starts, ends and mapqs (36 B, three loads), or - PACKED - their four start deltas and
+// their four packed (length, mapq) words (12 B, two loads, and the group's base: one address per 16 lanes;
+// ContigView::ds, gbase, lq).  get() hands out what fast_group takes either way: the starts rebuilt over the lane's row
+// (starts_from_deltas: the block's range begins on a group, a lane owns four consecutive fragments, so a row of 16 lanes
+// is one group; the lanes of a row that are past the range are the upper ones) or, for a group whose base carries
+// kGbaseWide, read from the wide column here; end = start + (lq >> kLqBits), mapq = lq & kLqMapqSat (saturated:
+// packed_call_ok admits no threshold above it).
 template <bool PACKED>
 struct FastSlab {
     int4 s, e;
@@ -1099,18 +1114,22 @@ struct FastSlab {
         e = *reinterpret_cast<const int4*>(cv.end + i);
         q = *reinterpret_cast<const uchar4*>(cv.mapq + i);
     }
-    __device__ __forceinline__ void get(int4& s_, int4& e_, uchar4& q_) const { s_ = s; e_ = e; q_ = q; }
+    __device__ __forceinline__ void get(const ContigView&, int, int4& s_, int4& e_, uchar4& q_) const { s_ = s; e_ = e; q_ = q; }
 };
 template <>
 struct FastSlab<true> {
-    int4 s;
-    uint2 l;  // lq[i .. i + 3]
+    unsigned d;  // ds[i .. i + 3]
+    int gb;      // gbase[i / 64]
+    uint2 l;     // lq[i .. i + 3]
     __device__ __forceinline__ void load(const ContigView& cv, int i) {
-        s = *reinterpret_cast<const int4*>(cv.start + i);
+        d = *reinterpret_cast<const unsigned*>(cv.ds + i);
+        gb = cv.gbase[i / kDsGroup];
         l = *reinterpret_cast<const uint2*>(cv.lq + i);
     }
-    __device__ __forceinline__ void get(int4& s_, int4& e_, uchar4& q_) const {
+    __device__ __forceinline__ void get(const ContigView& cv, int i, int4& s_, int4& e_, uchar4& q_) const {
         const unsigned w[4] = {l.x & 0xffffu, l.x >> 16, l.y & 0xffffu, l.y >> 16};
+        int4 s = starts_from_deltas(d, gb);
+        if (gb < 0) s = *reinterpret_cast<const int4*>(cv.start + i);
         s_ = s;
         e_ = make_int4(s.x + (int)(w[0] >> kLqBits), s.y + (int)(w[1] >> kLqBits), s.z + (int)(w[2] >> kLqBits),
                        s.w + (int)(w[3] >> kLqBits));
@@ -1136,7 +1155,7 @@ __device__ __forceinline__ void fast_stream(const ContigView& cv, const FeatPara
             if (i < hi) {
                 int4 s, e;
                 uchar4 q;
-                slab[u].get(s, e, q);
+                slab[u].get(cv, i, s, e, q);
                 const int nxt = i + 16 * kFeatBS;
                 if (nxt < hi) slab[u].load(cv, nxt);
                 fast_group<CHK, HIST, DF, BL, GAPS, BAM>(cv, P, i, s, e, q, W, o0, o1, h, a);
@@ -1153,6 +1172,9 @@ __device__ __forceinline__ void feat_fast_body(const ContigView& cv, int ws_raw,
     int lo, hi;
     uint32_t nc;
     window_candidates(cv, ws_raw, we_raw, lmax, -1, lo, hi, nc);
+    // PACKED: the range begins on a group of the delta columns (FastSlab<true>); the window test rejects the surplus
+    // candidates in front like the index's own, and they are counted as processed below
+    if (PACKED && hi > lo) lo &= ~(kDsGroup - 1);
     if (HIST) {
         for (int b = tid; b <= P.n_bins; b += kFeatBS) lds_hist[b] = 0;
         __syncthreads();
@@ -1306,9 +1328,11 @@ constexpr int kWpsPrefetch = 4;  // fragments per thread held in registers for t
 // `if (p.nt_store) nt-store else store` the two branches differ only in the !nontemporal metadata, and the optimiser
 // may sink them into ONE plain store (it did once this body became a device function: WPS 175 -> 197 us per launch,
 // the feature pass behind it 37 -> 53 us).
-// PACKED: the tile reads start and the packed (length, mapq) word of its candidates (ContigView::lq, 6 B per fragment
-// instead of 9); the word travels in the register that holds `end` otherwise and is unpacked where the fragment is
-// applied.  Single-contig, unfused tiles, one per block, only (the launches launch_wps and launch_feat_t make with it).
+// PACKED: the tile reads the start deltas and the packed (length, mapq) words of its candidates (ContigView::ds, gbase,
+// lq: 3 B per fragment instead of 9) in the registers that hold start, mapq and end otherwise; starts are rebuilt where the
+// fragment is applied, by a scan over the wave, whose 64 lanes hold one group (unpack below); a group with a delta above
+// 255 reads the wide starts.  Single-contig, unfused tiles, one per block, only (the launches launch_wps and
+// launch_feat_t make with it).
 template <bool MULTI, bool BATCH, bool FUSED, bool PACKED, bool NT>
 __device__ __forceinline__ void wps_block(const unsigned block_id, const unsigned n_blocks, ContigView cv, WpsParams p,
                                           const int64_t* iv_start_, const int64_t* iv_stop_, const int64_t* out_off_,
@@ -1397,20 +1421,28 @@ __device__ __forceinline__ void wps_block(const unsigned block_id, const unsigne
         if (e < 0) atomicAdd(&pre_s[par], 1); else if (e < T) atomicAdd(&d[e], 1);
     };
 
-    // fragment i's registers: start; end - PACKED: its lq word; mapq - PACKED: unused (ok = false: an empty slot)
+    // fragment i's registers: start - PACKED: its start delta; end - PACKED: its lq word; mapq - PACKED: its group's
+    // base (ok = false: an empty slot)
     auto fetch = [&](int i, bool ok, int& fs, int& fe, int& q) {
-        fs = ok ? cv.start[i] : 0;
         if (PACKED) {
+            fs = ok ? (int)cv.ds[i] : 0;
             fe = ok ? (int)cv.lq[i] : 0;
-            q = 0;
+            q = ok ? cv.gbase[i / kDsGroup] : 0;
         } else {
+            fs = ok ? cv.start[i] : 0;
             fe = ok ? cv.end[i] : 0;
             q = ok ? (int)cv.mapq[i] : -1;
         }
     };
-    // PACKED: end and (saturated) mapq from the word
-    auto unpack = [&](int fs, int& fe, int& q) {
+    // PACKED: start from the scan of the wave's deltas and the base (EVERY lane of the wave comes here: the range begins
+    // on a group and the lanes stride it by 256, so the wave's lanes hold one group in order; the empty slots are its
+    // upper lanes and add nothing below them) or, in a group whose base carries kGbaseWide, from the wide column; end and
+    // (saturated) mapq from the word
+    auto unpack = [&](int i, bool ok, int& fs, int& fe, int& q) {
         if (PACKED) {
+            const int gb = q;
+            fs = gb + wave_incl_scan_dpp(fs);
+            if (ok && gb < 0) fs = cv.start[i];
             q = fe & kLqMapqSat;
             fe = fs + (fe >> kLqBits);
         }
@@ -1491,6 +1523,9 @@ __device__ __forceinline__ void wps_block(const unsigned block_id, const unsigne
     __syncthreads();
     int lo = rng_s[0], hi = rng_s[1];
     int pfs[PF], pfe[PF], pfq[PF];
+    // PACKED: the range begins on a group of the delta columns (the surplus candidates in front clip to nothing like the
+    // index's own), so that the 64 lanes of a wave hold one group in every slot: group r of the range goes to wave r % 4
+    if (PACKED && hi > lo) lo &= ~(kDsGroup - 1);
 #pragma unroll
     for (int k = 0; k < PF; ++k) {
         const int i = lo + tid + 256 * k;
@@ -1508,22 +1543,38 @@ __device__ __forceinline__ void wps_block(const unsigned block_id, const unsigne
             if (tid < 2) nb = cand_bound(nxt, tid);
         }
         // ---- events -----------------------------------------------------------------
+        if constexpr (PACKED) {  // whole waves walk the slots (unpack scans over the wave); block-uniform bounds
 #pragma unroll
-        for (int k = 0; k < PF; ++k) {
-            const int i = lo + tid + 256 * k;
-            if (i < hi) {
-                int fe = pfe[k], q = pfq[k];
-                unpack(pfs[k], fe, q);
-                apply(cur, par, i, pfs[k], fe, q);
-                if (FUSED) feature(cur.t0, cur.len_t, i, pfs[k], fe, q);
+            for (int k = 0; k < PF; ++k) {
+                const int i = lo + tid + 256 * k;
+                if (i - tid < hi) {
+                    int fs = pfs[k], fe = pfe[k], q = pfq[k];
+                    unpack(i, i < hi, fs, fe, q);
+                    if (i < hi) apply(cur, par, i, fs, fe, q);
+                }
             }
-        }
-        for (int i = lo + PF * 256 + tid; i < hi; i += 256) {
-            int fs, fe, q;
-            fetch(i, true, fs, fe, q);
-            unpack(fs, fe, q);
-            apply(cur, par, i, fs, fe, q);
-            if (FUSED) feature(cur.t0, cur.len_t, i, fs, fe, q);
+            for (int c = lo + PF * 256; c < hi; c += 256) {
+                const int i = c + tid;
+                int fs, fe, q;
+                fetch(i, i < hi, fs, fe, q);
+                unpack(i, i < hi, fs, fe, q);
+                if (i < hi) apply(cur, par, i, fs, fe, q);
+            }
+        } else {
+#pragma unroll
+            for (int k = 0; k < PF; ++k) {
+                const int i = lo + tid + 256 * k;
+                if (i < hi) {
+                    apply(cur, par, i, pfs[k], pfe[k], pfq[k]);
+                    if (FUSED) feature(cur.t0, cur.len_t, i, pfs[k], pfe[k], pfq[k]);
+                }
+            }
+            for (int i = lo + PF * 256 + tid; i < hi; i += 256) {
+                int fs, fe, q;
+                fetch(i, true, fs, fe, q);
+                apply(cur, par, i, fs, fe, q);
+                if (FUSED) feature(cur.t0, cur.len_t, i, fs, fe, q);
+            }
         }
         if (FUSED) {  // counters of the tile's first bin: one LDS atomic per wave and counter
             const int a0 = wave_reduce_add(f_cov), a1 = wave_reduce_add(f_sh), a2 = wave_reduce_add(f_lg),
@@ -2054,11 +2105,12 @@ void launch_window_stats(hipStream_t s, const uint32_t* hist, int n_win, int n_b
     hipLaunchKernelGGL(window_stats_kernel, dim3((n_win + 3) / 4), dim3(256), 0, s, hist, n_win, n_bins, len_lo, short_cut, out);
 }
 
-void launch_stats(hipStream_t s, const int32_t* start, const int32_t* end, const uint8_t* mapq, uint16_t* lq, int n,
-                  int n_pad, FragStats* st) {
+void launch_stats(hipStream_t s, const int32_t* start, const int32_t* end, const uint8_t* mapq, uint16_t* lq, uint8_t* ds,
+                  int32_t* gbase, int n, int n_pad, FragStats* st) {
     if (!lq) n_pad = n;
-    int blocks = min(1024, max(1, (n_pad + kStatsThreads - 1) / kStatsThreads));
-    hipLaunchKernelGGL(stats_kernel, dim3(blocks), dim3(kStatsThreads), 0, s, start, end, mapq, lq, n, n_pad, st);
+    const int n_all = lq ? (n_pad / kDsGroup + 1) * kDsGroup : n;  // the delta columns' whole groups
+    int blocks = min(1024, max(1, (n_all + kStatsThreads - 1) / kStatsThreads));
+    hipLaunchKernelGGL(stats_kernel, dim3(blocks), dim3(kStatsThreads), 0, s, start, end, mapq, lq, ds, gbase, n, n_pad, n_all, st);
 }
 
 void launch_bin_index(hipStream_t s, const int32_t* start, int n, int n_bins, int32_t* idx) {

@@ -1,5 +1,6 @@
-// The packed (length, mapq) word of a fragment and the rule that decides which calls may read it (host code, plain
-// C++: tools/check_packed_rule.cpp exercises it without a GPU).
+// The packed (length, mapq) word of a fragment, the start column as 1-byte deltas, and the rule that decides which calls
+// may read them (host code, plain C++: tools/check_packed_rule.cpp and tools/check_delta_columns.cpp exercise it without
+// a GPU).
 #pragma once
 
 #include <stdint.h>
@@ -16,6 +17,44 @@ constexpr int kLqBits = 5;
 constexpr int kLqMapqSat = (1 << kLqBits) - 1;        // 31: saturated mapq
 constexpr int kLqLenSat = (1 << (16 - kLqBits)) - 1;  // 2047: saturated length
 constexpr int kLqLenMax = kLqLenSat - 1;              // 2046: longest fragment of a contig that keeps the column
+
+// The start column as 1-byte deltas (ContigView::ds, ContigView::gbase), read by the same kernels INSTEAD of the 4-byte
+// starts.  Fragments are sorted by start, so inside a group of kDsGroup = 64 consecutive fragments
+//   ds[i]    = (uint8_t)(start[i] - start[i - 1]), and 0 for a group's first fragment (i % 64 == 0);
+//   gbase[g] = start[64 g], with bit 31 (kGbaseWide; coordinates are below 2^30) set when a delta INSIDE the group
+//              exceeds 255.  The gap in front of a group's first fragment is no delta of the group.
+//   start[i] = gbase[g] + ds[64 g + 1] + ... + ds[i] in a group without the bit; a group with it is read from the
+//              wide column, which stays resident.
+// Both columns cover whole groups: the fragments behind the contig's last one sit at kDsPadCoord like the padding of the
+// wide columns (so the group that holds fragment n, when n is no multiple of 64, carries the bit).
+constexpr int kDsGroup = 64;
+constexpr uint32_t kGbaseWide = 0x80000000u;
+constexpr int32_t kDsPadCoord = 1 << 30;
+
+// the two columns of start[0, n) over n_groups groups (n_groups * 64 >= n)
+inline void ds_encode(const int32_t* start, long long n, long long n_groups, uint8_t* ds, int32_t* gbase) {
+    for (long long g = 0; g < n_groups; ++g) {
+        bool wide = false;
+        for (long long i = g * kDsGroup; i < (g + 1) * kDsGroup; ++i) {
+            const int32_t s = i < n ? start[i] : kDsPadCoord, prev = i == 0 ? s : i - 1 < n ? start[i - 1] : kDsPadCoord;
+            const uint32_t d = i % kDsGroup ? (uint32_t)s - (uint32_t)prev : 0u;
+            ds[i] = (uint8_t)d;
+            wide |= d > 255u;
+            if (i % kDsGroup == 0) gbase[g] = s;
+        }
+        if (wide) gbase[g] = (int32_t)((uint32_t)gbase[g] | kGbaseWide);
+    }
+}
+
+// start[i] as the kernels rebuild it (the device form: an in-lane prefix over four deltas, a scan over the 16 lanes of a
+// group, the group's base)
+inline int32_t ds_decode(const int32_t* start, const uint8_t* ds, const int32_t* gbase, long long i) {
+    const long long g = i / kDsGroup;
+    if ((uint32_t)gbase[g] & kGbaseWide) return start[i];
+    int32_t s = gbase[g];
+    for (long long k = g * kDsGroup + 1; k <= i; ++k) s += ds[k];
+    return s;
+}
 
 // Every comparison one call makes with a fragment's mapq or length.  A part that does not run has run = false.
 struct PackedCall {
