@@ -1454,9 +1454,11 @@ static int wps_params(ftk_ctx* ctx, const ContigData& c, int64_t chrom_size, int
         p->hl = window_size / 2;
         p->hr = window_size / 2 - 1;
     }
-    p->min_len = min_len < 0 ? 0 : min_len;
+    // The tile's sign tests subtract these from a length below 2^30 and a mapq below 256 in int (ftk_wps_events.h):
+    // clamped to where every comparison keeps its answer and no difference overflows.
+    p->min_len = std::clamp(min_len, 0, 1 << 30);
     p->max_len = max_len;
-    p->mapq_min = mapq_min;
+    p->mapq_min = std::clamp(mapq_min, 0, 256);
     p->lmax = std::max(0, std::min(max_len, c.max_len));
     // Scores are written once and not re-read by this library: non-temporal stores keep them from
     // displacing the fragment columns in the Infinity Cache and from leaving 256 MB of dirty lines for

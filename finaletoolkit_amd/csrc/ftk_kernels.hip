@@ -13,6 +13,7 @@
 //     16-byte stores, 1 KB contiguous per store instruction.
 #include "ftk_device.h"
 #include "ftk_kernels.h"
+#include "ftk_wps_events.h"
 
 #include <cstdlib>
 
@@ -1311,6 +1312,7 @@ struct WpsTile {
     long long fmin, fmax;  // fetch window of the owning interval (frag/_wps.py:156-157)
     long long out_base;  // index of t0's score in the output
     int len_t;           // bases in the tile (<= kWpsTile)
+    WpsEvTile ev;        // the same in int, for the events (ftk_wps_events.h)
 };
 
 constexpr int kWpsPrefetch = 4;  // fragments per thread held in registers for the next tile
@@ -1368,6 +1370,9 @@ __device__ __forceinline__ void wps_block(const unsigned block_id, const unsigne
         b_start = I.start; b_stop = I.stop; b_off = I.out_off; b_tile0 = I.tile_base;
     }
 
+    // BAM: the overlap test of the fetch reads the read1 columns.  A PACKED contig never has them: compiled out.
+    bool read1 = false;
+    if constexpr (!PACKED) read1 = cv.r1_start != nullptr;
     auto tile_info = [&](long long t) {
         WpsTile ti;
         long long iv_start, iv_stop, out_off, k;
@@ -1384,6 +1389,11 @@ __device__ __forceinline__ void wps_block(const unsigned block_id, const unsigne
         ti.fmin = max(iv_start - (long long)p.max_len, 0LL);
         ti.fmax = min(iv_stop + (long long)p.max_len, p.chrom_size);
         ti.out_base = out_off + k * T;
+        ti.ev.t0 = (int)ti.t0;  // exact in every tile that has candidates (ftk_wps_events.h, "ranges")
+        ti.ev.len_t = ti.len_t;
+        ti.ev.fmin = wps_clamp_coord(ti.fmin);
+        ti.ev.fmax = wps_clamp_coord(ti.fmax);
+        ti.ev.edge = wps_tile_is_edge(ti.t0, ti.len_t, ti.fmin, ti.fmax, hl, hr, p.lmax, read1 && !cv.r1_inside);
         return ti;
     };
     // Candidate fragments: fs - hr <= t1 - 1 and fe + hl >= t0 - 1, i.e.
@@ -1393,32 +1403,23 @@ __device__ __forceinline__ void wps_block(const unsigned block_id, const unsigne
         const long long q = which == 0 ? ti.t0 - 1 - hl - (long long)p.lmax : ti.t0 + ti.len_t + hr;
         return index_bound(cv, q, which);
     };
-    // one fragment -> its +-1/+-2 events in the tile's difference array
-    auto apply = [&](const WpsTile& ti, int par, int i, int fs, int fe, int q) {
-        const int len = fe - fs;
-        const long long mid = ((long long)fs + (long long)fe) >> 1;
-        if (q < p.mapq_min || len < p.min_len || len > p.max_len || mid < ti.fmin || mid >= ti.fmax) return;
-        if (cv.r1_start) {
+    // one fragment -> its +-1/+-2 events in the tile's difference array: 32-bit tile-relative cells, one OR-ed sign
+    // test for every rejection, the fetch-window tests only in an edge tile (block-uniform), each step one select of its
+    // LDS address (a step left of the tile goes to the carry cell pre_s[par]) - ftk_wps_events.h states it, with the
+    // ranges that keep it inside int.  Every instantiation takes this form: the bounds hold for the wide columns too.
+    const WpsEvCall K{hl, hr, p.min_len, p.max_len, p.mapq_min};
+    auto apply = [&](const WpsTile& ti, int par, int i, int fs, int len, int q) {
+        const WpsEv v = wps_events(K, ti.ev.t0, fs, len);
+        if (wps_accept(K, ti.ev, fs, len, q, v, read1) < 0) return;
+        if constexpr (!PACKED) {
             // BAM: the fetch returns read1 alignments overlapping [fmin, fmax).  A fragment inside the fetch window
             // holds its read1 there (ContigView::r1_inside): the read1 columns are read for the fragments that
-            // cross its bounds - none at all in a whole-contig call.
-            if (!cv.r1_inside || (long long)fs < ti.fmin || (long long)fe > ti.fmax) {
+            // cross its bounds - none at all in an interior tile.
+            if (read1 && wps_read1_decides(ti.ev, fs, len, cv.r1_inside)) {
                 if (!((long long)cv.r1_start[i] < ti.fmax && (long long)cv.r1_end[i] > ti.fmin)) return;
             }
-        } else if (!((long long)fs < ti.fmax && (long long)fe > ti.fmin)) {
-            return;
         }
-        const long long a = (long long)fs - hr - ti.t0;
-        const long long b = (long long)fs + hl + 1 - ti.t0;
-        const long long c = (long long)fe - hr - ti.t0;
-        const long long e = (long long)fe + hl + 1 - ti.t0;
-        if (e <= -1 || a >= ti.len_t) return;  // no effect on [t0 - 1, t1)
-        if (a < 0) atomicAdd(&pre_s[par], -1); else if (a < T) atomicAdd(&d[a], -1);
-        if (c >= b) {  // start / stop ranges disjoint: spanning range in between
-            if (b < 0) atomicAdd(&pre_s[par], 2); else if (b < T) atomicAdd(&d[b], 2);
-            if (c < 0) atomicAdd(&pre_s[par], -2); else if (c < T) atomicAdd(&d[c], -2);
-        }
-        if (e < 0) atomicAdd(&pre_s[par], 1); else if (e < T) atomicAdd(&d[e], 1);
+        wps_emit<T>(v, [&](int cell, int val) { atomicAdd(cell < 0 ? &pre_s[par] : &d[cell], val); });
     };
 
     // fragment i's registers: start - PACKED: its start delta; end - PACKED: its lq word; mapq - PACKED: its group's
@@ -1436,15 +1437,15 @@ __device__ __forceinline__ void wps_block(const unsigned block_id, const unsigne
     };
     // PACKED: start from the scan of the wave's deltas and the base (EVERY lane of the wave comes here: the range begins
     // on a group and the lanes stride it by 256, so the wave's lanes hold one group in order; the empty slots are its
-    // upper lanes and add nothing below them) or, in a group whose base carries kGbaseWide, from the wide column; end and
-    // (saturated) mapq from the word
-    auto unpack = [&](int i, bool ok, int& fs, int& fe, int& q) {
+    // upper lanes and add nothing below them) or, in a group whose base carries kGbaseWide, from the wide column; length
+    // and (saturated) mapq from the word
+    auto unpack = [&](int i, bool ok, int& fs, int& len, int& q) {
         if (PACKED) {
             const int gb = q;
             fs = gb + wave_incl_scan_dpp(fs);
             if (ok && gb < 0) fs = cv.start[i];
-            q = fe & kLqMapqSat;
-            fe = fs + (fe >> kLqBits);
+            q = len & kLqMapqSat;
+            len = len >> kLqBits;
         }
     };
 
@@ -1548,31 +1549,31 @@ __device__ __forceinline__ void wps_block(const unsigned block_id, const unsigne
             for (int k = 0; k < PF; ++k) {
                 const int i = lo + tid + 256 * k;
                 if (i - tid < hi) {
-                    int fs = pfs[k], fe = pfe[k], q = pfq[k];
-                    unpack(i, i < hi, fs, fe, q);
-                    if (i < hi) apply(cur, par, i, fs, fe, q);
+                    int fs = pfs[k], len = pfe[k], q = pfq[k];
+                    unpack(i, i < hi, fs, len, q);
+                    if (i < hi) apply(cur, par, i, fs, len, q);
                 }
             }
             for (int c = lo + PF * 256; c < hi; c += 256) {
                 const int i = c + tid;
-                int fs, fe, q;
-                fetch(i, i < hi, fs, fe, q);
-                unpack(i, i < hi, fs, fe, q);
-                if (i < hi) apply(cur, par, i, fs, fe, q);
+                int fs, len, q;
+                fetch(i, i < hi, fs, len, q);
+                unpack(i, i < hi, fs, len, q);
+                if (i < hi) apply(cur, par, i, fs, len, q);
             }
         } else {
 #pragma unroll
             for (int k = 0; k < PF; ++k) {
                 const int i = lo + tid + 256 * k;
                 if (i < hi) {
-                    apply(cur, par, i, pfs[k], pfe[k], pfq[k]);
+                    apply(cur, par, i, pfs[k], pfe[k] - pfs[k], pfq[k]);
                     if (FUSED) feature(cur.t0, cur.len_t, i, pfs[k], pfe[k], pfq[k]);
                 }
             }
             for (int i = lo + PF * 256 + tid; i < hi; i += 256) {
                 int fs, fe, q;
                 fetch(i, true, fs, fe, q);
-                apply(cur, par, i, fs, fe, q);
+                apply(cur, par, i, fs, fe - fs, q);
                 if (FUSED) feature(cur.t0, cur.len_t, i, fs, fe, q);
             }
         }
@@ -1596,7 +1597,7 @@ __device__ __forceinline__ void wps_block(const unsigned block_id, const unsigne
             if (tid == 2 && F.do_delfi && fcnt[3] - fcnt[1]) atomicAdd(reinterpret_cast<ull*>(F.short_out + f_w0), (ull)(fcnt[3] - fcnt[1]));
             if (tid == 3 && F.do_delfi && fcnt[3] - fcnt[2]) atomicAdd(reinterpret_cast<ull*>(F.long_out + f_w0), (ull)(fcnt[3] - fcnt[2]));
         }
-        // ---- read the difference array (and clear it for the next tile), scan ---------
+        // ---- read the difference array (MULTI: and clear it for the next tile), scan ---
         int2 va[NP], vb[NP];
         int exa[NP], exb[NP];
         {
@@ -1607,8 +1608,10 @@ __device__ __forceinline__ void wps_block(const unsigned block_id, const unsigne
                 const int ia = j * 512 + wv * 128 + lane;  // int2 index of bases sb + 2l, sb + 2l + 1
                 va[j] = d2[ia];
                 vb[j] = d2[ia + 64];
-                d2[ia] = z;
-                d2[ia + 64] = z;
+                if constexpr (MULTI) {
+                    d2[ia] = z;
+                    d2[ia + 64] = z;
+                }
                 const int sa = va[j].x + va[j].y, sb2 = vb[j].x + vb[j].y;
                 const int ia_incl = wave_incl_scan_dpp(sa);
                 const int ib_incl = wave_incl_scan_dpp(sb2);
@@ -1619,18 +1622,22 @@ __device__ __forceinline__ void wps_block(const unsigned block_id, const unsigne
                 if (lane == 0) wtot[j][wv] = tot_a + tot_b;
             }
         }
-        if (tid < 2) rng_s[tid] = nb;
-        if (tid == 2) pre_s[par ^ 1] = 0;
-        __syncthreads();
-        // ---- prefetch the next tile's fragments (in flight behind the stores below) ---
+        if constexpr (MULTI) {  // one tile per block hands nothing on
+            if (tid < 2) rng_s[tid] = nb;
+            if (tid == 2) pre_s[par ^ 1] = 0;
+        }
+        __syncthreads();  // the cross-wave carries (wtot)
         int base = pre_s[par];
+        // ---- MULTI: prefetch the next tile's fragments (in flight behind the stores below) ---
         int lo2 = lo, hi2 = lo;
         int nfs[PF], nfe[PF], nfq[PF];
-        if (has_next) { lo2 = rng_s[0]; hi2 = rng_s[1]; }
+        if constexpr (MULTI) {
+            if (has_next) { lo2 = rng_s[0]; hi2 = rng_s[1]; }
 #pragma unroll
-        for (int k = 0; k < PF; ++k) {
-            const int i = lo2 + tid + 256 * k;
-            fetch(i, MULTI && i < hi2, nfs[k], nfe[k], nfq[k]);
+            for (int k = 0; k < PF; ++k) {
+                const int i = lo2 + tid + 256 * k;
+                fetch(i, i < hi2, nfs[k], nfe[k], nfq[k]);
+            }
         }
         // ---- scores -------------------------------------------------------------------
         int64_t* dst = out + cur.out_base;
@@ -1669,16 +1676,20 @@ __device__ __forceinline__ void wps_block(const unsigned block_id, const unsigne
                 }
             }
         }
-        cur = nxt;
-        lo = lo2;
-        hi = hi2;
+        if constexpr (MULTI) {
+            cur = nxt;
+            lo = lo2;
+            hi = hi2;
 #pragma unroll
-        for (int k = 0; k < PF; ++k) { pfs[k] = nfs[k]; pfe[k] = nfe[k]; pfq[k] = nfq[k]; }
+            for (int k = 0; k < PF; ++k) { pfs[k] = nfs[k]; pfe[k] = nfe[k]; pfq[k] = nfq[k]; }
+        } else {
+            break;  // one tile per block, and the compiler must know: the candidate registers die with the events
+        }
     }
 }
 
 template <bool MULTI, bool BATCH, bool FUSED, bool PACKED, bool NT>
-__global__ __launch_bounds__(256) void wps_stream_kernel(ContigView cv, WpsParams p, const int64_t* iv_start_,
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5, 5))) void wps_stream_kernel(ContigView cv, WpsParams p, const int64_t* iv_start_,
                                                          const int64_t* iv_stop_, const int64_t* out_off_,
                                                          const int32_t* tile_iv, const int32_t* tile_k,
                                                          long long n_tiles, int tiles_per_block,
