@@ -12,6 +12,7 @@
 //     with ds_add, scan it on DPP and stream the scores out with non-temporal
 //     16-byte stores, 1 KB contiguous per store instruction.
 #include "ftk_device.h"
+#include "ftk_feat_interior.h"
 #include "ftk_kernels.h"
 #include "ftk_wps_events.h"
 
@@ -1138,16 +1139,21 @@ struct FastSlab<true> {
     }
 };
 
-template <int kFeatBS, bool CHK, bool HIST, bool DF, bool BL, bool GAPS, bool BAM, bool PACKED>
+// EDGE: the range is [lo, cut) and [cut + skip, hi + skip) - a window's candidates without its interior (FeatInterior,
+// ftk_feat_interior.h) - walked as one: position i >= cut stands for fragment i + skip.  lo, cut and skip are multiples
+// of kDsGroup, so a row of 16 lanes still holds one group.
+template <int kFeatBS, bool CHK, bool HIST, bool DF, bool BL, bool GAPS, bool BAM, bool PACKED, bool EDGE = false>
 __device__ __forceinline__ void fast_stream(const ContigView& cv, const FeatParams& P, int lo, int hi, int tid,
-                                            const FastWin& W, int o0, int o1, uint32_t* h, FastAcc& a) {
+                                            const FastWin& W, int o0, int o1, uint32_t* h, FastAcc& a, int cut = 0,
+                                            int skip = 0) {
     static_assert(!(PACKED && BAM), "a contig with read1 columns has no packed column");
     FastSlab<PACKED> slab[4];
     const int i0 = lo + 4 * tid;
+    auto at = [&](int i) { return EDGE && i >= cut ? i + skip : i; };
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
         const int i = i0 + u * (4 * kFeatBS);
-        if (i < hi) slab[u].load(cv, i);
+        if (i < hi) slab[u].load(cv, at(i));
     }
     for (int base = i0; base < hi; base += 16 * kFeatBS) {
 #pragma unroll
@@ -1156,19 +1162,73 @@ __device__ __forceinline__ void fast_stream(const ContigView& cv, const FeatPara
             if (i < hi) {
                 int4 s, e;
                 uchar4 q;
-                slab[u].get(cv, i, s, e, q);
+                slab[u].get(cv, at(i), s, e, q);
                 const int nxt = i + 16 * kFeatBS;
-                if (nxt < hi) slab[u].load(cv, nxt);
-                fast_group<CHK, HIST, DF, BL, GAPS, BAM>(cv, P, i, s, e, q, W, o0, o1, h, a);
+                if (nxt < hi) slab[u].load(cv, at(nxt));
+                fast_group<CHK, HIST, DF, BL, GAPS, BAM>(cv, P, at(i), s, e, q, W, o0, o1, h, a);
             }
         }
     }
 }
 
-template <int kFeatBS, bool CHK, bool HIST, bool DF, bool BAM, bool PACKED = false>
+// The interior of a window's candidate range (FeatInterior): every fragment of [i0, i1) passes the window test, so its
+// packed word alone gives the mapq test and the histogram bin (feat_interior_bin) - no start, no delta scan.  A lane owns
+// four consecutive fragments per 8-byte load and issues all kInteriorDepth loads of a round before it uses the first: a
+// 100 kb window at 30x is about ten of them per lane of a 256-thread block, one round.  The loads of a lane that runs out
+// of fragments are aimed at the interior's last four (always inside it) and not used, so that no load waits on a branch.
+// The WPS tiles behind the feature blocks find the contig's columns in the Infinity Cache because the feature blocks have
+// just read them; a tile that has to fetch its candidates from HBM while 6 TB/s of scores are on their way there waits
+// far longer (measured: feature blocks that read nothing cost the step 0.53 ms, docs/experiments.md).  So the interior,
+// which needs neither the deltas nor the group bases, still TOUCHES them: a load that writes LDS directly, to a dump
+// cell nobody reads, costs no register and no VALU.
+__device__ __forceinline__ void touch_dword(const void* p, uint32_t* wave_cells) {
+    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) uint32_t*)p,
+                                     (__attribute__((address_space(3))) uint32_t*)wave_cells, 4, 0, 0);
+}
+
+constexpr int kInteriorDepth = 12;
+static_assert(kFeatIndexShift == kBinShift, "the interior rule reads the position index");
+
+template <int kFeatBS>
+__device__ __forceinline__ void interior_stream(const ContigView& cv, const FeatParams& P, int i0, int i1, int tid,
+                                                uint32_t* h) {
+    constexpr int D = kInteriorDepth, R = 4 * kFeatBS;
+    __shared__ uint32_t dump[kFeatBS];  // where the touched dwords land: 64 cells per wave, never read
+    uint32_t* const cell = dump + (tid & ~63);
+    for (int base = i0 + 4 * tid; base < i1; base += D * R) {
+        uint2 l[D];
+#pragma unroll
+        for (int u = 0; u < D; ++u) l[u] = *reinterpret_cast<const uint2*>(cv.lq + min(base + u * R, i1 - 4));
+#pragma unroll
+        for (int u = 0; u < D; ++u) {
+            const int i = min(base + u * R, i1 - 4);
+            touch_dword(cv.ds + i, cell);
+            touch_dword(cv.gbase + i / kDsGroup, cell);
+        }
+#pragma unroll
+        for (int u = 0; u < D; ++u) {
+            if (base + u * R < i1) {
+                const unsigned w[4] = {l[u].x & 0xffffu, l[u].x >> 16, l[u].y & 0xffffu, l[u].y >> 16};
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    unsigned add;
+                    const unsigned b = feat_interior_bin(w[j], P.ch_q, P.len_lo, P.n_bins, add);
+                    atomicAdd(&h[b], add);
+                }
+            }
+        }
+    }
+}
+
+// CFH (the launch passes feat_counts_from_hist, ftk_feat_interior.h): a window without blacklist entries and out of reach
+// of the gap intervals takes its coverage and DELFI counts from its length histogram; only the histogram is built, by the
+// window test for the edge of the candidate range and from the packed word alone for its interior.  Every other window
+// of the launch keeps the per-fragment counters (a block-uniform choice, like `bl` and `gaps`).
+template <int kFeatBS, bool CHK, bool HIST, bool DF, bool BAM, bool PACKED = false, bool CFH = false>
 __device__ __forceinline__ void feat_fast_body(const ContigView& cv, int ws_raw, int we_raw, int lmax,
                                                const FeatParams& P, int o0, int o1, size_t row, uint32_t* lds_hist,
                                                int (*red)[kFeatBS / 64]) {
+    static_assert(!CFH || (CHK && HIST && PACKED && !BAM), "counts from the histogram: a packed launch that builds one");
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     int lo, hi;
     uint32_t nc;
@@ -1200,7 +1260,14 @@ __device__ __forceinline__ void feat_fast_body(const ContigView& cv, int ws_raw,
     }
     FastAcc a;
     const bool bl = DF && o1 > o0;
-    if (bl) {
+    const bool from_hist = CFH && !bl && !gaps;
+    if (CFH && from_hist) {
+        const FeatInterior in = feat_interior(cv.bin_idx, cv.n_bins, cv.n, ws_raw, we_raw, max(lmax, cv.max_len), lo, hi);
+        FastAcc none;  // the edge adds to the histogram only
+        fast_stream<kFeatBS, true, true, false, false, false, false, true, true>(cv, P, lo, hi - (in.i1 - in.i0), tid, W, o0, o1,
+                                                                                 lds_hist, none, in.i0, in.i1 - in.i0);
+        interior_stream<kFeatBS>(cv, P, in.i0, in.i1, tid, lds_hist);
+    } else if (bl) {
         if (gaps) fast_stream<kFeatBS, CHK, HIST, DF, true, true, BAM, PACKED>(cv, P, lo, hi, tid, W, o0, o1, lds_hist, a);
         else fast_stream<kFeatBS, CHK, HIST, DF, true, false, BAM, PACKED>(cv, P, lo, hi, tid, W, o0, o1, lds_hist, a);
     } else {
@@ -1210,7 +1277,18 @@ __device__ __forceinline__ void feat_fast_body(const ContigView& cv, int ws_raw,
     if (HIST) {
         __syncthreads();
         uint32_t* dst = P.hist_out + row * P.n_bins;
-        for (int b = tid; b < P.n_bins; b += kFeatBS) dst[b] = lds_hist[b];
+        if (CFH && from_hist) {
+            // PASSING fragments here, not rejected ones: all bins, the short bins, the long bins (feat_counts_add)
+            unsigned cov = tid == 0 ? lds_hist[P.n_bins] : 0u, sh = 0, lg = 0;
+            for (int b = tid; b < P.n_bins; b += kFeatBS) {
+                const uint32_t v = lds_hist[b];
+                dst[b] = v;
+                feat_counts_add(P.len_lo, b, v, cov, sh, lg);
+            }
+            a.cov = (int)cov; a.rej = (int)sh; a.lg = (int)lg;
+        } else {
+            for (int b = tid; b < P.n_bins; b += kFeatBS) dst[b] = lds_hist[b];
+        }
     }
     a.cov = wave_reduce_add(a.cov);
     a.rej = wave_reduce_add(a.rej);
@@ -1222,14 +1300,19 @@ __device__ __forceinline__ void feat_fast_body(const ContigView& cv, int ws_raw,
         int cov = 0, rej = 0, lg = 0;
 #pragma unroll
         for (int k = 0; k < kFeatBS / 64; ++k) { cov += red[0][k]; rej += red[1][k]; lg += red[2][k]; }
-        if (tid == 0 && CHK && P.do_cov) P.cov_out[row] = n - cov;
+        if (CFH && from_hist) {
+            if (tid == 0 && P.do_cov) P.cov_out[row] = cov;
+            if (tid == 2 && DF) P.short_out[row] = rej;
+        } else {
+            if (tid == 0 && CHK && P.do_cov) P.cov_out[row] = n - cov;
+            if (tid == 2 && DF) P.short_out[row] = n - rej - lg;
+        }
         if (tid == 1 && HIST) P.over_out[row] = (int)lds_hist[P.n_bins];
-        if (tid == 2 && DF) P.short_out[row] = n - rej - lg;
         if (tid == 3 && DF) P.long_out[row] = lg;
     }
 }
 
-template <int kFeatBS, bool CHK, bool HIST, bool DF, bool BAM, bool PACKED>
+template <int kFeatBS, bool CHK, bool HIST, bool DF, bool BAM, bool PACKED, bool CFH>
 __global__ __launch_bounds__(kFeatBS) void feat_fast_kernel(ContigView cv, const int32_t* ws_, const int32_t* we_,
                                                         int n_win, int lmax, FeatParams P) {
     extern __shared__ uint32_t lds_hist[];
@@ -1237,7 +1320,7 @@ __global__ __launch_bounds__(kFeatBS) void feat_fast_kernel(ContigView cv, const
     const int w = blockIdx.x;
     int o0, o1;
     blacklist_range<DF>(P.dp.bl_off, w, o0, o1);
-    feat_fast_body<kFeatBS, CHK, HIST, DF, BAM, PACKED>(cv, ws_[w], we_[w], lmax, P, o0, o1, (size_t)w, lds_hist, red);
+    feat_fast_body<kFeatBS, CHK, HIST, DF, BAM, PACKED, CFH>(cv, ws_[w], we_[w], lmax, P, o0, o1, (size_t)w, lds_hist, red);
 }
 
 // The block kernels for the windows of SEVERAL contigs in one launch (ftk_window_features_batch): block b owns
@@ -1706,7 +1789,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5, 5))) voi
 // retire (the feature pass's tail and the WPS ramp overlap instead of adding up), and WPS finds the contig's
 // columns in the Infinity Cache behind the feature blocks that just read them.  The two kinds of block share
 // nothing: results are those of the two separate launches.
-template <bool CHK, bool HIST, bool DF, bool BAM, bool PACKED, bool NT>
+template <bool CHK, bool HIST, bool DF, bool BAM, bool PACKED, bool CFH, bool NT>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5, 5))) void feat_then_wps_kernel(ContigView cv, const int32_t* ws_, const int32_t* we_,
                                                             int n_win, int lmax, FeatParams P, WpsParams p,
                                                             long long n_tiles, int64_t* __restrict__ out) {
@@ -1716,7 +1799,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5, 5))) voi
         const int w = blockIdx.x;
         int o0, o1;
         blacklist_range<DF>(P.dp.bl_off, w, o0, o1);
-        feat_fast_body<256, CHK, HIST, DF, BAM, PACKED>(cv, ws_[w], we_[w], lmax, P, o0, o1, (size_t)w, lds_hist, red);
+        feat_fast_body<256, CHK, HIST, DF, BAM, PACKED, CFH>(cv, ws_[w], we_[w], lmax, P, o0, o1, (size_t)w, lds_hist, red);
         return;
     }
     wps_block<false, false, false, PACKED, NT>(blockIdx.x - (unsigned)n_win, gridDim.x - (unsigned)n_win, cv, p, nullptr, nullptr,
@@ -2252,6 +2335,22 @@ static bool use_packed(const ContigView& cv, const FeatParams* P, bool hist, con
 // beside every launch of a PACKED instantiation: the debug counter behind packed_launches()
 static void count_packed_launch() { g_packed_launches.fetch_add(1, std::memory_order_relaxed); }
 
+// May the blocks of a FAST launch take coverage and the DELFI counts from the window's histogram (feat_counts_from_hist,
+// ftk_feat_interior.h)?  The caller has passed feat_fast_ok.  FTK_FEAT_INTERIOR=0 keeps the per-fragment counters in every
+// window (tests run both).
+static bool counts_from_hist(const FeatParams& P, bool hist, bool packed, bool bam) {
+    static const int allow = getenv("FTK_FEAT_INTERIOR") ? atoi(getenv("FTK_FEAT_INTERIOR")) : 1;
+    if (!allow) return false;
+    FeatCountsCall c;
+    c.hist = hist;
+    c.len_lo = P.len_lo;
+    c.n_bins = P.n_bins;
+    c.fast_ok = true;
+    c.packed = packed;
+    c.bam = bam;
+    return feat_counts_from_hist(c);
+}
+
 template <int CH, bool DF, bool BAM>
 static bool launch_feat_t(hipStream_t s, int grid_large, const ContigView& cv, const int32_t* ws, const int32_t* we,
                           int n_win, const WindowPlan& pl, const FeatParams& P, bool small_path, int block_lmax,
@@ -2263,27 +2362,29 @@ static bool launch_feat_t(hipStream_t s, int grid_large, const ContigView& cv, c
         if (tail && tail->n_tiles > 0 && (long long)n_win + tail->n_tiles < (1LL << 31)) {
             // the merged launch: feature blocks first, the WPS tiles behind them (feat_then_wps_kernel)
             const dim3 grid((unsigned)((long long)n_win + tail->n_tiles));
-            with_bools([&](auto HIST, auto PACKED, auto NT) {
-                if constexpr (!(BAM && PACKED())) {
-                    hipLaunchKernelGGL((feat_then_wps_kernel<CH != 0, HIST(), DF, BAM, PACKED(), NT()>), grid, dim3(256),
+            const bool packed = !BAM && use_packed(cv, &Pf, hist, &tail->p);
+            with_bools([&](auto HIST, auto PACKED, auto NT, auto CFH) {
+                if constexpr (!(BAM && PACKED()) && (!CFH() || (CH != 0 && HIST() && PACKED()))) {
+                    hipLaunchKernelGGL((feat_then_wps_kernel<CH != 0, HIST(), DF, BAM, PACKED(), CFH(), NT()>), grid, dim3(256),
                                        lds1, s, cv, ws, we, n_win, block_lmax, Pf, tail->p, (long long)tail->n_tiles,
                                        tail->out);
                     if constexpr (PACKED()) count_packed_launch();
                 }
-            }, hist, !BAM && use_packed(cv, &Pf, hist, &tail->p), tail->p.nt_store != 0);
+            }, hist, packed, tail->p.nt_store != 0, counts_from_hist(Pf, hist, packed, BAM));
             return true;
         }
-        with_bools([&](auto HIST, auto PACKED) {
-            if constexpr (!(BAM && PACKED())) {
+        const bool packed = !BAM && use_packed(cv, &Pf, hist, nullptr);
+        with_bools([&](auto HIST, auto PACKED, auto CFH) {
+            if constexpr (!(BAM && PACKED()) && (!CFH() || (CH != 0 && HIST() && PACKED()))) {
                 if (block_threads >= 512)
-                    hipLaunchKernelGGL((feat_fast_kernel<512, CH != 0, HIST(), DF, BAM, PACKED()>), dim3(n_win), dim3(512),
+                    hipLaunchKernelGGL((feat_fast_kernel<512, CH != 0, HIST(), DF, BAM, PACKED(), CFH()>), dim3(n_win), dim3(512),
                                        lds1, s, cv, ws, we, n_win, block_lmax, Pf);
                 else
-                    hipLaunchKernelGGL((feat_fast_kernel<256, CH != 0, HIST(), DF, BAM, PACKED()>), dim3(n_win), dim3(256),
+                    hipLaunchKernelGGL((feat_fast_kernel<256, CH != 0, HIST(), DF, BAM, PACKED(), CFH()>), dim3(n_win), dim3(256),
                                        lds1, s, cv, ws, we, n_win, block_lmax, Pf);
                 if constexpr (PACKED()) count_packed_launch();
             }
-        }, hist, !BAM && use_packed(cv, &Pf, hist, nullptr));
+        }, hist, packed, counts_from_hist(Pf, hist, packed, BAM));
         return false;
     }
     if (block_lmax >= 0) {
