@@ -55,7 +55,7 @@ _FLAT_BY_MODULE = {
               "frag_site_profile", "read_sites", "frag_vplot", "VPlot", "frag_wps_spectrum", "WpsSpectrum", "frag_ocf", "OCF",
               "frag_wps_peaks", "WpsPeaks", "frag_preferred_ends", "PreferredEnds", "preferred_end_thresholds",
               "frag_hotspots", "IfsHotspots", "ifs_thresholds", "frag_end_context", "EndContext",
-              "frag_cofragmentation", "CoFragmentation", "ks_neglog10_p"),
+              "frag_cofragmentation", "CoFragmentation", "ks_neglog10_p", "frag_motif_lengths", "MotifLengths"),
     "genome": ("GenomeGaps", "ContigGaps", "ucsc_hg19_gap_bed", "b37_gap_bed", "ucsc_hg38_gap_bed"),
     "io": ("Fragment", "AlignmentWrapper"),
 }

@@ -48,6 +48,8 @@ CONTEXT_MAX_CLASSES = 8  # FTK_CONTEXT_MAX_CLASSES
 CONTEXT_ANCHOR = {"ends": 0, "centre": 1}  # FTK_CONTEXT_ENDS, FTK_CONTEXT_CENTRE
 COFRAG_MAX_BINS = 4096  # FTK_COFRAG_MAX_BINS
 COFRAG_MAX_LEN_BINS = 4096  # FTK_COFRAG_MAX_LEN_BINS
+MOTIFLEN_MAX_K = 4  # FTK_MOTIFLEN_MAX_K
+MOTIFLEN_MAX_ROWS = 1024  # FTK_MOTIFLEN_MAX_ROWS
 HOTSPOTS_TILE = 4096  # kCallTile: windows per workgroup of the hotspot passes
 HOTSPOTS_BATCH_TILES = 4096  # kCallBatchTiles: tiles the call plans, counts and writes at a time
 SPECTRUM_TILE = 16 << 10  # kSpectrumLdsSamples: a run of up to this many samples is folded out of LDS, a longer one from memory
@@ -92,6 +94,7 @@ EXPORTS = [
     "ftk_ifs_hotspots", "ftk_ifs_track", "ftk_ifs_totals",
     "ftk_end_context", "ftk_ref_context", "ftk_end_context_lds_classes",
     "ftk_hist_ks", "ftk_cofrag", "ftk_hist_ks_shape",
+    "ftk_motif_length_table", "ftk_motif_length_lds_rows",
 ]
 
 
@@ -387,6 +390,8 @@ def load() -> C.CDLL:
     lib.ftk_hist_ks.argtypes = [vp, vp, i64, i32, vp, vp, vp]
     lib.ftk_cofrag.argtypes = [vp, C.c_int, vp, vp, i64, C.POINTER(Filter), i32, i32, vp, vp, vp, vp]
     lib.ftk_hist_ks_shape.argtypes = [C.POINTER(i32), C.POINTER(i32)]
+    lib.ftk_motif_length_table.argtypes = [vp, C.c_int, C.c_int, i32, i32, i32, i32, i32, i32, vp, vp]
+    lib.ftk_motif_length_lds_rows.argtypes = [i32]
     lib.ftk_comm_unique_id.argtypes = [C.c_char_p]
     lib.ftk_comm_create.argtypes = [vp, C.c_int, C.c_int, C.c_char_p, C.POINTER(vp)]
     lib.ftk_comm_size.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]

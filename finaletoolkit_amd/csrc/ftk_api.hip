@@ -1489,3 +1489,4 @@ static int wps_params(ftk_ctx* ctx, const ContigData& c, int64_t chrom_size, int
 #include "ftk_api_hotspots.inc"
 #include "ftk_api_endcontext.inc"
 #include "ftk_api_cofrag.inc"
+#include "ftk_api_motiflen.inc"

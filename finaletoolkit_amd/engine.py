@@ -857,6 +857,33 @@ class Engine:
         self._check(self.lib.ftk_ref_context(self.ctx, int(rid), int(pos_lo), int(pos_hi), L.ptr(out)))
         return out
 
+    # -- motif x length: end-motif counts per fragment length (csrc/ftk_motiflen.hip) ----
+    def motif_length_lds_rows(self, k: int) -> int:
+        """Length rows one workgroup of the motif x length kernel keeps in LDS at motif length ``k``
+        (``ftk_motif_length_lds_rows``; 0 for ``k`` outside 1 .. 4); a call with more rows walks them in bands of that many."""
+        return int(self.lib.ftk_motif_length_lds_rows(int(k)))
+
+    def motif_length_table(self, name: str, rid: int, k: int, shift: int, len_lo: int, len_hi: int, len_bin: int = 1,
+                           quality_threshold=30):
+        """``(table, n_kept)`` of resident contig ``name`` against reference image ``rid`` (``ftk_motif_length_table``; the
+        rule is in ``include/ftk.h``, "motif x length"): ``table[kind, r, code]`` = kept fragments (``mapq >=
+        quality_threshold``, ``len_lo <= L <= len_hi``) of length row ``r = (L - len_lo) // len_bin`` whose reading of ``kind``
+        (0: ``base(s + shift + i)``, the U end on the + strand; 1: ``comp(base(e - 1 - shift - i))``, the D end on the -
+        strand; ``i = 0 .. k-1``) has that code - first base most significant, ``A C G T`` = 0 .. 3, column ``4 ** k`` for a
+        reading with an N or off the contig - int64 of shape ``(2, n_rows, 4 ** k + 1)``; ``n_kept[r]``: the kept fragments
+        of row ``r``, int64.  Every row of either kind sums to ``n_kept[r]``."""
+        k, lo, hi, b = int(k), int(len_lo), int(len_hi), int(len_bin)
+        n_rows = (hi - lo) // b + 1 if b >= 1 and hi >= lo else 1
+        if not 1 <= n_rows <= L.MOTIFLEN_MAX_ROWS or not 1 <= k <= L.MOTIFLEN_MAX_K:
+            shape = (2, 1, 1)  # (the call refuses these arguments and writes nothing)
+        else:
+            shape = (2, n_rows, 4 ** k + 1)
+        table = np.empty(shape, np.int64)
+        n_kept = np.empty(shape[1], np.int64)
+        self._check(self.lib.ftk_motif_length_table(self.ctx, self.contig_id(name), int(rid), k, int(shift), lo, hi, b,
+                                                    int(quality_threshold), L.ptr(table), L.ptr(n_kept)))
+        return table, n_kept
+
     # -- co-fragmentation: pairwise KS numerators of length histograms (csrc/ftk_cofrag.hip) ----
     def hist_ks_shape(self):
         """``(T, chunk)`` of the tiled pair kernel (``ftk_hist_ks_shape``): the edge of the pair tile one workgroup

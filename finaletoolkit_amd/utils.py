@@ -17,7 +17,7 @@ from .exceptions import InvalidInputError
 from .source import get_engine, open_source
 
 __all__ = ["chrom_sizes_to_list", "chrom_sizes_to_dict", "get_intervals", "overlaps", "frags_in_region", "frag_generator",
-           "frag_array", "frag_export", "frag_filter", "frag_gc_coverage", "frag_site_profile", "frag_vplot", "VPlot", "frag_ocf", "OCF", "frag_wps_spectrum", "WpsSpectrum", "frag_wps_peaks", "WpsPeaks", "frag_preferred_ends", "PreferredEnds", "preferred_end_thresholds", "frag_hotspots", "IfsHotspots", "ifs_thresholds", "frag_end_context", "EndContext", "read_sites", "gc_weights", "read_gc_bias_table", "read_region_mask", "agg_bw", "gen_kmers", "reverse_complement", "validate_compatible_contigs", "valid_interval",
+           "frag_array", "frag_export", "frag_filter", "frag_gc_coverage", "frag_site_profile", "frag_vplot", "VPlot", "frag_ocf", "OCF", "frag_wps_spectrum", "WpsSpectrum", "frag_wps_peaks", "WpsPeaks", "frag_preferred_ends", "PreferredEnds", "preferred_end_thresholds", "frag_hotspots", "IfsHotspots", "ifs_thresholds", "frag_end_context", "EndContext", "frag_motif_lengths", "MotifLengths", "read_sites", "gc_weights", "read_gc_bias_table", "read_region_mask", "agg_bw", "gen_kmers", "reverse_complement", "validate_compatible_contigs", "valid_interval",
            "_none_eq", "_none_geq", "_none_leq"]
 
 FragTuple = Tuple[str, int, int, int, bool]
@@ -1769,6 +1769,119 @@ def frag_end_context(input_file, reference_file, output_file=None, contig=None, 
         writers.write_end_context_rows(os.fspath(output_file), res)
     if verbose:
         sys.stderr.write(f"frag_end_context: {int(n_kept.sum())} fragments in {time.time() - t0:.3f} s\n")
+    return res
+
+
+class MotifLengths(NamedTuple):
+    """Result of ``frag_motif_lengths``: end-motif (or breakpoint-motif) counts per fragment length row and per kind of
+    reading (0: the U end on the + strand, 1: the D end on the - strand).  Row ``r`` holds the lengths ``min_length + r *
+    length_bin .. min_length + (r + 1) * length_bin - 1``; column ``4 ** k`` counts the readings with an N or off the contig."""
+    table: np.ndarray        # int64 (2, n_rows, 4 ** k + 1): motifs in the order of gen_kmers(k), then "undefined"
+    n_kept: np.ndarray       # int64 per row: the kept fragments; every row table[kind, r] sums to n_kept[r]
+    k: int
+    kind: str                # "end" or "breakpoint"
+    min_length: int          # the first length of row 0
+    length_bin: int          # lengths per row
+    skipped_contigs: tuple   # contigs of the input the reference does not hold
+
+    def lengths(self) -> np.ndarray:
+        """int64 per row: the first length of the row."""
+        return int(self.min_length) + int(self.length_bin) * np.arange(len(self.n_kept), dtype=np.int64)
+
+    def motifs(self) -> list:
+        """The names of the first ``4 ** k`` columns: ``gen_kmers(k, "ACGT")``."""
+        return gen_kmers(int(self.k), "ACGT")
+
+    def frequency(self) -> np.ndarray:
+        """float64 ``(2, n_rows, 4 ** k)``: each motif's share among the defined motifs of its row; NaN where a row has none."""
+        count = np.asarray(self.table)[..., :-1].astype(np.float64)
+        total = count.sum(axis=-1, keepdims=True)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return np.where(total > 0, count / total, np.nan)
+
+    def mds(self) -> np.ndarray:
+        """float64 ``(3, n_rows)``: the motif diversity score ``-sum f ln f / ln(4 ** k)`` (``0 ln 0 = 0``) of the U ends, of
+        the D ends and of both pooled, per row; NaN where a row has no defined motif."""
+        t = np.asarray(self.table)[..., :-1].astype(np.float64)
+        count = np.concatenate([t, t.sum(axis=0, keepdims=True)], axis=0)
+        total = count.sum(axis=-1, keepdims=True)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            f = np.where(total > 0, count / total, np.nan)
+            logs = np.log(f, out=np.zeros_like(f), where=f > 0)  # (NaN > 0 is False: the NaN comes back through f * logs)
+        return (0.0 - (f * logs).sum(axis=-1)) / np.log(4.0 ** int(self.k))  # (0.0 - x: a single motif gives 0.0, not -0.0)
+
+    def pooled(self, lo: int, hi: int) -> np.ndarray:
+        """int64 ``(2, 4 ** k + 1)``: the rows of the lengths ``lo .. hi`` summed - what an end-motif count restricted to
+        that size selection gives.  ``lo`` must start a row and ``hi`` end one (the last row may be narrower than
+        ``length_bin``: any ``hi`` inside it ends it)."""
+        lo, hi, first, b = int(lo), int(hi), int(self.min_length), int(self.length_bin)
+        last = first + b * len(self.n_kept) - 1
+        if lo > hi or lo < first or hi > last or (lo - first) % b or ((hi + 1 - first) % b and hi <= last - b):
+            raise ValueError(f"invalid length range ({lo}, {hi}): whole rows of {b} lengths within {first} .. {last}")
+        return np.asarray(self.table)[:, (lo - first) // b:(hi - first) // b + 1].sum(axis=1)
+
+
+def _check_motif_length_args(output_file, summary_file, k, kind, min_length, max_length, length_bin):
+    from . import _lib as L
+    from . import writers
+    k, lo, hi, b = int(k), int(min_length), int(max_length), int(length_bin)
+    if not 1 <= k <= L.MOTIFLEN_MAX_K:
+        raise ValueError(f"invalid k ({k}): 1 .. {L.MOTIFLEN_MAX_K}")
+    if kind not in ("end", "breakpoint"):
+        raise ValueError(f"invalid kind ({kind!r}): 'end' or 'breakpoint'")
+    if kind == "breakpoint" and k % 2:
+        raise ValueError(f"invalid k ({k}): a breakpoint motif has k / 2 bases either side of the end, k must be even")
+    if lo < 1 or hi < lo or hi > 1 << 30 or b < 1:
+        raise ValueError(f"invalid lengths ({lo} .. {hi} in rows of {b}): 1 <= min_length <= max_length <= 2**30, length_bin >= 1")
+    n_rows = (hi - lo) // b + 1
+    if n_rows > L.MOTIFLEN_MAX_ROWS:
+        raise ValueError(f"invalid lengths ({lo} .. {hi} in rows of {b}): {n_rows} rows, at most {L.MOTIFLEN_MAX_ROWS}")
+    for what, path in (("output_file", output_file), ("summary_file", summary_file)):
+        if path is not None and not str(path).endswith(writers.MOTIF_LENGTH_SUFFIXES):
+            raise ValueError(f"{what} should have .tsv or .tsv.gz as suffix")
+    return k, (0 if kind == "end" else -(k // 2)), lo, hi, b, n_rows
+
+
+def frag_motif_lengths(input_file, reference_file, output_file=None, summary_file=None, contig=None, k: int = 4, kind: str = "end",
+                       min_length: int = 1, max_length: int = 1000, length_bin: int = 1, quality_threshold: int = 30,
+                       workers=None, verbose=False) -> MotifLengths:
+    """End-motif counts of ``input_file`` against ``reference_file`` (``.2bit`` or FASTA) per fragment length: the table
+    behind "motif frequency against fragment size" and the motif diversity score per length, counted on the GPU in one
+    pass per contig as the input is decoded.
+
+    A fragment ``[s, e)`` of length ``L`` with ``mapq >= quality_threshold`` and ``min_length <= L <= max_length`` falls
+    into row ``(L - min_length) // length_bin`` (at most 1024 rows) and gives two readings of ``k`` bases (1 .. 4): the U end
+    on the + strand, ``base(s + shift + i)``, and the D end on the - strand, ``complement(base(e - 1 - shift - i))``, ``i
+    = 0 .. k-1``.  ``kind="end"``: ``shift = 0``, the end motifs; ``kind="breakpoint"`` (even ``k``): ``shift = -k // 2``, the
+    breakpoint motifs - the two k-mers ``end_motifs`` / ``breakpoint_motifs`` read.  A reading with an N (a 2bit N block, a
+    FASTA byte other than ACGTacgt) or a base off the contig counts in the last column, "undefined"; no fragment is dropped.
+
+    Contigs of the input that the reference lacks are skipped with one ``UserWarning`` and listed in ``skipped_contigs``.
+    Returns a ``MotifLengths``: see its ``lengths``, ``motifs``, ``frequency``, ``mds`` and ``pooled``.  ``output_file``
+    (``.tsv`` / ``.tsv.gz``): ``writers.write_motif_length_rows``; ``summary_file``: ``writers.write_motif_length_summary``."""
+    import os
+    import sys
+    import time
+
+    from . import writers
+    k, shift, lo, hi, b, n_rows = _check_motif_length_args(output_file, summary_file, k, kind, min_length, max_length, length_bin)
+    t0 = time.time()
+    table = np.zeros((2, n_rows, 4 ** k + 1), np.int64)
+    n_kept = np.zeros(n_rows, np.int64)
+
+    def one_contig(eng, key, rid, name, size):
+        t, kept = eng.motif_length_table(key, rid, k, shift, lo, hi, b, quality_threshold)
+        table[...] += t
+        n_kept[...] += kept
+        return f"{int(kept.sum())} fragments"
+    missing = _over_reference_contigs("frag_motif_lengths", input_file, reference_file, contig, workers, verbose, one_contig)
+    res = MotifLengths(table, n_kept, k, str(kind), lo, b, missing)
+    if output_file is not None:
+        writers.write_motif_length_rows(os.fspath(output_file), res)
+    if summary_file is not None:
+        writers.write_motif_length_summary(os.fspath(summary_file), res)
+    if verbose:
+        sys.stderr.write(f"frag_motif_lengths: {int(n_kept.sum())} fragments in {time.time() - t0:.3f} s\n")
     return res
 
 

@@ -552,7 +552,55 @@ def write_end_context_rows(output_file: str, res) -> None:
     _emit(output_file, end_context_text(res), (".tsv",), (".tsv.gz",), message)
 
 
-COFRAG_TRACK_HEADER = "contig\tstart\tstop\tn_frags\toverflow\tvalid\tpc1\n"
+MOTIF_LENGTH_SUFFIXES = (".tsv", ".tsv.gz")
+MOTIF_LENGTH_HEADER = "length_lo\tlength_hi\tend\tmotif\tcount\tfrequency\n"
+MOTIF_LENGTH_SUMMARY_HEADER = "length_lo\tlength_hi\tn_frags\tundefined_u\tundefined_d\tmds_u\tmds_d\tmds\n"
+
+
+def motif_length_text(res) -> str:
+    """The rows of a ``utils.MotifLengths``: the header ``length_lo length_hi end motif count frequency``, then one row per
+    non-zero cell - per length row (the lengths ``length_lo .. length_hi``, both inclusive), per end (``U`` / ``D``) and per
+    motif in the order of ``gen_kmers``, the undefined column last, written ``N``.  ``frequency`` is ``repr(float)`` of
+    ``res.frequency()``, ``nan`` for N."""
+    table, names = np.asarray(res.table), list(res.motifs()) + ["N"]
+    freq = np.concatenate([res.frequency(), np.full(table.shape[:2] + (1,), np.nan)], axis=-1)
+    first, b = res.lengths(), int(res.length_bin)
+    rows = [MOTIF_LENGTH_HEADER]
+    for r in np.flatnonzero(table.any(axis=(0, 2))):
+        for kind in range(2):
+            head = f"{int(first[r])}\t{int(first[r]) + b - 1}\t{'UD'[kind]}\t"
+            rows += [f"{head}{names[m]}\t{int(table[kind, r, m])}\t{float(freq[kind, r, m])!r}\n" for m in np.flatnonzero(table[kind, r])]
+    return "".join(rows)
+
+
+def motif_length_summary_text(res) -> str:
+    """One row per length row of a ``utils.MotifLengths`` that holds a fragment: the header ``length_lo length_hi n_frags
+    undefined_u undefined_d mds_u mds_d mds``, the undefined readings of either end and ``repr(float)`` of ``res.mds()``."""
+    table, mds = np.asarray(res.table), res.mds()
+    first, b = res.lengths(), int(res.length_bin)
+    rows = [MOTIF_LENGTH_SUMMARY_HEADER]
+    rows += [f"{int(first[r])}\t{int(first[r]) + b - 1}\t{int(res.n_kept[r])}\t{int(table[0, r, -1])}\t{int(table[1, r, -1])}\t"
+             f"{float(mds[0, r])!r}\t{float(mds[1, r])!r}\t{float(mds[2, r])!r}\n" for r in np.flatnonzero(np.asarray(res.n_kept))]
+    return "".join(rows)
+
+
+def write_motif_length_rows(output_file: str, res) -> None:
+    """``motif_length_text`` to ``output_file``: ``.tsv`` as text, ``.tsv.gz`` as gzip."""
+    message = "output_file should have .tsv or .tsv.gz as suffix"
+    if not output_file.endswith(MOTIF_LENGTH_SUFFIXES):
+        raise ValueError(message)
+    _emit(output_file, motif_length_text(res), (".tsv",), (".tsv.gz",), message)
+
+
+def write_motif_length_summary(output_file: str, res) -> None:
+    """``motif_length_summary_text`` to ``output_file``: ``.tsv`` as text, ``.tsv.gz`` as gzip."""
+    message = "summary_file should have .tsv or .tsv.gz as suffix"
+    if not output_file.endswith(MOTIF_LENGTH_SUFFIXES):
+        raise ValueError(message)
+    _emit(output_file, motif_length_summary_text(res), (".tsv",), (".tsv.gz",), message)
+
+
+COFRAG_TRACK_HEADER ="contig\tstart\tstop\tn_frags\toverflow\tvalid\tpc1\n"
 COFRAG_PAIRS_HEADER = "contig\tstart_i\tstart_j\tn_i\tn_j\tks_num\td\tat\tz\tneglog10_p\tcorr\n"
 
 

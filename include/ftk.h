@@ -1143,6 +1143,44 @@ int ftk_cofrag(ftk_ctx* ctx, int contig_id, const int32_t* w_start, const int32_
                int32_t len_lo, int32_t n_bins, int64_t* k_out, int32_t* at_out, int64_t* n_out, int64_t* overflow_out);
 int ftk_hist_ks_shape(int32_t* tile_out, int32_t* chunk_out);
 
+/* ---- motif x length: end-motif counts per fragment length (csrc/ftk_motiflen.hip) -----------------------------
+ * The joint table behind "motif frequency against fragment size" and the motif diversity score per length: what
+ * ftk_motif_counts gives per window without a length filter, per length row of one contig, in one pass.
+ *
+ * Bases.  base(q) and comp(x) are those of the "end context" section above: A C G T = 0 .. 3, N = 4 (outside
+ * [0, chrom_len), inside a 2bit N block, a FASTA byte other than ACGTacgt), comp(x) = 3 - x for x < 4, comp(4) = 4.
+ *
+ * Which fragments count.  A fragment [s, e) with L = e - s is KEPT when mapq >= mapq_min and len_lo <= L <= len_hi.  Its
+ * row is r = (L - len_lo) / len_bin; there are n_rows = (len_hi - len_lo) / len_bin + 1 rows (the last one may be
+ * narrower than len_bin).
+ *
+ * Readings.  Every kept fragment gives two readings of k bases; `shift` moves the anchor:
+ *    kind 0 (U end, + strand):  u_i = base(s + shift + i),             i = 0 .. k-1
+ *    kind 1 (D end, - strand):  d_i = comp(base(e - 1 - shift - i)),   i = 0 .. k-1
+ * The code of a reading is sum x_i 4^(k-1-i): the first base is most significant, in the ACGT order of gen_kmers.  When
+ * any base of the reading is 4 the reading goes to column 4^k ("undefined") instead.  shift = 0 gives the end motifs,
+ * shift = -k/2 the breakpoint motifs: with fwd_offset = shift and rev_offset = -k - shift these are exactly the two k-mers
+ * ftk_motif_counts reads.  Readings may run past the fragment's other end (L < k): that is reference sequence and it is
+ * counted.
+ *
+ * The table.
+ *    out[kind][r][code] += 1      int64, shape [2][n_rows][4^k + 1]
+ *    n_kept_out[r]                int64, kept fragments of row r
+ * Every row out[kind][r] therefore sums to n_kept_out[r], for both kinds.  Unlike ftk_motif_counts nothing is dropped and
+ * nothing is an error at the contig's ends: an off-contig base makes the reading undefined, and that is all.
+ *   ftk_motif_length_table      the table and n_kept_out[n_rows] of a resident contig; outputs host or device, every cell
+ *                               written by the call; an empty contig gives zeros.
+ *   ftk_motif_length_lds_rows   rows one workgroup keeps in LDS (the further rows of a call go to further rows of the
+ *                               grid); 0 for k outside [1, FTK_MOTIFLEN_MAX_K].
+ * FTK_ERR_INVALID: a NULL pointer, a reference without layout, chrom_len >= 2^30, k outside [1, FTK_MOTIFLEN_MAX_K],
+ * |shift| > 4, len_lo < 1, len_hi < len_lo, len_hi > 2^30, len_bin < 1, n_rows > FTK_MOTIFLEN_MAX_ROWS;
+ * FTK_ERR_NO_CONTIG: an unknown contig or reference.  A failing call writes nothing. */
+#define FTK_MOTIFLEN_MAX_K 4
+#define FTK_MOTIFLEN_MAX_ROWS 1024
+int ftk_motif_length_table(ftk_ctx* ctx, int contig_id, int ref_id, int32_t k, int32_t shift, int32_t len_lo, int32_t len_hi,
+                           int32_t len_bin, int32_t mapq_min, int64_t* table_out, int64_t* n_kept_out);
+int ftk_motif_length_lds_rows(int32_t k);
+
 /* ---- multi-GPU (SURVEY 8-e, 8-b's export list) -------------------------------------------------
  * One process and one ftk_ctx per GPU.  Contigs / genome runs are dealt to the ranks by the host and every window,
  * bin and base depends on its own contig's fragments only, so the data path has no collective.  What remains are the

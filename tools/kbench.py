@@ -768,6 +768,32 @@ if "endcontext" in which:
     del os.environ["FTK_CONTEXT_ARRANGE"]
     print("endcontext checksum", int(table.sum()), int(table[..., 20:].sum()), int(eng.ref_context(ride, 0, size).sum()),
           "(share of the LDS estimate = the us above / the measured us)")
+if "motiflen" in which:
+    # Motif x length at k = 4 over the lengths 1 .. 1000, against the 2bit image of KBENCH=gcbias / endcontext: the whole call
+    # (table zeroed, both passes, 4 MB copied to the host).  The bytes it is held against: the (start, end, mapq) columns once
+    # for the row pass and once per POPULATED band of the table pass (an empty band returns before it reads a column), and
+    # two 32-byte sectors of the image per kept fragment (one per end).
+    rng = np.random.default_rng(7)
+    packed = rng.integers(0, 256, (size + 3) // 4, dtype=np.uint8)
+    ridm = eng.ref_upload(("kb", "gcbias2bit"), packed, 1)
+    eng.ref_set_layout(ridm, size, 0, 0, [10_000_000], [10_050_000])
+    K, LO, HI = 4, 1, 1000
+    table, kept = eng.motif_length_table("c", ridm, K, 0, LO, HI, 1, 30)
+
+    def call_bytes(k):
+        band = eng.motif_length_lds_rows(k)
+        populated = sum(1 for r0 in range(0, len(kept), band) if kept[r0:r0 + band].any())
+        return band, populated, 9 * n * (1 + populated) + 64 * int(kept.sum())
+
+    band, populated, nbytes = call_bytes(K)
+    print(f"motiflen: {n} fragments, {int(kept.sum())} kept, k = {K}, rows {LO} .. {HI}, bands of {band} rows: {populated} of "
+          f"{-(-len(kept) // band)} populated, {nbytes} algorithmic bytes", flush=True)
+    for _ in range(2):  # twice: the spread between the two passes is the noise
+        timeit(lambda: eng.motif_length_table("c", ridm, K, 0, LO, HI, 1, 30), "motif x length k=4 1-1000", nbytes)
+        timeit(lambda: eng.motif_length_table("c", ridm, 2, -1, LO, HI, 1, 30), "motif x length k=2 breakpoint", call_bytes(2)[2])
+    assert np.array_equal(table.sum(axis=-1), np.stack([kept, kept]))
+    print("motiflen checksum", int(table.sum()), int(table[..., -1].sum()), int((table[0] * np.arange(4 ** K + 1)).sum()),
+          int((table[1] * np.arange(4 ** K + 1)).sum()))
 if "cofrag" in which:
     # Co-fragmentation: N = 2490 bins of 100 kb (chr1 at that bin size), lengths 0 .. 1000.  The work is pair steps, not bytes:
     # N (N + 1) / 2 pairs x n_bins lengths, each two 32 x 32 -> 64 multiplies, a 64-bit subtraction, an absolute value, a compare
